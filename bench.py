@@ -15,7 +15,10 @@ descriptors) and a match stream, over four buffer sets: launch g's matcher
 overlaps the next launches' extraction (every launch does all of its work; the
 timed region ends with a device synchronize).
 
-Prints ONE JSON line on rank 0 (driver contract) with `roofline` (dominant
+Prints ONE JSON line on rank 0 (driver contract).  A plain run sets up, warms
+up, times the steps, writes the last step's outputs when --dump-outputs DIR is
+given, and prints the headline (`value`, `ms_per_step`, `config`).  --full adds
+everything else to the line, measured after the timed region: `roofline` (dominant
 kernel, HIP-event timed alone after the timed region, and pipelined in a
 profiled pass of the same launches after it -- no event sits inside the timed
 region; HBM bytes per SURVEY §8(d) as
@@ -207,6 +210,51 @@ def snapshot_sample(sets, g_end, n_sets, n_batches, B, orb, per_set=16):
             out.append((b * B + i, k, st["desc"][i, :max(n, 0)].cpu().numpy(),
                         st["match"][i, :max(n, 0)].cpu().numpy(), int(st["nmatch"][i].item())))
     return out
+
+
+DUMP_FRAMES = 256  # frames --dump-outputs keeps (~160 B x capacity each as float32)
+
+
+def dump_outputs(out_dir, sets, counts, g_end, n_sets, n_batches, B, orb, torch, rank, seed):
+    """--dump-outputs: what the last timed step handed its caller, as float32
+    .npy files.  `keypoint_counts` covers every frame of the step; keypoints,
+    descriptors and SearchByProjection's assignments are kept for a fixed,
+    seeded sample of DUMP_FRAMES frames among those whose buffers the step's
+    last launches left resident (a buffer set is rewritten every n_sets
+    launches).  Rows past a frame's keypoint count are zeroed (kp_match: -1): a
+    caller reads only the first `count` of them."""
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    resident = list(range(g_end - min(n_sets, n_batches), g_end))
+    pool = np.array([(gg, i) for gg in resident for i in range(B)], np.int64)
+    rng = np.random.default_rng([seed & 0xFFFFFFFF, rank, 0xD0])
+    cap = sets[0]["kps"].shape[1]
+    keep = min(DUMP_FRAMES, len(pool), (60 << 20) // (cap * 4 * (7 + 32 + 1)))  # < 64 MB in all
+    pick = pool[np.sort(rng.choice(len(pool), size=keep, replace=False))]
+    frame, kps, desc, match, nmatch = [], [], [], [], []
+    for gg in resident:
+        idx = pick[pick[:, 0] == gg, 1]
+        if not len(idx):
+            continue
+        st, b = sets[gg % n_sets], gg % n_batches
+        di = torch.from_numpy(idx).to(st["kps"].device)
+        n = st["cnt"][di].cpu().numpy()
+        live = np.arange(st["kps"].shape[1])[None, :] < n[:, None]
+        k = st["kps"][di].cpu().numpy().view(orb.KEYPOINT_DTYPE)[..., 0]
+        kf = np.stack([k[f].astype(np.float32) for f in orb.KEYPOINT_DTYPE.names], axis=-1)
+        frame.append(b * B + idx)
+        kps.append(kf * live[..., None])
+        desc.append(st["desc"][di].cpu().numpy().astype(np.float32) * live[..., None])
+        match.append(np.where(live, st["match"][di].cpu().numpy(), -1).astype(np.float32))
+        nmatch.append(st["nmatch"][di].cpu().numpy().astype(np.float32))
+    arrays = {"keypoint_counts": counts.cpu().numpy().astype(np.float32),
+              "sample_frames": np.concatenate(frame).astype(np.float32),
+              "keypoints": np.concatenate(kps), "descriptors": np.concatenate(desc),
+              "kp_match": np.concatenate(match), "nmatches": np.concatenate(nmatch)}
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    suffix = "" if rank == 0 else f"_rank{rank}"
+    for name, a in arrays.items():
+        np.save(out_dir / f"{name}{suffix}.npy", a)
 
 
 def cpu_leg(imgs, maps, sample, args, scale, timed):
@@ -892,6 +940,15 @@ def main():
     ap.add_argument("--steps", type=int, default=60,
                     help="timed steps; one step = one pass over the --frames resident frames")
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything else the benchmark measures "
+                         "and checks: the per-frame drop-in timing, the kernel table and roofline, "
+                         "the host-input leg, C3 / C5 / latency, the oracle parity sample and the "
+                         "CPU baseline (a plain run times the headline steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed step's outputs (keypoint counts of every frame; "
+                         "keypoints, descriptors and matches of a fixed sample of frames) to "
+                         "DIR/<name>.npy as float32")
     ap.add_argument("--frames", type=int, default=8192,
                     help="distinct resident frames per GPU (a step processes each once)")
     ap.add_argument("--batch", type=int, default=1024,
@@ -912,18 +969,18 @@ def main():
                          "in a profiled pipelined pass after it)")
     ap.add_argument("--cpu-all-seconds", type=float, default=8.0,
                     help="wall-clock sample of the all-cores oracle rate (0: skip)")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the C3 / C5 extra keys")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="--full: skip the C3 / C5 extra keys")
     ap.add_argument("--dropin-prepare", metavar="DIR", help=argparse.SUPPRESS)
     ap.add_argument("--no-dropin", action="store_true",
-                    help="skip the per-frame drop-in timing (tests/integration_run harness)")
+                    help="--full: skip the per-frame drop-in timing (tests/integration_run harness)")
     ap.add_argument("--threads", type=int, default=16, help="host threads for input synthesis")
     ap.add_argument("--seed", type=int, default=0x4B495454)
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl (= RCCL, the measured path); gloo only for the multi-rank test "
                          "on one GPU (ORB_BENCH_DEVICE pins every rank to one device)")
     ap.add_argument("--host-frames", type=int, default=2048,
-                    help="pinned host frames the host-input leg cycles through (0: skip the leg)")
+                    help="--full: pinned host frames the host-input leg cycles through (0: skip the leg)")
     ap.add_argument("--host-passes", type=int, default=4,
                     help="timed passes of the host-input leg over --frames frames")
     ap.add_argument("--lanes", type=int, default=int(os.environ.get("ORB_BENCH_LANES", "2")),
@@ -943,13 +1000,15 @@ def main():
     if args.dropin_prepare:  # child of dropin_leg
         dropin_prepare(args, args.dropin_prepare)
         return
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
     world, spawn = resolve_world(args.gpus, os.environ)
     if spawn:  # before any torch / HIP call in this process
         raise SystemExit(launch_ranks(world))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
     dropin = None
-    if rank == 0 and world == 1 and not args.no_dropin and local == 0 \
+    if args.full and rank == 0 and world == 1 and not args.no_dropin and local == 0 \
             and os.environ.get("ORB_BENCH_DEVICE") is None:
         dropin = dropin_leg(args)  # first: before this process touches the GPU
     import torch
@@ -1135,7 +1194,7 @@ def main():
         raise RuntimeError("timed-step keypoint counts differ from the untimed pass")
     # the timed pipeline's own outputs for 64 sampled frames of its last launches
     # (keypoints, descriptors, matches), checked against the oracle in the CPU leg
-    sample = snapshot_sample(sets, g, NS, NB, B, orb)
+    sample = snapshot_sample(sets, g, NS, NB, B, orb) if args.full else None
     gather_ok = None
     if dist is not None:  # the gathered counts of the last step hold this rank's own
         k = ((g - 1) // NB) % 2
@@ -1147,6 +1206,62 @@ def main():
             ok = ok.to(dev)
         dist.all_reduce(ok, op=dist.ReduceOp.MIN)
         gather_ok = bool(ok.item())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, sets, step_counts[last_k], g, NS, NB, B, orb, torch, rank,
+                     args.seed)
+    n_kp = float(cnt_h.mean())
+    nmatch = float(sets[0]["nmatch"].float().mean().item())
+    total_frames = D * args.steps * world
+    if dist is None:
+        par = "single rank; no collective (one process, one GPU)"
+    else:
+        par = (f"frames sharded over {world} rank(s); one "
+               f"{'RCCL' if args.dist_backend == 'nccl' else 'gloo'} all-gather of the step's "
+               f"per-frame keypoint counts per step")
+    if step_diag:
+        gpu_ms = [step_ev[i - 1].elapsed_time(step_ev[i]) for i in range(1, len(step_ev))]
+        host_ms = [(host_q[i] - t0) * 1e3 for i in range(len(host_q))]
+        print(json.dumps({"step_diag": {"gpu_step_ms": [round(v, 3) for v in gpu_ms],
+                                        "host_queued_ms": [round(v, 2) for v in host_ms]}}),
+              file=sys.stderr)
+    result = {
+        "metric": METRIC,
+        "value": total_frames / elapsed,
+        "unit": "frames/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "u8",
+        "data": "synthetic",
+        "config": {
+            "workload": f"C4: {W}x{H} KITTI-shaped synthetic stream, {NF} feat/frame, "
+                        f"SearchByProjection vs {M}-point local map per frame",
+            "frames_per_gpu_per_step": D,
+            "distinct_frames_per_gpu": D,
+            "frames_per_launch": B,
+            "extraction_lanes": f"{L} extractor handle(s) on {L} stream(s), launches "
+                                "round-robin; SearchByProjection on " +
+                                ("one match stream" if MSN == 1 else
+                                 f"{MSN} match streams (a matcher handle each), launches round-robin"),
+            "timed_region_s": elapsed,
+            "inputs": "frames resident in HBM before the timed region (device-resident rate; "
+                      "the PCIe-inclusive drop-in rate is `host_input`, with --full)",
+            "parallelism": par,
+            "count_gather_verified": gather_ok,
+            "mean_keypoints_per_frame": n_kp,
+            "mean_matches_per_frame": nmatch,
+        },
+    }
+    if not args.full:  # a plain run: the headline figure only
+        if rank == 0:
+            print(json.dumps(result), flush=True)
+        if dist is not None:
+            dist.destroy_process_group()
+        return
 
     if args.timed_events != "both":
         # the profiled pipelined pass: the same launches, stage events on
@@ -1193,8 +1308,6 @@ def main():
         kern[name] = (ms, n)
     ext.profile(False)
     matcher.profile(False)
-    n_kp = float(cnt_h.mean())
-    nmatch = float(sets[0]["nmatch"].float().mean().item())
     rl = kern.get("k_pyr_resize", (0, 0))[1] / max(n_prof, 1)
     alg = algorithmic_bytes(W, H, scale, 8, n_kp, M, resize_launches=round(rl) if rl else None)
     # every kernel alone (one stream, every stage after the previous one, no
@@ -1230,7 +1343,6 @@ def main():
     hbm_gbs = t["alg_GBps_isolated"]
     traffic, traffic_src = measured_traffic(dom, B)
     valu = valu_issue(dom, B, dom_ms_per_launch)
-    total_frames = D * args.steps * world
     # the HBM roofline of the dominant kernel is the primary
     # fraction (algorithmic bytes per launch / its launch time alone); its VALU
     # issue rate against the guide's peak sits beside it (the integer kernels of
@@ -1278,49 +1390,7 @@ def main():
         del d_img
         host = host_input_leg(orb, torch, ext, matcher, imgs, args, dev, sets, d_mps, d_mpd,
                               d_lock, d_nmps, scale, cap, dist, rank)
-    if dist is None:
-        par = "single rank; no collective (one process, one GPU)"
-    else:
-        par = (f"frames sharded over {world} rank(s); one "
-               f"{'RCCL' if args.dist_backend == 'nccl' else 'gloo'} all-gather of the step's "
-               f"per-frame keypoint counts per step")
-    if step_diag:
-        gpu_ms = [step_ev[i - 1].elapsed_time(step_ev[i]) for i in range(1, len(step_ev))]
-        host_ms = [(host_q[i] - t0) * 1e3 for i in range(len(host_q))]
-        print(json.dumps({"step_diag": {"gpu_step_ms": [round(v, 3) for v in gpu_ms],
-                                        "host_queued_ms": [round(v, 2) for v in host_ms]}}),
-              file=sys.stderr)
-    result = {
-        "metric": METRIC,
-        "value": total_frames / elapsed,
-        "unit": "frames/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": elapsed / args.steps * 1e3,
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "u8",
-        "data": "synthetic",
-        "config": {
-            "workload": f"C4: {W}x{H} KITTI-shaped synthetic stream, {NF} feat/frame, "
-                        f"SearchByProjection vs {M}-point local map per frame",
-            "frames_per_gpu_per_step": D,
-            "distinct_frames_per_gpu": D,
-            "frames_per_launch": B,
-            "extraction_lanes": f"{L} extractor handle(s) on {L} stream(s), launches "
-                                "round-robin; SearchByProjection on " +
-                                ("one match stream" if MSN == 1 else
-                                 f"{MSN} match streams (a matcher handle each), launches round-robin"),
-            "timed_region_s": elapsed,
-            "inputs": "frames resident in HBM before the timed region (device-resident rate; "
-                      "the PCIe-inclusive drop-in rate is `host_input`)",
-            "parallelism": par,
-            "count_gather_verified": gather_ok,
-            "mean_keypoints_per_frame": n_kp,
-            "mean_matches_per_frame": nmatch,
-        },
+    result.update({
         "roofline": roof,
         "kernels_ms_per_launch": {k: v[0] / max(v[1], 1) for k, v in kern.items()},
         "kernels": table,
@@ -1328,7 +1398,7 @@ def main():
         "extraction_call_ms_per_launch": call_ms / max(call_n, 1),
         "fast_side_stream_ms_per_launch": side_ms,
         "host_input": host,
-    }
+    })
     if rank == 0 and world == 1 and not args.no_secondary:
         if args.host_frames <= 0:
             del d_img

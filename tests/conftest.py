@@ -50,3 +50,13 @@ def gpu(orb):
 
 
 REFERENCE = Path(os.environ.get("ORB_REFERENCE", "/root/reference"))
+
+
+def reference_present(*parts):
+    """True where REFERENCE/parts is a file this user can read (a tree that is
+    absent, or mounted where this user may not look, counts as not present)."""
+    p = REFERENCE.joinpath(*parts)
+    try:
+        return p.is_file() and os.access(p, os.R_OK)
+    except OSError:
+        return False

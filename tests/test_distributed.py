@@ -77,3 +77,50 @@ def test_bench_gpus_mismatch_exits_nonzero():
     r = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "2"], env=env,
                        capture_output=True, text=True, timeout=120)
     assert r.returncode != 0 and "WORLD_SIZE" in r.stderr
+
+
+def test_bench_dump_outputs_sample(tmp_path, orb):
+    """--dump-outputs: float32 arrays of the last step's resident launches, the
+    same fixed sample on every call, rows past a frame's count blanked."""
+    import numpy as np
+
+    import bench
+
+    B, cap, NS, NB = 96, 37, 4, 8
+    rng = np.random.default_rng(1)
+    sets = []
+    for _ in range(NS):
+        k = np.zeros((B, cap), orb.KEYPOINT_DTYPE)
+        k["x"], k["octave"], k["class_id"] = rng.random((B, cap)), rng.integers(0, 8, (B, cap)), -1
+        sets.append(dict(kps=torch.from_numpy(k.view(np.int32).reshape(B, cap, 7)),
+                         desc=torch.from_numpy(rng.integers(1, 256, (B, cap, 32), dtype=np.uint8)),
+                         cnt=torch.from_numpy(rng.integers(0, cap + 1, B).astype(np.int32)),
+                         match=torch.from_numpy(rng.integers(0, 5000, (B, cap)).astype(np.int32)),
+                         nmatch=torch.from_numpy(rng.integers(0, cap, B).astype(np.int32))))
+    counts = torch.arange(B * NB, dtype=torch.int32)
+    g_end = 3 * NB  # three steps of NB launches: launches 20..23 are resident (batches 4..7)
+    for d in ("a", "b"):
+        bench.dump_outputs(tmp_path / d, sets, counts, g_end, NS, NB, B, orb, torch, 0, 7)
+    a = {p.stem: np.load(p) for p in (tmp_path / "a").glob("*.npy")}
+    assert set(a) == {"keypoint_counts", "sample_frames", "keypoints", "descriptors", "kp_match",
+                      "nmatches"}
+    for name, arr in a.items():
+        assert arr.dtype == np.float32 and np.array_equal(arr, np.load(tmp_path / "b" / f"{name}.npy"))
+    assert sum(arr.nbytes for arr in a.values()) <= 64 << 20
+    n = min(bench.DUMP_FRAMES, NS * B)
+    assert a["keypoint_counts"].tolist() == list(range(B * NB))
+    assert a["keypoints"].shape == (n, cap, 7) and a["descriptors"].shape == (n, cap, 32)
+    assert a["kp_match"].shape == (n, cap) and a["nmatches"].shape == (n,)
+    f = a["sample_frames"].astype(int)
+    assert len(set(f)) == n and f.min() >= 4 * B and f.max() < 8 * B
+    for row, fr in enumerate(f):  # each row is that frame's buffer row, cut at its count
+        st, i = sets[(fr // B) % NS], fr % B
+        c = int(st["cnt"][i])
+        assert a["nmatches"][row] == int(st["nmatch"][i])
+        assert np.array_equal(a["descriptors"][row, :c], st["desc"][i, :c].numpy().astype(np.float32))
+        assert np.array_equal(a["kp_match"][row, :c], st["match"][i, :c].numpy().astype(np.float32))
+        k = st["kps"][i].numpy().view(orb.KEYPOINT_DTYPE)[:, 0]
+        assert np.array_equal(a["keypoints"][row, :c, 0], k["x"][:c])
+        assert np.array_equal(a["keypoints"][row, :c, 5], k["octave"][:c].astype(np.float32))
+        assert not a["descriptors"][row, c:].any() and not a["keypoints"][row, c:].any()
+        assert (a["kp_match"][row, c:] == -1).all()

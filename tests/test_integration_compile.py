@@ -5,19 +5,23 @@ integration/ORBmatcher.cc, ORBextractor.cc and FrameStereo.cc replace
 src/ORBmatcher.cc, src/ORBextractor.cc and Frame::ComputeStereoMatches.  OpenCV
 is not installed, so they are syntax-checked against
 tests/integration_stub/orb_slam2_decls.h (declarations only; nothing is linked
-and no reference source is compiled).  When the reference tree is present, the
-stub's ORB_SLAM2 declarations are checked against the reference headers:
-ORBmatcher's declarations are exactly include/ORBmatcher.h's, and every other
-stub declaration (Frame, KeyFrame, MapPoint, ORBextractor members the drop-ins
-use) appears in the reference header, except the documented additions marked
-INTEGRATION CHANGE."""
+and no reference source is compiled).  The stub's ORB_SLAM2 declarations are
+checked against the reference headers: ORBmatcher's declarations are exactly
+include/ORBmatcher.h's, and every other stub declaration (Frame, KeyFrame,
+MapPoint, ORBextractor members the drop-ins use) appears in the reference
+header, except the documented additions marked INTEGRATION CHANGE.  The
+reference's declarations are recorded as digests of their normalised text in
+tests/golden/reference_facts.json (tests/golden/make_reference_facts.py); where
+the reference tree is present the record is first checked against it."""
+import hashlib
+import json
 import re
 import subprocess
 from pathlib import Path
 
 import pytest
 
-from conftest import REFERENCE
+from conftest import REFERENCE, reference_present
 
 ROOT = Path(__file__).resolve().parents[1]
 STUB = ROOT / "tests" / "integration_stub"
@@ -82,20 +86,29 @@ def _ref_decls(header, name):
     return _decls(_class_body(_strip_comments((REFERENCE / "include" / header).read_text()), name))
 
 
-needs_ref = pytest.mark.skipif(not (REFERENCE / "include" / "ORBmatcher.h").exists(),
-                               reason="reference tree not mounted")
+def _digest(decl):
+    return hashlib.sha256(decl.encode()).hexdigest()[:16]
 
 
-@needs_ref
+def _ref_digests(header, name):
+    """Digests of the reference class's normalised declarations, as recorded;
+    the record must equal the reference tree's where that is present."""
+    facts = json.loads((ROOT / "tests" / "golden" / "reference_facts.json").read_text())
+    recorded = facts["declarations"][name]
+    if reference_present("include", header):
+        assert sorted(_digest(d) for d in _ref_decls(header, name)) == recorded
+    return set(recorded)
+
+
 def test_orbmatcher_declarations_are_the_references():
-    assert _stub_decls("ORBmatcher") == _ref_decls("ORBmatcher.h", "ORBmatcher")
+    assert {_digest(d) for d in _stub_decls("ORBmatcher")} == _ref_digests("ORBmatcher.h", "ORBmatcher")
 
 
-@needs_ref
 @pytest.mark.parametrize("name,header", [("ORBextractor", "ORBextractor.h"), ("Frame", "Frame.h"),
                                          ("KeyFrame", "KeyFrame.h"), ("MapPoint", "MapPoint.h")])
 def test_stub_members_exist_in_reference(name, header):
-    missing = _stub_decls(name) - _ref_decls(header, name)
+    ref = _ref_digests(header, name)
+    missing = {d for d in _stub_decls(name) if _digest(d) not in ref}
     assert not missing, missing
 
 

@@ -1,17 +1,47 @@
 """Constants the reference embeds -- its only built-in known answers:
 the rBRIEF sampling table, umax, per-level quotas, scale tables, Appendix B
-level sizes, matcher thresholds.  Checked against the reference source text when
-/root/reference is present (this container), and against the survey's derived
-values always."""
+level sizes, matcher thresholds.  Checked against what was recorded from the
+reference source text (tests/golden/reference_facts.json, written by
+tests/golden/make_reference_facts.py; where the reference tree is present the
+record is first checked against it), and against the survey's derived values."""
+import hashlib
+import json
 import re
 
 import numpy as np
 import pytest
 
-from conftest import PKG_DIR, REFERENCE
+from conftest import PKG_DIR, REFERENCE, reference_present
 
 SRC = REFERENCE / "src" / "ORBextractor.cc"
-needs_ref = pytest.mark.skipif(not SRC.exists(), reason="reference tree not mounted")
+FACTS = json.loads((PKG_DIR.parent / "tests" / "golden" / "reference_facts.json").read_text())
+# constants the reference states in its source text: file -> {name: value}
+STATED = {"src/ORBmatcher.cc": {"TH_HIGH": 100, "TH_LOW": 50, "HISTO_LENGTH": 30},
+          "include/Frame.h": {"FRAME_GRID_ROWS": 48, "FRAME_GRID_COLS": 64},
+          "src/ORBextractor.cc": {"EDGE_THRESHOLD": 19, "HALF_PATCH_SIZE": 15, "PATCH_SIZE": 31}}
+
+
+def pattern_digest(values):
+    return hashlib.sha256(" ".join(str(v) for v in values).encode()).hexdigest()
+
+
+def reference_pattern():
+    text = SRC.read_text(encoding="utf-8", errors="replace")
+    body = text.split("bit_pattern_31_[256*4] =", 1)[1].split("};", 1)[0]
+    body = re.sub(r"/\*.*?\*/", " ", body, flags=re.S)
+    return [int(v) for v in re.findall(r"-?\d+", body)]
+
+
+def reference_constants():
+    """{file: {name: value}} of STATED's names as the reference tree states them."""
+    out = {}
+    for rel, names in STATED.items():
+        text = (REFERENCE / rel).read_text(encoding="utf-8", errors="replace")
+        out[rel] = {}
+        for n in names:
+            m = re.search(r"\b" + n + r"\s*=?\s*(\d+)\b", text)
+            out[rel][n] = int(m.group(1)) if m else None
+    return out
 
 
 def _pattern_header():
@@ -20,13 +50,12 @@ def _pattern_header():
     return [int(v) for v in re.findall(r"-?\d+", body)]
 
 
-@needs_ref
 def test_pattern_table_is_the_reference_table():
-    text = SRC.read_text(encoding="utf-8", errors="replace")
-    body = text.split("bit_pattern_31_[256*4] =", 1)[1].split("};", 1)[0]
-    body = re.sub(r"/\*.*?\*/", " ", body, flags=re.S)
-    ref = [int(v) for v in re.findall(r"-?\d+", body)]
-    assert len(ref) == 1024 and _pattern_header() == ref
+    if reference_present("src", "ORBextractor.cc"):
+        ref = reference_pattern()
+        assert len(ref) == 1024 and pattern_digest(ref) == FACTS["bit_pattern_31_sha256"]
+    mine = _pattern_header()
+    assert len(mine) == 1024 and pattern_digest(mine) == FACTS["bit_pattern_31_sha256"]
 
 
 def test_pattern_table_shape():
@@ -72,11 +101,9 @@ def test_level_sizes(oracle, w, h, sizes):
     assert oracle.level_sizes(w, h) == sizes
 
 
-@needs_ref
 def test_matcher_thresholds_in_reference():
-    m = (REFERENCE / "src" / "ORBmatcher.cc").read_text(encoding="utf-8", errors="replace")
-    assert "TH_HIGH = 100" in m and "TH_LOW = 50" in m and "HISTO_LENGTH = 30" in m
-    f = (REFERENCE / "include" / "Frame.h").read_text(encoding="utf-8", errors="replace")
-    assert re.search(r"FRAME_GRID_ROWS\s+48", f) and re.search(r"FRAME_GRID_COLS\s+64", f)
-    e = SRC.read_text(encoding="utf-8", errors="replace")
-    assert "EDGE_THRESHOLD = 19" in e and "HALF_PATCH_SIZE = 15" in e and "PATCH_SIZE = 31" in e
+    if reference_present("src", "ORBextractor.cc"):
+        assert reference_constants() == FACTS["constants"]
+    assert FACTS["constants"] == STATED
+    abi = (PKG_DIR.parent / "include" / "orb_abi.h").read_text()
+    assert re.search(r"#define ORB_GRID_ROWS 48\b", abi) and re.search(r"#define ORB_GRID_COLS 64\b", abi)

@@ -7,7 +7,7 @@ TAG=$1; shift
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out; mkdir -p "$O"
 OUT=$O/ab_$TAG.jsonl; : > "$OUT"
-ARGS="--no-cpu --no-secondary --frames 2048 --steps 30"
+ARGS="--full --no-cpu --no-secondary --frames 2048 --steps 30"
 timeout -k 10 200 python "$R/bench.py" $ARGS > "$O/ab_base.json" 2>> "$O/ab_$TAG.err" || exit 1
 echo "{\"variant\": \"base\", \"bench\": $(cat "$O/ab_base.json")}" >> "$OUT"
 for v in "$@"; do

@@ -14,18 +14,18 @@ O=$R/gpurun_out
 L0LIB=$R/orb_slam2-chinese-annotation_amd/lib/variants/l0inline.so
 mkdir -p "$O"
 cd "$R"
-timeout -k 10 400 python bench.py > "$O/bench_$TAG.json" 2> "$O/bench_$TAG.err"
+timeout -k 10 400 python bench.py --full > "$O/bench_$TAG.json" 2> "$O/bench_$TAG.err"
 cd /tmp && export TMPDIR=/tmp
 # the kernel-trace pass runs the bench's own timed workload (8192 resident
 # frames, two lanes, 60 steps) without the side legs, so its per-kernel averages
 # compare with the line's HIP-event times
-SMALL="--no-cpu --no-secondary --host-frames 0"
+SMALL="--full --no-cpu --no-secondary --host-frames 0"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$O/prof_$TAG" -o run --output-format csv \
   -- python3 "$R/bench.py" $SMALL > "$O/prof_$TAG.json" 2> "$O/prof_$TAG.err"
 ORB_AMD_LIB=$L0LIB timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE -d "$O/pmcf_$TAG" -o run --output-format csv \
-  -- python3 "$R/bench.py" --no-cpu --no-secondary --frames 512 --steps 2 --warmup 1 --host-frames 0 > "$O/pmcf_$TAG.json" 2> "$O/pmcf_$TAG.err"
+  -- python3 "$R/bench.py" --full --no-cpu --no-secondary --frames 512 --steps 2 --warmup 1 --host-frames 0 > "$O/pmcf_$TAG.json" 2> "$O/pmcf_$TAG.err"
 ORB_AMD_LIB=$L0LIB timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE -d "$O/pmcw_$TAG" -o run --output-format csv \
-  -- python3 "$R/bench.py" --no-cpu --no-secondary --frames 512 --steps 2 --warmup 1 --host-frames 0 > "$O/pmcw_$TAG.json" 2> "$O/pmcw_$TAG.err"
+  -- python3 "$R/bench.py" --full --no-cpu --no-secondary --frames 512 --steps 2 --warmup 1 --host-frames 0 > "$O/pmcw_$TAG.json" 2> "$O/pmcw_$TAG.err"
 timeout -k 10 120 rocprofv3 --pmc FETCH_SIZE -d "$O/calib_$TAG" -o run --output-format csv \
   -- "$R/tools/probe/fetch_calib" > "$O/calib_$TAG.log" 2>&1
 timeout -k 10 120 rocprofv3 --pmc WRITE_SIZE -d "$O/calibw_$TAG" -o run --output-format csv \
