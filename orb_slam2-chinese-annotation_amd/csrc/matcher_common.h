@@ -93,20 +93,21 @@ __device__ __forceinline__ void for_features_in_area(const orb_keypoint_t* K,
   const int nMaxCellY = min(ORB_GRID_ROWS - 1, (int)ceilf((y - P.minY + r) * P.invH));
   if (nMaxCellY < 0) return;
   const bool checkLevels = (minLevel > 0) || (maxLevel >= 0);
+  // The grid is column-major (grid_cell) and cs a prefix over its cells: the
+  // cells nMinCellY..nMaxCellY of a column are one contiguous run of ci, in
+  // the reference's order (iy, then list order) -- two table reads per column
+  // instead of two per cell.
   for (int ix = nMinCellX; ix <= nMaxCellX; ++ix) {
-    for (int iy = nMinCellY; iy <= nMaxCellY; ++iy) {
-      const int c = ix * ORB_GRID_ROWS + iy;
-      const int e = cs[c + 1];
-      for (int j = cs[c]; j < e; ++j) {
-        const int idx = ci[j];
-        const orb_keypoint_t& kp = K[idx];
-        if (checkLevels) {
-          if (kp.octave < minLevel) continue;
-          if (maxLevel >= 0 && kp.octave > maxLevel) continue;
-        }
-        const float dx = kp.x - x, dy = kp.y - y;
-        if (fabsf(dx) < r && fabsf(dy) < r) visit(idx, kp);
+    const int e = cs[ix * ORB_GRID_ROWS + nMaxCellY + 1];
+    for (int j = cs[ix * ORB_GRID_ROWS + nMinCellY]; j < e; ++j) {
+      const int idx = ci[j];
+      const orb_keypoint_t& kp = K[idx];
+      if (checkLevels) {
+        if (kp.octave < minLevel) continue;
+        if (maxLevel >= 0 && kp.octave > maxLevel) continue;
       }
+      const float dx = kp.x - x, dy = kp.y - y;
+      if (fabsf(dx) < r && fabsf(dy) < r) visit(idx, kp);
     }
   }
 }

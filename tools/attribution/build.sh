@@ -12,6 +12,10 @@
 #   FC_LDS_PAD_TILES  measured-slower k_orient_desc / k_fast_cells variants
 # PATCHES=fast_runs.patch instead restores k_fast_runs (round 6: FAST over runs
 # of ORB_FAST_RUN_CELLS cells per wave; measured slower).
+# PATCHES=grid_runs.patch restores two variants of k_proj_candidates' run scan
+# (round 7, both measured and not kept): -DPROJ_PREFETCH=1
+# (next entry read one iteration ahead) and -DPROJ_CS_GLOBAL=1 (run bounds read
+# from the global cell table, no LDS copy of it).
 # Select the build with ORB_AMD_LIB=<path>.  variants.patch is the diff from
 # the product file to the round-5 source that held these blocks inline
 # (regenerate: tools/unifdef.py resolves them, see its docstring).
