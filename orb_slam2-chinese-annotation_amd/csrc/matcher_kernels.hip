@@ -561,13 +561,87 @@ __device__ __forceinline__ bool lock_test(const uint32_t* bm, int idx) {
   return (bm[idx >> 5] >> (idx & 31)) & 1u;
 }
 
+// Barrier ordering LDS only: global loads and stores still in flight (the
+// next windows' prefetch) are not waited for, unlike __syncthreads().
+__device__ __forceinline__ void lds_barrier() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+  __builtin_amdgcn_s_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+}
+
+// The prefix resolve's step between the phases of a round.  One wave issues
+// its LDS accesses in program order and the LDS serves them in that order, so
+// with NW == 1 nothing is waited for: the compiler only may not move LDS
+// accesses across this point.
+template <int NW>
+__device__ __forceinline__ void round_sync() {
+  if constexpr (NW == 1) {
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+  } else {
+    lds_barrier();
+  }
+}
+
+// The prefix resolve's exact scan of a point whose top-K ran dry, under the
+// committed locks: over the point's candidate list (scan order, static tests
+// applied) when it has one, else GetFeaturesInArea.  Returns the keypoint the
+// point takes, or -1.  Inlined, and P by reference: as a call (fp_slow's way)
+// the resolve held 96 VGPRs and 400 B of stack, and with P by value 272 B of
+// stack, instead of 81 VGPRs and none; that much stack per lane made the
+// kernel's time alone jump between 0.12 and 0.6-0.9 ms from process to process.
+__device__ __forceinline__ int prefix_slow(const uint32_t* bm, const orb_mp_track_t* mpp,
+                                        const uint8_t* mpd, const orb_keypoint_t* K,
+                                        const uint8_t* D, const uint8_t* LK, const float* UR,
+                                        const int32_t* cs, const int32_t* ci, const ProjParams& P,
+                                        const uint32_t* lst, int nl) {
+  int bd = 256, bl = -1, bd2 = 256, bl2 = -1, bi = -1;
+  if (lst) {
+    for (int j = 0; j < nl; ++j) {
+      const uint32_t ce = lst[j];
+      const int idx = cand_idx(ce);
+      if (lock_test(bm, idx)) continue;
+      const int dist = cand_dist(ce);
+      if (dist < bd) {
+        bd2 = bd; bd = dist; bl2 = bl; bl = cand_oct(ce); bi = idx;
+      } else if (dist < bd2) {
+        bl2 = cand_oct(ce); bd2 = dist;
+      }
+    }
+  } else {
+    const orb_mp_track_t mp = *mpp;
+    const int lvl = mp.level;
+    float r = (double)mp.view_cos > 0.998 ? 2.5f : 4.0f;
+    if (P.th != 1.0f) r *= P.th;
+    const float rs = r * P.scale[lvl];
+    const ulonglong4 qd = load_desc(mpd);
+    for_features_in_area(K, cs, ci, P, mp.proj_x, mp.proj_y, rs, lvl - 1, lvl,
+                         [&](int idx, const orb_keypoint_t& kp) {
+                           if ((LK && LK[idx]) || lock_test(bm, idx)) return;
+                           if (UR && UR[idx] > 0) {
+                             const float er = fabsf(mp.proj_xr - UR[idx]);
+                             if (er > rs) return;
+                           }
+                           const int dist = hamming256(qd, load_desc(D + (size_t)idx * 32));
+                           if (dist < bd) {
+                             bd2 = bd; bd = dist; bl2 = bl; bl = kp.octave; bi = idx;
+                           } else if (dist < bd2) {
+                             bl2 = kp.octave; bd2 = dist;
+                           }
+                         });
+  }
+  return bd <= 100 && !(bl == bl2 && (float)bd > P.nnratio * (float)bd2) ? bi : -1;
+}
+
 // A window is 64 * NW points (NW waves of one workgroup per problem): every
 // thread evaluates its point, claims are resolved across the whole window in
 // LDS (earliest claiming thread per keypoint), and the longest conflict-free
 // prefix over all waves is committed.  NW = 1 is one wave per problem; wider
 // windows cut the number of sequential rounds for large local maps.
-
-template <int NW>
+// KM_LDS: the keypoint -> point result (kpMatch) is kept in LDS and written
+// out once at the end, as in k_proj_resolve_fp; without it (frames whose
+// 8 B per keypoint the host finds too much LDS) kpMatch takes global atomics.
+template <int NW, bool KM_LDS>
 __global__ __launch_bounds__(64 * NW) void k_proj_resolve(
     const orb_keypoint_t* __restrict__ keys, const uint8_t* __restrict__ desc,
     const float* __restrict__ uright, const uint8_t* __restrict__ locked,
@@ -576,13 +650,13 @@ __global__ __launch_bounds__(64 * NW) void k_proj_resolve(
     const int32_t* __restrict__ cellStart, const int32_t* __restrict__ cellIdx, ProjParams P,
     const uint32_t* __restrict__ topk, const int32_t* __restrict__ ncand,
     int32_t* __restrict__ kpMatch, int32_t* __restrict__ nmatches) {
-  constexpr int W = 64 * NW, CHUNK = 256 * NW;
+  constexpr int W = 64 * NW, RING = 4, CHUNK = RING * W, AHEAD = 4;
   // LDS: lock bitmap (1 bit / keypoint), earliest claiming thread per keypoint
-  // of the current window, and a prefetched chunk of per-point resolve inputs
+  // of the current window, kpMatch (KM_LDS), and a ring of RING blocks of W
+  // points' resolve inputs
   extern __shared__ __attribute__((aligned(16))) uint32_t dyn[];
   __shared__ uint4 cTop[CHUNK];
-  __shared__ int cN[CHUNK];
-  __shared__ uint8_t cObs[CHUNK];
+  __shared__ int cN[CHUNK];  // raw: count, obs, list slot
   __shared__ int sFirst[NW], sCount[NW];
   __shared__ int sSlow;
   const int p = blockIdx.x, t = threadIdx.x, lane = t & 63, wv = t >> 6;
@@ -590,135 +664,145 @@ __global__ __launch_bounds__(64 * NW) void k_proj_resolve(
   const int words = (kpStride + 31) >> 5;
   uint32_t* bm = dyn;
   int* claimBy = (int*)(dyn + ((words + 3) & ~3));
+  int32_t* km = KM_LDS ? (int32_t*)(claimBy + kpStride) : kpMatch + (size_t)p * kpStride;
   for (int i = t; i < words; i += W) bm[i] = 0u;
   for (int i = t; i < kpStride; i += W) claimBy[i] = W;
-  int32_t* km = kpMatch + (size_t)p * kpStride;
   for (int i = t; i < n; i += W) km[i] = -1;
-  __syncthreads();
   const float nnratio = P.nnratio;
   const size_t pbase = (size_t)p * mpStride;
+  // Input pipeline.  Block b is points [b * W, b * W + W), one per thread, and
+  // lives in ring slot b % RING.  The window [start, start + W) touches the
+  // blocks s = start / W and s + 1; s .. s + RING - 1 are resident and the
+  // AHEAD blocks after them are in flight in registers (block b in pfTop /
+  // pfN[b % AHEAD]).  When the window enters a new block, the block it left
+  // is dead: the oldest block in flight is stored over it and its registers
+  // take the loads of the block AHEAD on.  A round commits at most W points,
+  // so the window enters one block at a time and a slide waits for loads
+  // issued AHEAD slides (at least as many rounds: the bench's maps commit a
+  // full window in two rounds of three) earlier, never for its own.  With
+  // KM_LDS no other global access is in flight inside the loop, so the wait
+  // at a slide is for the prefetch alone (kpMatch atomics would share the
+  // in-order vmcnt counter with it and be waited for as well).
+  auto load = [&](uint4& e, int& nc, int b) {  // (index clamped to the problem's points)
+    const size_t mg = pbase + (size_t)min(b * W + t, M - 1);
+    const uint32_t* tp = topk + mg * TOPK;
+    e = make_uint4(tp[0], tp[1], tp[2], tp[3]);
+    nc = ncand[mg];
+  };
+  auto store = [&](const uint4& e, int nc, int b) {
+    const int j = (b * W + t) & (CHUNK - 1);
+    cTop[j] = e;
+    cN[j] = nc;
+  };
+  // (plain arrays: as an array of structs the first blocks went through the stack)
+  uint4 pfTop[AHEAD];
+  int pfN[AHEAD];
+#pragma unroll
+  for (int c = 0; c < AHEAD; ++c) {
+    pfTop[c] = make_uint4(0u, 0u, 0u, 0u);
+    pfN[c] = -1;
+  }
+  int pfb = RING;  // the oldest block in flight
+  if (M > 0) {
+    uint4 inTop[RING];  // every load issued before the first store
+    int inN[RING];
+#pragma unroll
+    for (int k = 0; k < RING; ++k) load(inTop[k], inN[k], k);
+#pragma unroll
+    for (int k = 0; k < RING; ++k) store(inTop[k], inN[k], k);
+    // (issued after the stores: issued before them, the compiler's waits at
+    // three of four slides came out as vmcnt(0))
+#pragma unroll
+    for (int c = 0; c < AHEAD; ++c)
+      load(pfTop[(RING + c) % AHEAD], pfN[(RING + c) % AHEAD], RING + c);
+  }
+  if constexpr (KM_LDS)
+    round_sync<NW>();
+  else
+    __syncthreads();  // kpMatch's reset reaches memory before the first atomic on it
   int matches = 0;  // this wave's committed accepts
   int start = 0;
-  int cb = -CHUNK;  // first point held in the LDS chunk
-  while (start < M) {
-    if (start + W > cb + CHUNK && cb + CHUNK < M) {  // slide the chunk to `start`
-      cb = start;
-      __syncthreads();
-      for (int j = t; j < CHUNK; j += W) {
-        const int m = cb + j;
-        if (m < M) {
-          cTop[j] = *reinterpret_cast<const uint4*>(topk + (pbase + m) * TOPK);
-          const int v = ncand[pbase + m];
-          cN[j] = v;  // raw: count, obs, list slot
-          cObs[j] = nc_obs(v);
-        }
-      }
-      __syncthreads();
-    }
+  auto round = [&]() {
     const int m = start + t;
     const bool active = m < M;
     int nc = -1, ncRaw = -1;
-    uint32_t e[TOPK];
-    bool hasObs = false;
+    uint32_t e[TOPK] = {0u, 0u, 0u, 0u};
     if (active) {
-      const int j = m - cb;
+      const int j = m & (CHUNK - 1);
       ncRaw = cN[j];
       nc = nc_count(ncRaw);
       const uint4 t4 = cTop[j];
       e[0] = t4.x; e[1] = t4.y; e[2] = t4.z; e[3] = t4.w;
-      hasObs = cObs[j] != 0;
     }
-    // evaluate against the current locks
+    const bool hasObs = nc_obs(ncRaw);
+    // evaluate against the current locks: every lock word read before any is
+    // used (entries past the point's count read keypoint 0's word, ignored)
     int bestDist = 256, bestLevel = -1, bestDist2 = 256, bestLevel2 = -1, bestIdx = -1;
     int consumed = 0, found = 0;
-    if (nc > 0) {
-      const int avail = nc < TOPK ? nc : TOPK;
-      for (int j = 0; j < avail && found < 2; ++j) {
-        ++consumed;
-        const int idx = cand_idx(e[j]);
-        if (lock_test(bm, idx)) continue;
-        if (found == 0) {
-          bestDist = cand_dist(e[j]);
-          bestLevel = cand_oct(e[j]);
-          bestIdx = idx;
-        } else {
-          bestDist2 = cand_dist(e[j]);
-          bestLevel2 = cand_oct(e[j]);
-        }
-        ++found;
+    const int avail = nc < TOPK ? (nc > 0 ? nc : 0) : TOPK;
+    uint32_t lw[TOPK];
+#pragma unroll
+    for (int j = 0; j < TOPK; ++j) lw[j] = bm[(j < avail ? cand_idx(e[j]) : 0) >> 5];
+#pragma unroll
+    for (int j = 0; j < TOPK; ++j) {
+      const bool look = j < avail && found < 2;
+      const int idx = cand_idx(e[j]);
+      const bool use = look && !((lw[j] >> (idx & 31)) & 1u);
+      if (use && found == 0) {
+        bestDist = cand_dist(e[j]); bestLevel = cand_oct(e[j]); bestIdx = idx;
+      } else if (use) {
+        bestDist2 = cand_dist(e[j]); bestLevel2 = cand_oct(e[j]);
       }
+      consumed += look ? 1 : 0;
+      found += use ? 1 : 0;
     }
     const bool slow = nc > TOPK && found < 2;
-    const int slowSlot = nc_slot(ncRaw);
     bool accept = false;
     if (nc > 0 && !slow && bestDist <= 100)
       accept = !(bestLevel == bestLevel2 && (float)bestDist > nnratio * (float)bestDist2);
     const bool locks = accept && hasObs;
-    // conflict: an earlier thread of this window locks a keypoint this one looked at
+    // conflict: an earlier thread of this window locks a keypoint this one
+    // looked at (all claims read in one round trip, like the lock words)
     if (locks) atomicMin(&claimBy[bestIdx], t);
-    __syncthreads();
-    bool conflict = false;
-    for (int q = 0; q < consumed; ++q) conflict |= claimBy[cand_idx(e[q])] < t;
-    const unsigned long long bad = __ballot(active && (conflict || (slow && t > 0)));
-    if (lane == 0) sFirst[wv] = bad ? wv * 64 + (int)__builtin_ctzll(bad) : W;
-    if (t == 0) sSlow = active && slow;
-    __syncthreads();
-    if (locks) claimBy[bestIdx] = W;
-    int commit = W;
+    round_sync<NW>();
+    int cl[TOPK];
 #pragma unroll
-    for (int i = 0; i < NW; ++i) commit = min(commit, sFirst[i]);
-    if (sSlow) {
+    for (int q = 0; q < TOPK; ++q) cl[q] = claimBy[q < consumed ? cand_idx(e[q]) : 0];
+    bool conflict = false;
+#pragma unroll
+    for (int q = 0; q < TOPK; ++q) conflict |= q < consumed && cl[q] < t;
+    const unsigned long long bad = __ballot(active && (conflict || (slow && t > 0)));
+    int commit;
+    bool anySlow;
+    if constexpr (NW == 1) {
+      // one wave: the ballot is the whole window's answer
+      commit = bad ? (int)__builtin_ctzll(bad) : W;
+      anySlow = (__ballot(active && slow) & 1ull) != 0;
+      round_sync<NW>();
+    } else {
+      if (lane == 0) sFirst[wv] = bad ? wv * 64 + (int)__builtin_ctzll(bad) : W;
+      if (t == 0) sSlow = active && slow;
+      round_sync<NW>();
+      commit = W;
+#pragma unroll
+      for (int i = 0; i < NW; ++i) commit = min(commit, sFirst[i]);
+      anySlow = sSlow != 0;
+    }
+    if (locks) claimBy[bestIdx] = W;
+    if (anySlow) {
       // exact re-scan of the first point of the window, thread 0, current locks
-      if (t == 0 && slowSlot >= 0) {  // the point's candidate list (scan order)
-        const uint32_t* lst = ovf_list(P, p, slowSlot);
-        int bd = 256, bl = -1, bd2 = 256, bl2 = -1, bi = -1;
-        for (int j = 0; j < nc; ++j) {
-          const uint32_t ce = lst[j];
-          const int idx = cand_idx(ce);
-          if (lock_test(bm, idx)) continue;
-          const int dist = cand_dist(ce);
-          if (dist < bd) {
-            bd2 = bd; bd = dist; bl2 = bl; bl = cand_oct(ce); bi = idx;
-          } else if (dist < bd2) {
-            bl2 = cand_oct(ce); bd2 = dist;
-          }
-        }
-        if (bd <= 100 && !(bl == bl2 && (float)bd > nnratio * (float)bd2)) {
+      if (t == 0) {
+        const int slot = nc_slot(ncRaw);
+        const int bi = prefix_slow(bm, mps + pbase + m, mpDesc + (pbase + m) * 32,
+                                   keys + (size_t)p * kpStride, desc + (size_t)p * kpStride * 32,
+                                   locked ? locked + (size_t)p * kpStride : nullptr,
+                                   uright ? uright + (size_t)p * kpStride : nullptr,
+                                   cellStart + (size_t)p * (GRID_CELLS + 1),
+                                   cellIdx + (size_t)p * kpStride, P,
+                                   slot >= 0 ? ovf_list(P, p, slot) : nullptr, nc);
+        if (bi >= 0) {
           atomicMax(&km[bi], m);
-          if (cObs[m - cb]) bm[bi >> 5] |= 1u << (bi & 31);
-          ++matches;
-        }
-      } else if (t == 0) {
-        const size_t mg = pbase + m;
-        const orb_mp_track_t mp = mps[mg];
-        const int lvl = mp.level;
-        float r = (double)mp.view_cos > 0.998 ? 2.5f : 4.0f;
-        if (P.th != 1.0f) r *= P.th;
-        const float rs = r * P.scale[lvl];
-        const orb_keypoint_t* K = keys + (size_t)p * kpStride;
-        const uint8_t* D = desc + (size_t)p * kpStride * 32;
-        const uint8_t* LK = locked ? locked + (size_t)p * kpStride : nullptr;
-        const float* UR = uright ? uright + (size_t)p * kpStride : nullptr;
-        const ulonglong4 qd = load_desc(mpDesc + mg * 32);
-        int bd = 256, bl = -1, bd2 = 256, bl2 = -1, bi = -1;
-        for_features_in_area(K, cellStart + (size_t)p * (GRID_CELLS + 1),
-                             cellIdx + (size_t)p * kpStride, P, mp.proj_x, mp.proj_y, rs,
-                             lvl - 1, lvl, [&](int idx, const orb_keypoint_t& kp) {
-                               if ((LK && LK[idx]) || lock_test(bm, idx)) return;
-                               if (UR && UR[idx] > 0) {
-                                 const float er = fabsf(mp.proj_xr - UR[idx]);
-                                 if (er > r * P.scale[lvl]) return;
-                               }
-                               const int dist = hamming256(qd, load_desc(D + (size_t)idx * 32));
-                               if (dist < bd) {
-                                 bd2 = bd; bd = dist; bl2 = bl; bl = kp.octave; bi = idx;
-                               } else if (dist < bd2) {
-                                 bl2 = kp.octave; bd2 = dist;
-                               }
-                             });
-        if (bd <= 100 && !(bl == bl2 && (float)bd > nnratio * (float)bd2)) {
-          atomicMax(&km[bi], m);
-          if (mp.has_obs) bm[bi >> 5] |= 1u << (bi & 31);
+          if (hasObs) bm[bi >> 5] |= 1u << (bi & 31);
           ++matches;
         }
       }
@@ -730,8 +814,32 @@ __global__ __launch_bounds__(64 * NW) void k_proj_resolve(
       }
       matches += __popcll(__ballot(t < commit && accept));
     }
-    __syncthreads();  // this round's locks before the next window's evaluation
+    round_sync<NW>();  // this round's locks before the next window's evaluation
     start += commit;
+  };
+  // Rounds while the window stays in the blocks it is in, then a slide.  The
+  // slides are unrolled over the AHEAD register sets, so each is a fixed
+  // place in the order the loads are issued in and the compiler's wait there
+  // (one in-order counter) leaves the AHEAD - 1 later blocks in flight.
+  static_assert(RING % AHEAD == 0, "block RING is held in pfTop[0]");
+  while (start < M) {
+#pragma unroll
+    for (int c = 0; c < AHEAD; ++c) {
+      while (start < min(M, (pfb - RING + 1) * W)) round();
+      // (straight out: by way of the loop's head the compiler would count on
+      // reaching slide 0 from here, with block 0's loads the last ones issued)
+      if (start >= M) goto done;
+      // the window left block pfb - RING; what is stored over it is read by
+      // the rounds after the next one at the earliest
+      store(pfTop[c], pfN[c], pfb);
+      load(pfTop[c], pfN[c], pfb + AHEAD);
+      ++pfb;
+    }
+  }
+done:
+  if constexpr (KM_LDS) {
+    int32_t* out = kpMatch + (size_t)p * kpStride;
+    for (int i = t; i < n; i += W) out[i] = km[i];
   }
   if (lane == 0) sCount[wv] = matches;
   __syncthreads();
@@ -743,15 +851,6 @@ __global__ __launch_bounds__(64 * NW) void k_proj_resolve(
   }
 }
 
-
-// Barrier ordering LDS only: global stores and atomics still in flight (the
-// fire-and-forget kpMatch updates, the next window's prefetch) are not waited
-// for, unlike __syncthreads().
-__device__ __forceinline__ void lds_barrier() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-}
 
 // The exact scan of a point whose top-K ran dry (more than K candidates, too
 // many of them taken): GetFeaturesInArea under the same "taken" test.  Not
@@ -1397,19 +1496,24 @@ hipError_t orb_k_proj_resolve(const orb_keypoint_t* keys, const uint8_t* desc,
     return hipGetLastError();
   }
   const size_t words = (size_t)((kpStride + 31) / 32);
-  const size_t lds = ((words + 3) & ~(size_t)3) * 4 + (size_t)kpStride * 4;
-  if (kern == ORB_RESOLVE_KERNEL_PREFIX_W8)
-    hipLaunchKernelGGL(k_proj_resolve<8>, dim3(nproblems), dim3(512), lds, s, keys, desc, uright,
-                       locked, nkeys, kpStride, mps, mpDesc, nmps, mpStride, cellStart, cellIdx,
-                       P, topk, ncand, kpMatch, nmatches);
-  else if (kern == ORB_RESOLVE_KERNEL_PREFIX_W1)
-    hipLaunchKernelGGL(k_proj_resolve<1>, dim3(nproblems), dim3(64), lds, s, keys, desc, uright,
-                       locked, nkeys, kpStride, mps, mpDesc, nmps, mpStride, cellStart, cellIdx,
-                       P, topk, ncand, kpMatch, nmatches);
-  else
-    hipLaunchKernelGGL(k_proj_resolve<4>, dim3(nproblems), dim3(256), lds, s, keys, desc, uright,
-                       locked, nkeys, kpStride, mps, mpDesc, nmps, mpStride, cellStart, cellIdx,
-                       P, topk, ncand, kpMatch, nmatches);
+  const int nw = kern == ORB_RESOLVE_KERNEL_PREFIX_W8 ? 8 : kern == ORB_RESOLVE_KERNEL_PREFIX_W1 ? 1 : 4;
+  // lock bitmap and claims; kpMatch too while the workgroup (with 5.2 KB of
+  // static LDS per wave: the input ring) stays within 64 KB
+  size_t lds = ((words + 3) & ~(size_t)3) * 4 + (size_t)kpStride * 4;
+  const bool kmLds = lds + (size_t)kpStride * 4 + (size_t)nw * 5200 <= 64 * 1024;
+  if (kmLds) lds += (size_t)kpStride * 4;
+#define RESOLVE_LAUNCH(NW, KM)                                                                     \
+  hipLaunchKernelGGL((k_proj_resolve<NW, KM>), dim3(nproblems), dim3(64 * NW), lds, s, keys, desc, \
+                     uright, locked, nkeys, kpStride, mps, mpDesc, nmps, mpStride, cellStart,      \
+                     cellIdx, P, topk, ncand, kpMatch, nmatches)
+  if (nw == 8) {
+    if (kmLds) RESOLVE_LAUNCH(8, true); else RESOLVE_LAUNCH(8, false);
+  } else if (nw == 1) {
+    if (kmLds) RESOLVE_LAUNCH(1, true); else RESOLVE_LAUNCH(1, false);
+  } else {
+    if (kmLds) RESOLVE_LAUNCH(4, true); else RESOLVE_LAUNCH(4, false);
+  }
+#undef RESOLVE_LAUNCH
   return hipGetLastError();
 }
 

@@ -1733,7 +1733,9 @@ static orb_status_t ovf_pool(orb_matcher_t* m, int nproblems, ProjParamsHost& P,
   if ((st = m->dOvf.ensure(orb_k_proj_ovf_bytes(nproblems)))) return st;
   const size_t oldBytes = m->dOvfCtr.bytes;  // (a reallocation may return the old address)
   if ((st = m->dOvfCtr.ensure((size_t)std::max(nproblems, 1) * 4))) return st;
-  if (m->dOvfCtr.bytes != oldBytes) HIP_TRY(hipMemsetAsync(m->dOvfCtr.p, 0, m->dOvfCtr.bytes, s));
+  // (also when the gen wraps: tags of 4,095 calls ago would pass for this call's)
+  if (m->dOvfCtr.bytes != oldBytes || m->ovfGen >= 4095u)
+    HIP_TRY(hipMemsetAsync(m->dOvfCtr.p, 0, m->dOvfCtr.bytes, s));
   m->ovfGen = m->ovfGen % 4095u + 1u;
   P.ovf = m->dOvf.as<uint32_t>();
   P.ovfCtr = m->dOvfCtr.as<uint32_t>();

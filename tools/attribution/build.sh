@@ -16,6 +16,10 @@
 # (round 7, both measured and not kept): -DPROJ_PREFETCH=1
 # (next entry read one iteration ahead) and -DPROJ_CS_GLOBAL=1 (run bounds read
 # from the global cell table, no LDS copy of it).
+# PATCHES=resolve_chain.patch restores four variants of k_proj_resolve<NW>'s
+# input pipeline (round 8, measured and not kept):
+# -DRESOLVE_AHEAD=1|2 (blocks in flight in registers), -DRESOLVE_KM_GLOBAL=1
+# (kpMatch by global atomics) and -DRESOLVE_SLOW_CALL=1 (the exact re-scan as a call).
 # Select the build with ORB_AMD_LIB=<path>.  variants.patch is the diff from
 # the product file to the round-5 source that held these blocks inline
 # (regenerate: tools/unifdef.py resolves them, see its docstring).
