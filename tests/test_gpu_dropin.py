@@ -30,6 +30,7 @@ from pathlib import Path
 import numpy as np
 import pytest
 
+import border_cases as BC
 import scenarios as S
 
 pytestmark = pytest.mark.gpu
@@ -54,9 +55,18 @@ def _run(tmp_path, scenario, files, meta):
     assert r.returncode == 0, r.stderr[-2000:]
 
 
-@pytest.mark.parametrize("w,h,nf,seed", [(640, 480, 1000, 1), (1241, 376, 2000, 7)])
+# seed "border": the first b = 3 image of border_cases.border_set, whose
+# keypoints sit 0 and 1 px inside every side of every level
+@pytest.mark.parametrize("w,h,nf,seed", [(640, 480, 1000, 1), (1241, 376, 2000, 7),
+                                         (380, 230, BC.NF, "border")])
 def test_extractor_dropin(gpu, oracle, tmp_path, w, h, nf, seed):
-    img = oracle.synth_image(seed, 0, w, h)
+    if seed == "border":
+        ref = BC.border_oracle(oracle, w, h)[BC.DROPIN_IMAGE]
+        img = ref[0]
+        missing = BC.EDGE_BINS - BC.bins_of(oracle, w, h, [ref])
+        assert not missing, sorted(missing, key=str)
+    else:
+        img = oracle.synth_image(seed, 0, w, h)
     _run(tmp_path, "extract", {"img.bin": img}, [w, h, nf])
     kr, dr, _ = oracle.extract(img, nf)
     assert (tmp_path / "kps.bin").read_bytes() == kr.tobytes()
