@@ -68,6 +68,19 @@
  *                                  KeyFrame::ComputeBoW src/KeyFrame.cc:60-71 ->
  *                                  TemplatedVocabulary::transform(features, BowVector&,
  *                                  FeatureVector&, levelsup) TemplatedVocabulary.h:1128-1283
+ *   orb_vocabulary_score(_batch)   TemplatedVocabulary::score TemplatedVocabulary.h ->
+ *                                  L1/L2/ChiSquare/Bhattacharyya/DotProduct Scoring::score
+ *                                  Thirdparty/DBoW2/DBoW2/ScoringObject.cpp:23-311
+ *   orb_kf_database_create / _add / _erase / _clear
+ *                                  KeyFrameDatabase ctor, add, erase, clear
+ *                                  src/KeyFrameDatabase.cc:34-76
+ *   orb_kf_database_detect_relocalization
+ *                                  KeyFrameDatabase::DetectRelocalizationCandidates
+ *                                  src/KeyFrameDatabase.cc:205-339 (src/Tracking.cc:1569)
+ *   orb_kf_database_detect_loop    KeyFrameDatabase::DetectLoopCandidates
+ *                                  src/KeyFrameDatabase.cc:79-202 (src/LoopClosing.cc:125-158)
+ *   orb_kf_database_set_covisibility  KeyFrame::GetBestCovisibilityKeyFrames(10) as read at
+ *                                  src/KeyFrameDatabase.cc:155,286
  *
  * Error behaviour: the reference has no status codes (an empty image returns
  * silently with outputs untouched, src/ORBextractor.cc:1095-1096; a non-8UC1
@@ -703,6 +716,99 @@ orb_status_t orb_vocabulary_transform_batch(orb_vocabulary_t* v, int n_frames,
                                             int32_t* d_n_words, uint32_t* d_fv_nodes,
                                             int32_t* d_fv_offs, uint32_t* d_fv_feats,
                                             int32_t* d_n_fv_nodes, void* stream);
+
+/* ------------------------------------------- place recognition (BoW score) */
+
+/* TemplatedVocabulary::score(v1, v2) with the vocabulary's own scoring type
+ * (ScoringObject.cpp:23-311) for n_pairs pairs.  BowVectors in the layout
+ * orb_vocabulary_transform emits: pair p's first vector is a_words / a_values
+ * [a_offs[p], a_offs[p+1]) with the words strictly ascending, its second b_*
+ * likewise; out[p] = the reference's double, bit for bit (the sum over the
+ * common words is one chain of double adds in ascending word order).
+ * Limits: KL_DIVERGENCE calls log(), whose rounding no build pins: a KL
+ * vocabulary returns ORB_EINVAL here and from orb_kf_database_create.  Offsets
+ * are int32 (fewer than 2^31 words per call).  Host buffers; synchronous. */
+orb_status_t orb_vocabulary_score(orb_vocabulary_t* v, int n_pairs, const int32_t* a_offs,
+                                  const uint32_t* a_words, const double* a_values,
+                                  const int32_t* b_offs, const uint32_t* b_words,
+                                  const double* b_values, double* out);
+/* Device-pointer form (e.g. on orb_vocabulary_transform_batch outputs, whose
+ * frame f occupies [f * stride, f * stride + d_n_words[f]): the caller builds
+ * the offsets).  The vectors are not validated.  Asynchronous on `stream`. */
+orb_status_t orb_vocabulary_score_batch(orb_vocabulary_t* v, int n_pairs, const int32_t* d_a_offs,
+                                        const uint32_t* d_a_words, const double* d_a_values,
+                                        const int32_t* d_b_offs, const uint32_t* d_b_words,
+                                        const double* d_b_values, double* d_out, void* stream);
+
+/* --------------------------------------- place recognition (KeyFrameDatabase) */
+
+/* KeyFrameDatabase (src/KeyFrameDatabase.cc) over keyframe ids.  The BowVectors,
+ * the add sequence, the covisibility snapshots and the per-keyframe mRelocScore /
+ * mLoopScore live in device memory and grow on add; a query uploads its own
+ * BowVector (and the connected ids) only.  Every call is synchronous on the
+ * handle's own stream and serialised by the handle's mutex.  The vocabulary
+ * must outlive the database.
+ * Differences from the reference, each a status or a documented value:
+ *   - mRelocScore / mLoopScore of a keyframe no query has scored yet read 0.0f
+ *     (the reference leaves them uninitialised, include/KeyFrame.h); a keyframe
+ *     erased and added again is a new keyframe (new sequence number, scores 0).
+ *   - query ids are taken to be unique, as Frame / KeyFrame mnId are; 0 (the
+ *     initialiser of mnRelocQuery / mnLoopQuery) and the id of the previous
+ *     query of the same kind are refused.
+ *   - storage of erased keyframes is reclaimed by orb_kf_database_clear only;
+ *     at most 2^31 - 1 keyframes are added between two clears. */
+typedef struct orb_kf_database orb_kf_database_t;
+
+orb_status_t orb_kf_database_create(orb_vocabulary_t* v, orb_kf_database_t** out);
+void orb_kf_database_destroy(orb_kf_database_t* db);
+orb_status_t orb_kf_database_clear(orb_kf_database_t* db);   /* :72-76 */
+/* Number of keyframes in the database (added and not erased); < 0 = status. */
+int orb_kf_database_size(orb_kf_database_t* db);
+/* add(pKF) (:42-49) with pKF->mnId = kf_id and pKF->mBowVec = words / values.
+ * ORB_EINVAL if the words are not strictly ascending, a word is >= the
+ * vocabulary's word count, or kf_id is present already (the reference would
+ * list it twice). */
+orb_status_t orb_kf_database_add(orb_kf_database_t* db, int64_t kf_id, int n_words,
+                                 const uint32_t* words, const double* values);
+/* erase(pKF) (:51-70); an id that is not present is a no-op, as there. */
+orb_status_t orb_kf_database_erase(orb_kf_database_t* db, int64_t kf_id);
+/* Snapshot of pKF->GetBestCovisibilityKeyFrames(10) (n <= 10 ids, best first),
+ * read by the queries' accumulation step until replaced.  An id that is not
+ * in the database at query time never shares. */
+orb_status_t orb_kf_database_set_covisibility(orb_kf_database_t* db, int64_t kf_id, int n,
+                                              const int64_t* neighbour_ids);
+/* DetectRelocalizationCandidates(F) (:205-339; Tracking::Relocalization,
+ * src/Tracking.cc:1569) with F->mnId = query_id and F->mBowVec = words / values.
+ * out_ids = vpRelocCandidates in the reference's order.  On ORB_ECAPACITY
+ * *n_out holds the required count (never more than orb_kf_database_size) and
+ * the query has run: its scores are stored; asking again under a new query_id
+ * returns the same candidates. */
+orb_status_t orb_kf_database_detect_relocalization(orb_kf_database_t* db, uint64_t query_id,
+                                                   int n_words, const uint32_t* words,
+                                                   const double* values, int64_t* out_ids,
+                                                   int capacity, int* n_out);
+/* DetectLoopCandidates(pKF, minScore) (:79-202; LoopClosing::DetectLoop,
+ * src/LoopClosing.cc:125-158): connected_ids = pKF->GetConnectedKeyFrames()
+ * (ids not in the database are ignored). */
+orb_status_t orb_kf_database_detect_loop(orb_kf_database_t* db, uint64_t query_id, int n_words,
+                                         const uint32_t* words, const double* values,
+                                         int n_connected, const int64_t* connected_ids,
+                                         float min_score, int64_t* out_ids, int capacity,
+                                         int* n_out);
+/* lKFsSharingWords of the last query on this handle, in list order: ids[i],
+ * common[i] = mnRelocWords / mnLoopWords, scored[i] = 1 if that query scored
+ * it (common > minCommonWords), scores[i] = its mRelocScore / mLoopScore after
+ * the query (for an entry not scored: what an earlier query left, or 0).
+ * *n = the list's length (ORB_ECAPACITY if capacity is smaller; all outputs
+ * may be NULL to ask for it).  Empty after clear. */
+orb_status_t orb_kf_database_last_query(orb_kf_database_t* db, int64_t* ids, int32_t* common,
+                                        float* scores, uint8_t* scored, int capacity, int* n);
+/* Isolated kernel timing: runs kernel `stage` of the last query again `reps`
+ * times between two events (0 k_db_common, 1 k_db_list, 2 k_db_score,
+ * 3 k_db_accumulate, 4 k_db_select) and returns the total milliseconds and the
+ * kernel's name.  ORB_EINVAL if the database changed since that query. */
+orb_status_t orb_kf_database_profile(orb_kf_database_t* db, int stage, int reps,
+                                     double* total_ms, const char** name);
 
 /* ---------------------------------------------------------- synthetic input */
 

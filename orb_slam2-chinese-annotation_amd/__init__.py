@@ -89,6 +89,7 @@ def lib() -> ctypes.CDLL:
         pass
     L = ctypes.CDLL(str(LIB_PATH))
     vp, i32, f32, sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t
+    i64, u64 = ctypes.c_int64, ctypes.c_uint64
     sig = {
         "orb_abi_version": (i32, []),
         "orb_status_string": (ctypes.c_char_p, [i32]),
@@ -165,6 +166,19 @@ def lib() -> ctypes.CDLL:
         "orb_vocabulary_transform": (i32, [vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "orb_vocabulary_transform_batch": (i32, [vp, i32, vp, vp, i32, i32, vp, vp, vp, vp, vp,
                                                  vp, vp, vp, vp, vp, vp]),
+        "orb_vocabulary_score": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, vp]),
+        "orb_vocabulary_score_batch": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "orb_kf_database_create": (i32, [vp, vp]),
+        "orb_kf_database_destroy": (None, [vp]),
+        "orb_kf_database_clear": (i32, [vp]),
+        "orb_kf_database_size": (i32, [vp]),
+        "orb_kf_database_add": (i32, [vp, i64, i32, vp, vp]),
+        "orb_kf_database_erase": (i32, [vp, i64]),
+        "orb_kf_database_set_covisibility": (i32, [vp, i64, i32, vp]),
+        "orb_kf_database_detect_relocalization": (i32, [vp, u64, i32, vp, vp, vp, i32, vp]),
+        "orb_kf_database_detect_loop": (i32, [vp, u64, i32, vp, vp, i32, vp, f32, vp, i32, vp]),
+        "orb_kf_database_last_query": (i32, [vp, vp, vp, vp, vp, i32, vp]),
+        "orb_kf_database_profile": (i32, [vp, i32, i32, vp, vp]),
         "orb_undistort_points": (i32, [vp, i32, vp, vp, vp, i32, vp]),
         "orb_undistort_keypoints": (i32, [vp, i32, vp, vp, vp, i32, vp]),
         "orb_compute_image_bounds": (i32, [vp, i32, i32, vp, vp, i32, vp]),
@@ -1029,3 +1043,138 @@ class ORBVocabulary:
             self._h, n_frames, d_counts, d_desc, stride, levelsup, d_feat_word, d_feat_weight,
             d_feat_node, d_bow_words, d_bow_values, d_n_words, d_fv_nodes, d_fv_offs, d_fv_feats,
             d_n_fv_nodes, stream or None), "transform_batch")
+
+    def score_pairs(self, a_list, b_list) -> np.ndarray:
+        """score(a_list[p], b_list[p]) for every pair: the reference's double
+        (ScoringObject.cpp:23-311), bit for bit.  Each vector is a (words,
+        values) pair as transform returns them (further tuple entries ignored)."""
+        if len(a_list) != len(b_list):
+            raise ValueError("score_pairs: lists differ in length")
+
+        def csr(vs):
+            offs = np.zeros(len(vs) + 1, np.int32)
+            offs[1:] = np.cumsum([len(v[0]) for v in vs])
+            w = np.concatenate([np.asarray(v[0], np.uint32) for v in vs] + [np.zeros(0, np.uint32)])
+            x = np.concatenate([np.asarray(v[1], np.float64) for v in vs] + [np.zeros(0)])
+            return offs, np.ascontiguousarray(w), np.ascontiguousarray(x)
+
+        n = len(a_list)
+        out = np.zeros(n, np.float64)
+        ao, aw, av = csr(a_list)
+        bo, bw, bv = csr(b_list)
+        _check(lib().orb_vocabulary_score(self._h, n, _ptr(ao), _ptr(aw), _ptr(av), _ptr(bo),
+                                          _ptr(bw), _ptr(bv), _ptr(out)), "orb_vocabulary_score")
+        return out
+
+    def score(self, a, b) -> float:
+        """TemplatedVocabulary::score(a, b) with this vocabulary's scoring type."""
+        return float(self.score_pairs([a], [b])[0])
+
+    def score_batch(self, n_pairs, d_a_offs, d_a_words, d_a_values, d_b_offs, d_b_words,
+                    d_b_values, d_out, stream: int = 0):
+        """Device-pointer form of score_pairs (CSR offsets int32, asynchronous)."""
+        _check(lib().orb_vocabulary_score_batch(self._h, n_pairs, d_a_offs, d_a_words, d_a_values,
+                                                d_b_offs, d_b_words, d_b_values, d_out,
+                                                stream or None), "orb_vocabulary_score_batch")
+
+
+# ---------------------------------------------------------- keyframe database
+class KeyFrameDatabase:
+    """KeyFrameDatabase (src/KeyFrameDatabase.cc) over keyframe ids, resident on
+    the device.  `bow` arguments are (words, values[, ...]) as
+    ORBVocabulary.transform returns them.  The vocabulary must outlive it."""
+
+    def __init__(self, voc: ORBVocabulary):
+        self._voc = voc  # keeps the vocabulary alive
+        h = ctypes.c_void_p()
+        _check(lib().orb_kf_database_create(voc._h, ctypes.byref(h)), "orb_kf_database_create")
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().orb_kf_database_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @staticmethod
+    def _bow(bow):
+        w = np.ascontiguousarray(bow[0], np.uint32)
+        v = np.ascontiguousarray(bow[1], np.float64)
+        if len(w) != len(v):
+            raise ValueError("BowVector words and values differ in length")
+        return w, v
+
+    def __len__(self) -> int:
+        n = lib().orb_kf_database_size(self._h)
+        if n < 0:
+            raise OrbError(n, "orb_kf_database_size")
+        return n
+
+    def add(self, kf_id: int, bow):
+        w, v = self._bow(bow)
+        _check(lib().orb_kf_database_add(self._h, kf_id, len(w), _ptr(w), _ptr(v)),
+               "orb_kf_database_add")
+
+    def erase(self, kf_id: int):
+        _check(lib().orb_kf_database_erase(self._h, kf_id), "orb_kf_database_erase")
+
+    def clear(self):
+        _check(lib().orb_kf_database_clear(self._h), "orb_kf_database_clear")
+
+    def set_covisibility(self, kf_id: int, neighbour_ids):
+        """Snapshot of GetBestCovisibilityKeyFrames(10) of keyframe kf_id."""
+        nb = np.ascontiguousarray(neighbour_ids, np.int64)
+        _check(lib().orb_kf_database_set_covisibility(self._h, kf_id, len(nb), _ptr(nb)),
+               "orb_kf_database_set_covisibility")
+
+    def _query(self, call, what):
+        cap = max(len(self), 1)
+        out = np.zeros(cap, np.int64)
+        n = ctypes.c_int(0)
+        _check(call(_ptr(out), cap, ctypes.byref(n)), what)
+        return out[:n.value].copy()
+
+    def DetectRelocalizationCandidates(self, query_id: int, bow) -> np.ndarray:
+        """Candidate keyframe ids in the reference's order (:205-339)."""
+        w, v = self._bow(bow)
+        return self._query(lambda o, c, n: lib().orb_kf_database_detect_relocalization(
+            self._h, query_id, len(w), _ptr(w), _ptr(v), o, c, n), "detect_relocalization")
+
+    def DetectLoopCandidates(self, query_id: int, bow, connected_ids, min_score: float) -> np.ndarray:
+        """Candidate keyframe ids in the reference's order (:79-202)."""
+        w, v = self._bow(bow)
+        cn = np.ascontiguousarray(connected_ids, np.int64)
+        return self._query(lambda o, c, n: lib().orb_kf_database_detect_loop(
+            self._h, query_id, len(w), _ptr(w), _ptr(v), len(cn), _ptr(cn), min_score, o, c, n),
+            "detect_loop")
+
+    def last_query(self):
+        """lKFsSharingWords of the last query in list order: (ids, common word
+        counts, scores as float32, scored flags)."""
+        n = ctypes.c_int(0)
+        st = lib().orb_kf_database_last_query(self._h, None, None, None, None, 0, ctypes.byref(n))
+        if st not in (ORB_OK, ORB_ECAPACITY):
+            raise OrbError(st, "orb_kf_database_last_query")
+        cap = max(n.value, 1)
+        ids = np.zeros(cap, np.int64)
+        common = np.zeros(cap, np.int32)
+        scores = np.zeros(cap, np.float32)
+        scored = np.zeros(cap, np.uint8)
+        _check(lib().orb_kf_database_last_query(self._h, _ptr(ids), _ptr(common), _ptr(scores),
+                                                _ptr(scored), cap, ctypes.byref(n)),
+               "orb_kf_database_last_query")
+        k = n.value
+        return ids[:k], common[:k], scores[:k], scored[:k]
+
+    def profile(self, stage: int, reps: int):
+        """Isolated time of one kernel of the last query: (total ms, kernel name)."""
+        ms = ctypes.c_double(0)
+        name = ctypes.c_char_p()
+        _check(lib().orb_kf_database_profile(self._h, stage, reps, ctypes.byref(ms),
+                                             ctypes.byref(name)), "orb_kf_database_profile")
+        return ms.value, name.value.decode()

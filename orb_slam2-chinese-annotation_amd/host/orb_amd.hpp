@@ -11,6 +11,7 @@
 // INTEGRATION.md; it forwards to these calls.
 #pragma once
 
+#include <algorithm>
 #include <cassert>
 #include <cstdint>
 #include <map>
@@ -209,6 +210,28 @@ class ORBVocabulary {
       fv.emplace_hint(fv.end(), fvn[j],
                       std::vector<unsigned int>(fvf.begin() + fvo[j], fvf.begin() + fvo[j + 1]));
   }
+  // score(const BowVector& a, const BowVector& b), TemplatedVocabulary.h ->
+  // ScoringObject.cpp:23-311 with the vocabulary's scoring type (KL: assert).
+  double score(const BowVector& a, const BowVector& b) const {
+    std::vector<uint32_t> aw, bw;
+    std::vector<double> av, bv;
+    flatten(a, aw, av);
+    flatten(b, bw, bv);
+    const int32_t ao[2] = {0, (int32_t)aw.size()}, bo[2] = {0, (int32_t)bw.size()};
+    double out = 0.0;
+    check(orb_vocabulary_score(h_, 1, ao, aw.data(), av.data(), bo, bw.data(), bv.data(), &out),
+          "ORBVocabulary::score");
+    return out;
+  }
+  static void flatten(const BowVector& v, std::vector<uint32_t>& words,
+                      std::vector<double>& values) {
+    words.reserve(v.size());
+    values.reserve(v.size());
+    for (const auto& it : v) {
+      words.push_back(it.first);
+      values.push_back(it.second);
+    }
+  }
   orb_vocabulary_t* handle() { return h_; }
 
  private:
@@ -219,6 +242,70 @@ class ORBVocabulary {
   }
   int device_;
   orb_vocabulary_t* h_ = nullptr;
+};
+
+// KeyFrameDatabase (src/KeyFrameDatabase.cc) over keyframe ids (KeyFrame::mnId),
+// device-resident.  A keyframe is its id, its mBowVec and, once known, the ids
+// of GetBestCovisibilityKeyFrames(10); the queries return candidate ids in the
+// reference's order.  The vocabulary must outlive the database.
+class KeyFrameDatabase {
+ public:
+  explicit KeyFrameDatabase(ORBVocabulary& voc) {
+    check(orb_kf_database_create(voc.handle(), &h_), "KeyFrameDatabase");
+  }
+  ~KeyFrameDatabase() { orb_kf_database_destroy(h_); }
+  KeyFrameDatabase(const KeyFrameDatabase&) = delete;
+  KeyFrameDatabase& operator=(const KeyFrameDatabase&) = delete;
+
+  void add(int64_t kfId, const BowVector& bow) {  // :42-49
+    std::vector<uint32_t> w;
+    std::vector<double> v;
+    ORBVocabulary::flatten(bow, w, v);
+    check(orb_kf_database_add(h_, kfId, (int)w.size(), w.data(), v.data()),
+          "KeyFrameDatabase::add");
+  }
+  void erase(int64_t kfId) { check(orb_kf_database_erase(h_, kfId), "KeyFrameDatabase::erase"); }
+  void clear() { check(orb_kf_database_clear(h_), "KeyFrameDatabase::clear"); }
+  int size() const { return orb_kf_database_size(h_); }
+  // snapshot of pKF->GetBestCovisibilityKeyFrames(10), read at :155 and :286
+  void SetBestCovisibilityKeyFrames(int64_t kfId, const std::vector<int64_t>& ids) {
+    check(orb_kf_database_set_covisibility(h_, kfId, (int)ids.size(), ids.data()),
+          "KeyFrameDatabase::SetBestCovisibilityKeyFrames");
+  }
+  // DetectLoopCandidates(pKF, minScore) (:79-202): kfId = pKF->mnId, connected =
+  // the ids of pKF->GetConnectedKeyFrames().
+  std::vector<int64_t> DetectLoopCandidates(uint64_t kfId, const BowVector& bow,
+                                            const std::vector<int64_t>& connected,
+                                            float minScore) {
+    std::vector<uint32_t> w;
+    std::vector<double> v;
+    ORBVocabulary::flatten(bow, w, v);
+    std::vector<int64_t> out((size_t)std::max(size(), 1));
+    int n = 0;
+    check(orb_kf_database_detect_loop(h_, kfId, (int)w.size(), w.data(), v.data(),
+                                      (int)connected.size(), connected.data(), minScore,
+                                      out.data(), (int)out.size(), &n),
+          "KeyFrameDatabase::DetectLoopCandidates");
+    out.resize((size_t)n);
+    return out;
+  }
+  // DetectRelocalizationCandidates(F) (:205-339): frameId = F->mnId.
+  std::vector<int64_t> DetectRelocalizationCandidates(uint64_t frameId, const BowVector& bow) {
+    std::vector<uint32_t> w;
+    std::vector<double> v;
+    ORBVocabulary::flatten(bow, w, v);
+    std::vector<int64_t> out((size_t)std::max(size(), 1));
+    int n = 0;
+    check(orb_kf_database_detect_relocalization(h_, frameId, (int)w.size(), w.data(), v.data(),
+                                                out.data(), (int)out.size(), &n),
+          "KeyFrameDatabase::DetectRelocalizationCandidates");
+    out.resize((size_t)n);
+    return out;
+  }
+  orb_kf_database_t* handle() { return h_; }
+
+ private:
+  orb_kf_database_t* h_ = nullptr;
 };
 
 // ------------------------------------------------------------------ matcher

@@ -24,8 +24,12 @@ results table:
       + CPU oracle rate + exact check
   F3  SURVEY §8(f): ComputeDistinctiveDescriptors over 100,000 map points with
       1..20 observations (points/s) + CPU oracle rate + exact check
+  P1  place recognition: DetectRelocalizationCandidates against a database of
+      4,096 keyframes of about 1,000 words each on an ORBvoc-shaped synthetic
+      vocabulary (k 10, L 6), one query per call (queries/s), each kernel's
+      isolated time, bytes/s against 12 B per database entry + exact check
 
-Usage: python tools/bench_configs.py [--configs C1,C2,C3,C5,F1,F3] [--steps K]
+Usage: python tools/bench_configs.py [--configs C1,C2,C3,C5,F1,F3,P1] [--steps K]
 The oracle (CPU restatement) is used only for the CPU rows and parity checks.
 """
 import argparse
@@ -323,6 +327,71 @@ def f2(args, orb, oracle, torch):
             "alg_GBps": alg_bytes / sec / 1e9, "bit_exact": bool(exact)}
 
 
+def p1(args, orb, oracle, torch):
+    import placerec_ref
+    import scenarios
+    NKF, NF, NQ, SCENE = 4096, 1000, 32, 20000
+    voc = scenarios.vocabulary(rng_seed=11, k=10, L=6)
+    V = orb.ORBVocabulary(voc["k"], voc["L"], voc["parent"], voc["leaf"], voc["desc"],
+                          voc["weight"])
+    rng = np.random.default_rng(17)
+    # one place: every frame sees 1000 of the same 20,000 words (bits flipped)
+    scene = rng.choice(np.flatnonzero(voc["leaf"]), SCENE, replace=False)
+
+    def frame_bow():
+        bits = np.unpackbits(voc["desc"][rng.choice(scene, NF, replace=False)], axis=1)
+        bits ^= (rng.random(bits.shape) < 0.02).astype(np.uint8)
+        bw, bv, _ = V.transform(np.packbits(bits, axis=1), 4)
+        return bw.copy(), bv.copy()
+
+    db = orb.KeyFrameDatabase(V)
+    ref = placerec_ref.KeyFrameDatabase(V.n_words)
+    ids = np.arange(1, NKF + 1)
+    for i in ids:
+        b = frame_bow()
+        db.add(int(i), b)
+        ref.add(int(i), b)
+    for i in ids:  # neighbours in time, as a covisibility graph's best ten are
+        nb = [int(j) for j in range(i - 5, i + 6) if j != i and 1 <= j <= NKF]
+        db.set_covisibility(int(i), nb)
+        ref.set_covisibility(int(i), nb)
+    queries = [frame_bow() for _ in range(NQ)]
+    entries = sum(len(k.mBowVec[0]) for k in ref.kfs.values())
+    qid = [0]
+
+    def step():
+        qid[0] += 1
+        return db.DetectRelocalizationCandidates(qid[0], queries[qid[0] % NQ])
+
+    exact = True
+    for _ in range(2):
+        got = step()
+        want = ref.DetectRelocalizationCandidates(qid[0], queries[qid[0] % NQ])
+        gl, rl = db.last_query(), ref.last_query()
+        exact &= got.tolist() == want and all(
+            np.array_equal(np.ascontiguousarray(a).view(np.uint8), np.ascontiguousarray(b).view(np.uint8))
+            for a, b in zip(gl, rl))
+    steps = max(args.steps, 200)
+    sec = timed(step, steps, 10, torch)
+    reps = 50
+    kernels = {}
+    listed = len(db.last_query()[0])
+    scored = int(db.last_query()[3].sum())
+    for stage in range(5):
+        db.profile(stage, 5)
+        ms, name = db.profile(stage, reps)
+        kernels[name] = ms * 1e3 / reps
+    k_us = sum(kernels.values())
+    return {"config": "P1", "workload": f"DetectRelocalizationCandidates, {NKF} keyframes, "
+            f"{entries / NKF:.0f} words each, k 10 L 6 vocabulary, one query per call",
+            "unit": "queries/s", "value": 1.0 / sec, "us_per_query": sec * 1e6,
+            "kernel_us_isolated": kernels, "kernel_us_sum": k_us, "database_entries": entries,
+            "query_words": int(np.mean([len(q[0]) for q in queries])),
+            "last_query_listed": listed, "last_query_scored": scored,
+            "alg_bytes": entries * 12, "alg_GBps_per_query": entries * 12 / sec / 1e9,
+            "alg_GBps_kernels": entries * 12 / (k_us * 1e-6) / 1e9, "bit_exact": bool(exact)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--configs", default="C1,C2,C3,C5")
@@ -351,6 +420,8 @@ def main():
             r = f2(args, orb, oracle, torch)
         elif c == "F3":
             r = f3(args, orb, oracle, torch)
+        elif c == "P1":
+            r = p1(args, orb, oracle, torch)
         else:
             raise SystemExit(f"unknown config {c}")
         print(json.dumps(r), flush=True)
