@@ -19,12 +19,7 @@
 // VALU on CDNA4 makes this a few hundred nanoseconds per frame: it is a
 // latency-bound epilogue, kept separate so it can run after any extractor.
 #include "orb_device.h"
-
-struct UndistortParams {
-  double fx, fy, cx, cy, ifx, ify;  // A = mK (double), ifx = 1./fx
-  double rr[9];                     // RR = mK * I
-  double k[12];                     // k1 k2 p1 p2 k3 k4 k5 k6 s1 s2 s3 s4
-};
+#include "orb_kernels.h"
 
 __device__ __forceinline__ void undistort_one(const UndistortParams& P, float u, float v,
                                               float* ox, float* oy) {
@@ -83,23 +78,22 @@ __global__ __launch_bounds__(256) void k_undistort_keys(UndistortParams P, int n
   out[g] = r;
 }
 
-extern "C" hipError_t orb_k_undistort_points(const void* params, int n, const float* in,
-                                             float* out, hipStream_t s) {
+extern "C" hipError_t orb_k_undistort_points(const UndistortParams* params, int n,
+                                             const float* in, float* out, hipStream_t s) {
   if (n <= 0) return hipSuccess;
   hipLaunchKernelGGL(k_undistort_points, dim3((n + 255) / 256), dim3(256), 0, s,
-                     *(const UndistortParams*)params, n, (const float2*)in, (float2*)out);
+                     *params, n, (const float2*)in, (float2*)out);
   return hipGetLastError();
 }
 
-extern "C" hipError_t orb_k_undistort_keys(const void* params, int nFrames, const int32_t* counts,
-                                           int nSingle, int stride, const void* in, void* out,
-                                           int copyOnly, hipStream_t s) {
+extern "C" hipError_t orb_k_undistort_keys(const UndistortParams* params, int nFrames,
+                                           const int32_t* counts, int nSingle, int stride,
+                                           const void* in, void* out, int copyOnly,
+                                           hipStream_t s) {
   const long long total = (long long)nFrames * stride;
   if (total <= 0) return hipSuccess;
   hipLaunchKernelGGL(k_undistort_keys, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s,
-                     *(const UndistortParams*)params, nFrames, counts, nSingle, stride,
+                     *params, nFrames, counts, nSingle, stride,
                      (const KeyRec*)in, (KeyRec*)out, copyOnly);
   return hipGetLastError();
 }
-
-extern "C" size_t orb_k_undistort_params_size() { return sizeof(UndistortParams); }

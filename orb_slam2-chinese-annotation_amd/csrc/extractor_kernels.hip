@@ -21,6 +21,7 @@
 #include <algorithm>
 #include "orb_device.h"
 #include "orb_plan.h"
+#include "orb_kernels.h"
 #include "orb_pattern_data.h"
 #include "../../include/orb_abi.h"
 

@@ -7,6 +7,7 @@
 #include <climits>
 
 #include "matcher_common.h"
+#include "orb_kernels.h"
 
 // ================================================= SearchForInitialization
 // src/ORBmatcher.cc:429-577.  For each level-0 keypoint i1 of F1 (in order):
@@ -36,18 +37,7 @@
 #define INIT_STAGE 1536  // F2 level-0 keypoints staged in LDS (48 B each)
 #define INIT_WG 256
 
-struct InitParams {
-  float minX, minY, invW, invH;
-  float r, nnratio;
-  int checkOri;
-};
-
-// staged F2 keypoint: position, grid cell (ix << 16 | iy), original index
-struct InitKey {
-  float x, y;
-  uint32_t cell;
-  int32_t idx;
-};
+// (InitParams, InitKey: orb_kernel_params.h)
 
 template <int K>
 struct TopKReg {
@@ -399,10 +389,8 @@ __global__ __launch_bounds__(64) void k_init_resolve(
   if (lane == 0) nmatches[p] = n;
 }
 
-extern "C" size_t orb_k_init_params_size(void) { return sizeof(InitParams); }
 extern "C" size_t orb_k_init_list_len(void) { return INIT_LIST; }
 extern "C" size_t orb_k_init_topk(void) { return INIT_TOPK; }
-extern "C" size_t orb_k_init_key_size(void) { return sizeof(InitKey); }
 
 // LDS bytes of k_init_resolve for a problem stride (both frames <= kpStride).
 extern "C" size_t orb_k_init_lds(int kpStride) {
@@ -416,15 +404,14 @@ extern "C" hipError_t orb_k_search_init(const orb_keypoint_t* keys1, const uint8
                                         const int32_t* n1, const orb_keypoint_t* keys2,
                                         const uint8_t* desc2, const int32_t* n2, int kpStride,
                                         float* prev, const int32_t* cellStart,
-                                        const int32_t* cellIdx, const void* params,
+                                        const int32_t* cellIdx, const InitParams* params,
                                         int32_t* qList, int32_t* qOrder, int32_t* nQ,
-                                        void* stage,
+                                        InitKey* st,
                                         int32_t* nStage, uint32_t* topk, uint32_t* list,
                                         int32_t* ncand, int32_t* m12, int32_t* nmatches,
                                         int nproblems, hipStream_t s) {
   if (nproblems <= 0) return hipSuccess;
-  const InitParams P = *(const InitParams*)params;
-  InitKey* st = static_cast<InitKey*>(stage);
+  const InitParams P = *params;
   hipLaunchKernelGGL(k_init_prep, dim3(nproblems), dim3(INIT_WG), 0, s, keys1, n1, keys2,
                      kpStride, prev, cellStart, cellIdx, P, qList, qOrder, nQ, st, nStage);
   hipError_t e = hipGetLastError();

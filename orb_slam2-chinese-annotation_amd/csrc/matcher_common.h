@@ -4,6 +4,7 @@
 #pragma once
 #include "orb_device.h"
 #include "../../include/orb_abi.h"
+#include "orb_kernel_params.h"
 
 #define GRID_CELLS (ORB_GRID_COLS * ORB_GRID_ROWS)
 #define TOPK 4
@@ -27,16 +28,7 @@ __device__ __forceinline__ int grid_cell(const orb_keypoint_t& k, float minX, fl
 // order, packed as the top-K entries) into one of OVF_SLOTS lists per problem;
 // a point past OVF_CAP or beyond the slots keeps the grid re-scan.
 #define OVF_CAP 16
-#define OVF_SLOTS 512
-struct ProjParams {
-  float minX, minY, invW, invH;
-  float th, nnratio;
-  int nLevels;
-  float scale[ORB_MAX_LEVELS];
-  uint32_t* ovf;     // OVF_SLOTS x OVF_CAP entries per problem, or null (no lists)
-  uint32_t* ovfCtr;  // per problem: the call's gen << 20 | slots taken
-  uint32_t gen;      // 1..4095, a new value per call (no reset of ovfCtr needed)
-};
+#define OVF_SLOTS 512  // (the pool: ProjParams.ovf, orb_kernel_params.h)
 
 // A list slot of problem counter `ctr` for the call `gen`: the first
 // allocation of a call finds another call's tag and restarts the count.

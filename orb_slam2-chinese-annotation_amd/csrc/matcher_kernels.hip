@@ -10,6 +10,7 @@
 #include <cmath>
 
 #include "matcher_common.h"
+#include "orb_kernels.h"
 
 // ---------------------------------------------------------- k_hamming_batch
 __global__ __launch_bounds__(256) void k_hamming_batch(const uint8_t* __restrict__ a,
@@ -1349,9 +1350,9 @@ hipError_t orb_k_proj_candidates(const orb_keypoint_t* keys, const uint8_t* desc
                                  const uint8_t* mpDesc,
                                  const int32_t* nmps, int mpStride, int mpMax,
                                  const int32_t* cellStart, const int32_t* cellIdx,
-                                 const void* stagedGrid, const void* params, uint32_t* topk,
+                                 const void* stagedGrid, const ProjParams* params, uint32_t* topk,
                                  int32_t* ncand, int nproblems, hipStream_t s) {
-  const ProjParams P = *(const ProjParams*)params;
+  const ProjParams P = *params;
   if (mpMax <= 0 || nproblems <= 0) return hipSuccess;
   // dynamic LDS: the staged keypoints of a frame, sized to the key capacity
   const int stageCap = std::min(kpStride, PROJ_STAGE);
@@ -1457,11 +1458,11 @@ hipError_t orb_k_proj_resolve(const orb_keypoint_t* keys, const uint8_t* desc,
                               const float* uright, const uint8_t* locked, const int32_t* nkeys,
                               int kpStride, const orb_mp_track_t* mps, const uint8_t* mpDesc,
                               const int32_t* nmps, int mpStride, const int32_t* cellStart,
-                              const int32_t* cellIdx, const void* params, const uint32_t* topk,
+                              const int32_t* cellIdx, const ProjParams* params, const uint32_t* topk,
                               const int32_t* ncand, int32_t* kpMatch, int32_t* nmatches,
                               int nproblems, int schedule, int jacobiRounds, int32_t* jacScratch,
                               hipStream_t s) {
-  const ProjParams P = *(const ProjParams*)params;
+  const ProjParams P = *params;
   if (nproblems <= 0) return hipSuccess;
   const int kern = orb_k_proj_resolve_kernel(nproblems, kpStride, mpStride, schedule);
   if (kern == ORB_RESOLVE_KERNEL_FIXED_POINT || kern == ORB_RESOLVE_KERNEL_JACOBI) {
@@ -1517,8 +1518,6 @@ hipError_t orb_k_proj_resolve(const orb_keypoint_t* keys, const uint8_t* desc,
   return hipGetLastError();
 }
 
-size_t orb_k_proj_params_size(void) { return sizeof(ProjParams); }
-
 // bytes of the candidate-list pool (ProjParams.ovf) of n problems
 size_t orb_k_proj_ovf_bytes(int nproblems) {
   return (size_t)std::max(nproblems, 1) * OVF_SLOTS * OVF_CAP * 4;
@@ -1536,18 +1535,7 @@ size_t orb_k_proj_ovf_bytes(int nproblems) {
 //  2. 11x11 SAD (patch minus its centre) at the left octave for the 11 shifts,
 //     parabola sub-pixel, disparity window, depth = bf / disparity.
 // k_stereo_prune then drops matches whose SAD >= 1.5*1.4*median (:690-703).
-struct StereoParams {
-  int nLevels;
-  float bf, fx;
-  int w[ORB_MAX_LEVELS], h[ORB_MAX_LEVELS];
-  int strideL[ORB_MAX_LEVELS], strideR[ORB_MAX_LEVELS];
-  float scale[ORB_MAX_LEVELS], invScale[ORB_MAX_LEVELS];
-};
-
-struct StereoPairLevels {
-  const uint8_t* L[ORB_MAX_LEVELS];
-  const uint8_t* R[ORB_MAX_LEVELS];
-};
+// (StereoParams, StereoPairLevels: orb_kernel_params.h)
 
 // vRowIndices (src/Frame.cc:531-550) as CSR per pair: row yi lists every right
 // keypoint whose band [floor(y - 2 s), ceil(y + 2 s)] contains it (s = the
@@ -1968,13 +1956,12 @@ __global__ __launch_bounds__(256) void k_stereo_prune(const int32_t* __restrict_
   }
 }
 
-extern "C" size_t orb_k_stereo_params_size(void) { return sizeof(StereoParams); }
 
 // Row-index scratch of orb_k_stereo: ints per pair for the row starts and for
 // the row lists (every right keypoint listed in each row of its band).
-extern "C" void orb_k_stereo_scratch(const void* params, int kpStride, size_t* startInts,
+extern "C" void orb_k_stereo_scratch(const StereoParams* params, int kpStride, size_t* startInts,
                                      size_t* idxInts) {
-  const StereoParams& P = *(const StereoParams*)params;
+  const StereoParams& P = *params;
   float smax = 1.f;
   for (int l = 0; l < P.nLevels; ++l) smax = std::max(smax, P.scale[l]);
   *startInts = (size_t)P.h[0] + 1;
@@ -1985,11 +1972,12 @@ extern "C" void orb_k_stereo_scratch(const void* params, int kpStride, size_t* s
 extern "C" hipError_t orb_k_stereo(const orb_keypoint_t* lkeys, const uint8_t* ldesc,
                                    const int32_t* nleft, const orb_keypoint_t* rkeys,
                                    const uint8_t* rdesc, const int32_t* nright, int kpStride,
-                                   int maxLeft, const void* pyr, const void* params,
+                                   int maxLeft, const StereoPairLevels* pyr,
+                                   const StereoParams* params,
                                    float* uRight, float* depth, int32_t* sad, int npairs,
                                    int32_t* rowStart, int32_t* rowIdx, hipStream_t s) {
   if (npairs <= 0 || maxLeft <= 0) return hipSuccess;
-  const StereoParams P = *(const StereoParams*)params;
+  const StereoParams P = *params;
   size_t startInts, idxInts;
   orb_k_stereo_scratch(params, kpStride, &startInts, &idxInts);
   const size_t rowsLds = ((size_t)P.h[0] + 1) * sizeof(int);
@@ -2001,17 +1989,17 @@ extern "C" hipError_t orb_k_stereo(const orb_keypoint_t* lkeys, const uint8_t* l
   if (STEREO_KPW == 4)
     hipLaunchKernelGGL(k_stereo_match2<16>, dim3((maxLeft + 15) / 16, npairs), dim3(256), 0, s, lkeys,
                        ldesc, nleft, rkeys, rdesc, nright, kpStride,
-                       (const StereoPairLevels*)pyr, P, uRight, depth, sad, rowStart, rowIdx,
+                       pyr, P, uRight, depth, sad, rowStart, rowIdx,
                        (int)(idxInts / 2));
   else if (STEREO_KPW == 2)
     hipLaunchKernelGGL(k_stereo_match2<32>, dim3((maxLeft + 7) / 8, npairs), dim3(256), 0, s, lkeys,
                        ldesc, nleft, rkeys, rdesc, nright, kpStride,
-                       (const StereoPairLevels*)pyr, P, uRight, depth, sad, rowStart, rowIdx,
+                       pyr, P, uRight, depth, sad, rowStart, rowIdx,
                        (int)(idxInts / 2));
   else
     hipLaunchKernelGGL(k_stereo_match, dim3((maxLeft + 3) / 4, npairs), dim3(256), 0, s, lkeys,
                        ldesc, nleft, rkeys, rdesc, nright, kpStride,
-                       (const StereoPairLevels*)pyr, P, uRight, depth, sad, rowStart, rowIdx,
+                       pyr, P, uRight, depth, sad, rowStart, rowIdx,
                        (int)(idxInts / 2));
   e = hipGetLastError();
   if (e != hipSuccess) return e;
@@ -2026,13 +2014,7 @@ extern "C" hipError_t orb_k_stereo(const orb_keypoint_t* lkeys, const uint8_t* l
 // first K candidates in (distance, scan order).  k_frame_resolve: one wave per
 // problem replays the sequential loop (first-come locks by points with
 // observations), then the rotation histogram filter.
-struct FrameProjParams {
-  float minX, maxX, minY, maxY, invW, invH;
-  float fx, fy, cx, cy, bf;
-  float th;
-  int fwd, bwd, checkOri;
-  float scale[ORB_MAX_LEVELS];
-};
+// (FrameProjParams: orb_kernel_params.h)
 
 __global__ __launch_bounds__(256) void k_frame_candidates(
     const orb_keypoint_t* __restrict__ keys, const uint8_t* __restrict__ desc,
@@ -2223,16 +2205,14 @@ __global__ __launch_bounds__(64) void k_frame_resolve(
   if (lane == 0) *nmatches = acc - rem;
 }
 
-extern "C" size_t orb_k_frame_params_size(void) { return sizeof(FrameProjParams); }
-
 extern "C" hipError_t orb_k_frame_proj(const orb_keypoint_t* keys, const uint8_t* desc,
                                        const float* uright, const uint8_t* locked, int nkeys,
                                        const orb_last_mp_t* last, const uint8_t* lastDesc,
                                        int nlast, const int32_t* cellStart,
-                                       const int32_t* cellIdx, const void* params,
+                                       const int32_t* cellIdx, const FrameProjParams* params,
                                        uint32_t* topk, int32_t* ncand, int32_t* kpMatch,
                                        int32_t* nmatches, hipStream_t s) {
-  const FrameProjParams F = *(const FrameProjParams*)params;
+  const FrameProjParams F = *params;
   if (nlast > 0) {
     hipLaunchKernelGGL(k_frame_candidates, dim3((nlast + 255) / 256), dim3(256), 0, s, keys,
                        desc, uright, locked, last, lastDesc, nlast, cellStart, cellIdx, F, topk,
@@ -2411,12 +2391,7 @@ extern "C" hipError_t orb_k_bow(const uint8_t* kfDesc, const float* kfAngle, con
 //   dist = cv::norm(P-Ow)  double sum of squares, double sqrt, to float
 //   viewCos = PO.dot(Pn)/dist   double dot / double(dist), to float
 //   level = ceil(logf(maxDist/dist) / logScale) with logf pinned to pinned_log
-struct FrustumParams {
-  float fx, fy, cx, cy, bf;
-  float minX, maxX, minY, maxY;
-  float cosLimit, logScale;
-  int nLevels;
-};
+// (FrustumParams: orb_kernel_params.h)
 
 __global__ __launch_bounds__(256) void k_frustum(const orb_map_point_t* __restrict__ mps,
                                                  const int32_t* __restrict__ nmps, int mpStride,
@@ -2481,15 +2456,13 @@ __global__ __launch_bounds__(256) void k_frustum(const orb_map_point_t* __restri
   if ((threadIdx.x & 63) == 0 && c) atomicAdd(&nInView[p], c);
 }
 
-extern "C" size_t orb_k_frustum_params_size(void) { return sizeof(FrustumParams); }
-
 extern "C" hipError_t orb_k_frustum(const orb_map_point_t* mps, const int32_t* nmps, int mpStride,
-                         int mpMax, const orb_pose_t* poses, const void* params,
+                         int mpMax, const orb_pose_t* poses, const FrustumParams* params,
                          orb_mp_track_t* tracks, int32_t* nInView, int nproblems, hipStream_t s) {
   hipError_t e = hipMemsetAsync(nInView, 0, sizeof(int32_t) * nproblems, s);
   if (e != hipSuccess) return e;
   if (mpMax <= 0) return hipSuccess;
-  const FrustumParams fp = *static_cast<const FrustumParams*>(params);
+  const FrustumParams fp = *params;
   hipLaunchKernelGGL(k_frustum, dim3((mpMax + 255) / 256, nproblems), dim3(256), 0, s, mps, nmps,
                      mpStride, poses, fp, tracks, nInView);
   return hipGetLastError();

@@ -1,0 +1,156 @@
+// orb_kernel_params.h -- the parameter blocks and records the host runtime
+// fills and the matcher / mapping / vocabulary / place-recognition / camera
+// kernels read: one definition for both sides, as orb_plan.h is for the
+// extractor.  Plain C++ (no HIP): a host and a device compile both include it.
+// The blocks marked "by value" are kernel arguments, so their names are part
+// of the kernels' mangled symbols.
+#pragma once
+#include <stdint.h>
+
+#include "../../include/orb_abi.h"
+
+#ifndef ORB_MAX_LEVELS
+#define ORB_MAX_LEVELS 16  // as orb_plan.h, orb_device.h
+#endif
+
+// ------------------------------------------------------ matcher_kernels.hip
+// SearchByProjection(F, vpMapPoints) (by value).  ovf: the candidate lists of
+// the map points with more than TOPK candidates (OVF_SLOTS, OVF_CAP:
+// matcher_common.h).
+struct ProjParams {
+  float minX, minY, invW, invH;
+  float th, nnratio;
+  int nLevels;
+  float scale[ORB_MAX_LEVELS];
+  uint32_t* ovf;     // OVF_SLOTS x OVF_CAP entries per problem, or null (no lists)
+  uint32_t* ovfCtr;  // per problem: the call's gen << 20 | slots taken
+  uint32_t gen;      // 1..4095, a new value per call (no reset of ovfCtr needed)
+};
+
+// Frame::ComputeStereoMatches (by value)
+struct StereoParams {
+  int nLevels;
+  float bf, fx;
+  int w[ORB_MAX_LEVELS], h[ORB_MAX_LEVELS];
+  int strideL[ORB_MAX_LEVELS], strideR[ORB_MAX_LEVELS];
+  float scale[ORB_MAX_LEVELS], invScale[ORB_MAX_LEVELS];
+};
+
+// the pyramid levels of one stereo pair (device pointers; an array per call)
+struct StereoPairLevels {
+  const uint8_t* L[ORB_MAX_LEVELS];
+  const uint8_t* R[ORB_MAX_LEVELS];
+};
+
+// SearchByProjection(CurrentFrame, LastFrame) (by value)
+struct FrameProjParams {
+  float minX, maxX, minY, maxY, invW, invH;
+  float fx, fy, cx, cy, bf;
+  float th;
+  int fwd, bwd, checkOri;
+  float scale[ORB_MAX_LEVELS];
+};
+
+// k_frustum (by value)
+struct FrustumParams {
+  float fx, fy, cx, cy, bf;
+  float minX, maxX, minY, maxY;
+  float cosLimit, logScale;
+  int nLevels;
+};
+
+// --------------------------------------------------- projection_kernels.hip
+// the projection-window variants (by value)
+struct PPParams {
+  float R[9], t[3], Ow[3];  // world -> camera of the searched frame (first stage)
+  float R2[9], t2[3];       // SearchBySim3: camera A -> camera B (sR, t)
+  float fx, fy, cx, cy, bf;
+  float minX, maxX, minY, maxY, invW, invH;
+  float th, logScale;
+  int nLevels, thr, checkOri;
+  float scale[ORB_MAX_LEVELS], invSigma2[ORB_MAX_LEVELS];
+};
+
+// projected point: position, predicted window and levels; valid = 0 when the
+// reference skips the point before its window scan
+struct PPRec {
+  float u, v, ur, radius;
+  int minL, maxL, valid, pad;
+};
+
+// SearchForTriangulation (by value)
+struct TriParams {
+  float F[9];
+  float ex, ey;
+  int onlyStereo, checkOri;
+  float scale[ORB_MAX_LEVELS], sigma2[ORB_MAX_LEVELS];
+};
+
+// ------------------------------------------------------ mapping_kernels.hip
+// SearchForInitialization (by value)
+struct InitParams {
+  float minX, minY, invW, invH;
+  float r, nnratio;
+  int checkOri;
+};
+
+// staged F2 keypoint: position, grid cell (ix << 16 | iy), original index
+struct InitKey {
+  float x, y;
+  uint32_t cell;
+  int32_t idx;
+};
+
+// -------------------------------------------------------- vocab_kernels.hip
+struct VocNodeInfo {
+  int32_t first;  // device position of the first child
+  int32_t count;  // number of children (0 = Node::isLeaf)
+};
+
+// ------------------------------------------------------- camera_kernels.hip
+// cv::undistortPoints' double parameter block (by value): cvConvert of the
+// CV_32F matrices, ifx = 1./fx, RR = mK * I
+struct UndistortParams {
+  double fx, fy, cx, cy, ifx, ify;  // A = mK (double), ifx = 1./fx
+  double rr[9];                     // RR = mK * I
+  double k[12];                     // k1 k2 p1 p2 k3 k4 k5 k6 s1 s2 s3 s4
+};
+static_assert(sizeof(UndistortParams) == 27 * 8, "parameter block layout");
+
+// ----------------------------------------------------- placerec_kernels.hip
+#define PR_NEIGH 10  // covisibility neighbours stored per keyframe
+
+struct PrSlot {
+  long long off;  // first entry of the keyframe's BowVector in words / values
+  int32_t len;    // its word count
+  int32_t live;   // 0 once erased
+};
+
+// one keyframe database query: the database, the query, its scratch
+struct PrQueryArgs {
+  int type, loop;
+  float minScore;
+  int nSlots, nq, nConnected;
+  const PrSlot* slots;
+  const uint32_t* words;
+  const double* values;
+  const int32_t* neigh;
+  const long long* ids;
+  float* stored;
+  const uint32_t* qWords;
+  const double* qValues;
+  const int32_t* connSlots;
+  uint8_t* connected;
+  int32_t* common;
+  uint32_t* first;
+  int32_t* firstPos;
+  unsigned long long* keys;
+  uint32_t* list;
+  int32_t* hdr;
+  uint8_t* scored;
+  float* acc;
+  uint32_t* best;
+  uint8_t* valid;
+  long long* out;
+  int stage;  // -1: the whole query; 0..4: that kernel alone (isolated timing)
+};

@@ -31,9 +31,9 @@
 //                    compaction of each kept entry's best keyframe at its first
 //                    occurrence (:181-198, :316-336)
 #include "orb_device.h"
+#include "orb_kernels.h"
 
 #define PR_NONE 0xFFFFFFFFu
-#define PR_NEIGH 10
 #define PR_LDS_KEYS 4096  // list keys sorted in LDS up to this many slots (32 KiB)
 #define PR_Q_LDS 8192     // query words staged in LDS up to this many (32 KiB)
 
@@ -44,12 +44,6 @@
 #define PR_KL 3
 #define PR_BHAT 4
 #define PR_DOT 5
-
-struct PrSlot {
-  long long off;  // first entry of the keyframe's BowVector in words / values
-  int32_t len;    // its word count
-  int32_t live;   // 0 once erased
-};
 
 // Index of w in the ascending words[0, n), or -1.
 __device__ __forceinline__ int pr_find(const uint32_t* words, int n, uint32_t w) {
@@ -331,8 +325,6 @@ extern "C" hipError_t orb_k_bow_score(int type, int nPairs, const int32_t* aOffs
   return hipGetLastError();
 }
 
-extern "C" size_t orb_k_db_slot_size() { return sizeof(PrSlot); }
-
 // Scratch keys the list sort needs in global memory for nSlots slots (0: LDS).
 extern "C" size_t orb_k_db_key_scratch(int nSlots) {
   size_t P = 1024;
@@ -340,38 +332,8 @@ extern "C" size_t orb_k_db_key_scratch(int nSlots) {
   return P <= PR_LDS_KEYS ? 0 : P;
 }
 
-struct PrQueryArgs {
-  int type, loop;
-  float minScore;
-  int nSlots, nq, nConnected;
-  const void* slots;
-  const uint32_t* words;
-  const double* values;
-  const int32_t* neigh;
-  const long long* ids;
-  float* stored;
-  const uint32_t* qWords;
-  const double* qValues;
-  const int32_t* connSlots;
-  uint8_t* connected;
-  int32_t* common;
-  uint32_t* first;
-  int32_t* firstPos;
-  unsigned long long* keys;
-  uint32_t* list;
-  int32_t* hdr;
-  uint8_t* scored;
-  float* acc;
-  uint32_t* best;
-  uint8_t* valid;
-  long long* out;
-  int stage;  // -1: the whole query; 0..4: that kernel alone (isolated timing)
-};
-
-extern "C" size_t orb_k_db_query_args_size() { return sizeof(PrQueryArgs); }
-
-extern "C" hipError_t orb_k_db_query(const void* args, hipStream_t s) {
-  const PrQueryArgs& A = *(const PrQueryArgs*)args;
+extern "C" hipError_t orb_k_db_query(const PrQueryArgs* args, hipStream_t s) {
+  const PrQueryArgs& A = *args;
   const int n = A.nSlots;
   if (n <= 0) return hipSuccess;
   const bool all = A.stage < 0;
@@ -384,7 +346,7 @@ extern "C" hipError_t orb_k_db_query(const void* args, hipStream_t s) {
                          A.connSlots, A.nConnected, A.connected);
   }
   if (all || A.stage == 0)
-    hipLaunchKernelGGL(k_db_common, dim3(waveBlocks), dim3(256), 0, s, (const PrSlot*)A.slots, n,
+    hipLaunchKernelGGL(k_db_common, dim3(waveBlocks), dim3(256), 0, s, A.slots, n,
                        A.words, A.qWords, A.nq, A.loop ? A.connected : nullptr, A.common, A.first,
                        A.firstPos);
   if (all || A.stage == 1) {
@@ -396,7 +358,7 @@ extern "C" hipError_t orb_k_db_query(const void* args, hipStream_t s) {
   }
   if (all || A.stage == 2)
     hipLaunchKernelGGL(k_db_score, dim3(waveBlocks), dim3(256), 0, s, A.type, n,
-                       (const PrSlot*)A.slots, A.words, A.values, A.qWords, A.qValues, A.nq,
+                       A.slots, A.words, A.values, A.qWords, A.qValues, A.nq,
                        A.common, A.list, A.hdr, A.stored, A.scored);
   if (all || A.stage == 3)
     hipLaunchKernelGGL(k_db_accumulate, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, A.loop,

@@ -18,25 +18,11 @@
 #include <climits>
 
 #include "matcher_common.h"
+#include "orb_kernels.h"
 
 enum PPMode { PP_RELOC = 0, PP_SIM3_SBP = 1, PP_FUSE = 2, PP_FUSE_SIM3 = 3, PP_SIM3_DIR = 4 };
 
-struct PPParams {
-  float R[9], t[3], Ow[3];  // world -> camera of the searched frame (first stage)
-  float R2[9], t2[3];       // SearchBySim3: camera A -> camera B (sR, t)
-  float fx, fy, cx, cy, bf;
-  float minX, maxX, minY, maxY, invW, invH;
-  float th, logScale;
-  int nLevels, thr, checkOri;
-  float scale[ORB_MAX_LEVELS], invSigma2[ORB_MAX_LEVELS];
-};
-
-// projected point: position, predicted window and levels; valid = 0 when the
-// reference skips the point before its window scan
-struct PPRec {
-  float u, v, ur, radius;
-  int minL, maxL, valid, pad;
-};
+// (PPParams, PPRec, TriParams: orb_kernel_params.h)
 
 __device__ __forceinline__ void pp_xform(const float* R, const float* t, const float* P,
                                          float* o) {
@@ -332,13 +318,6 @@ __global__ __launch_bounds__(256) void k_sim3_mutual(const int32_t* __restrict__
 // lanes over the KF2 features of the same node; the reference keeps the LAST
 // passing candidate of minimum distance (dist <= bestDist), i.e. the minimum
 // of (dist, -position).  k_tri_finish applies the rotation filter.
-struct TriParams {
-  float F[9];
-  float ex, ey;
-  int onlyStereo, checkOri;
-  float scale[ORB_MAX_LEVELS], sigma2[ORB_MAX_LEVELS];
-};
-
 __global__ __launch_bounds__(256) void k_tri_match(
     const orb_keypoint_t* __restrict__ k1, const uint8_t* __restrict__ d1,
     const float* __restrict__ ur1, const uint8_t* __restrict__ hasMp1, int nodes1,
@@ -440,20 +419,15 @@ __global__ __launch_bounds__(256) void k_tri_finish(int nFeats1, const uint32_t*
 }
 
 // ----------------------------------------------------------------- launchers
-extern "C" size_t orb_k_pp_params_size(void) { return sizeof(PPParams); }
-extern "C" size_t orb_k_pp_rec_size(void) { return sizeof(PPRec); }
-extern "C" size_t orb_k_tri_params_size(void) { return sizeof(TriParams); }
-
 extern "C" hipError_t orb_k_pp_match(int mode, const orb_map_point_t* mps, const uint8_t* mpValid,
                                      const uint8_t* mpSkip, const uint8_t* mpDesc, int n,
                                      const orb_keypoint_t* keys, const uint8_t* desc,
                                      const float* uright, const int32_t* cellStart,
-                                     const int32_t* cellIdx, const void* params, void* recs,
+                                     const int32_t* cellIdx, const PPParams* params, PPRec* R,
                                      int32_t* best, uint32_t* topk, int32_t* ncand,
                                      hipStream_t s) {
   if (n <= 0) return hipSuccess;
-  const PPParams P = *(const PPParams*)params;
-  PPRec* R = static_cast<PPRec*>(recs);
+  const PPParams P = *params;
   const dim3 g((n + 255) / 256), b(256);
   switch (mode) {
     case PP_RELOC:
@@ -491,11 +465,11 @@ extern "C" size_t orb_k_pp_resolve_lds(int nkeys, int n) {
 extern "C" hipError_t orb_k_pp_resolve(const orb_keypoint_t* keys, const uint8_t* desc,
                                        int nkeys, const uint8_t* kpLocked, const uint8_t* mpDesc,
                                        const float* mpAngle, int n, const int32_t* cellStart,
-                                       const int32_t* cellIdx, const void* params,
-                                       const void* recs, const uint32_t* topk,
+                                       const int32_t* cellIdx, const PPParams* params,
+                                       const PPRec* recs, const uint32_t* topk,
                                        const int32_t* ncand, int32_t* kpMatch,
                                        int32_t* nmatches, hipStream_t s) {
-  const PPParams P = *(const PPParams*)params;
+  const PPParams P = *params;
   const size_t lds = orb_k_pp_resolve_lds(nkeys, n);
   if (lds > 160 * 1024) return hipErrorInvalidValue;
   if (lds > 65536) {
@@ -504,8 +478,7 @@ extern "C" hipError_t orb_k_pp_resolve(const orb_keypoint_t* keys, const uint8_t
     if (e != hipSuccess) return e;
   }
   hipLaunchKernelGGL(k_pp_resolve, dim3(1), dim3(64), lds, s, keys, desc, nkeys, kpLocked, mpDesc,
-                     mpAngle, n, cellStart, cellIdx, P, static_cast<const PPRec*>(recs), topk,
-                     ncand, kpMatch, nmatches);
+                     mpAngle, n, cellStart, cellIdx, P, recs, topk, ncand, kpMatch, nmatches);
   return hipGetLastError();
 }
 
@@ -523,8 +496,8 @@ extern "C" hipError_t orb_k_triangulation(
     int nodes1, const uint32_t* ids1, const int32_t* offs1, const uint32_t* feats1, int nFeats1,
     const orb_keypoint_t* k2, const uint8_t* d2, const float* ur2, const uint8_t* hasMp2,
     int nodes2, const uint32_t* ids2, const int32_t* offs2, const uint32_t* feats2,
-    const void* params, int32_t* match12, int32_t* acc, int32_t* nmatches, hipStream_t s) {
-  const TriParams T = *(const TriParams*)params;
+    const TriParams* params, int32_t* match12, int32_t* acc, int32_t* nmatches, hipStream_t s) {
+  const TriParams T = *params;
   if (nodes1 > 0) {
     hipLaunchKernelGGL(k_tri_match, dim3((nodes1 + 3) / 4), dim3(256), 0, s, k1, d1, ur1, hasMp1,
                        nodes1, ids1, offs1, feats1, k2, d2, ur2, hasMp2, nodes2, ids2, offs2,

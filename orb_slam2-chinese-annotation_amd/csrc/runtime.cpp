@@ -21,175 +21,8 @@
 #include <vector>
 
 #include "../../include/orb_abi.h"
-#include "orb_plan.h"
+#include "orb_kernels.h"
 #include "orb_synth.h"
-
-// ------------------------------------------------------- kernel launchers
-extern "C" {
-hipError_t orb_k_upload_constants(hipStream_t s);
-hipError_t orb_k_upload_umax(const int* umax16, hipStream_t s);
-hipError_t orb_k_pyr_resize(const uint8_t* src, long long srcImgPitch, int srcStride, int sw,
-                            int sh, uint8_t* dst, long long dstImgPitch, int dstStride, int dw,
-                            int dh, const int* xofs, const void* alpha, const int* yofs,
-                            const void* beta, int mode, int nimg, hipStream_t s);
-size_t orb_k_fast_band_lds(int bandElems);
-hipError_t orb_k_copy_pinned(void* dst, const void* src, size_t bytes, hipStream_t s);
-hipError_t orb_k_copy_to_pinned(void* dst, const void* src, size_t bytes, hipStream_t s);
-size_t orb_k_fast_cells_lds(int maxRows, int maxCols);
-bool orb_k_fast_cells_fits(const OrbPlanDesc* plan);
-
-hipError_t orb_k_pyr_resize2(const uint8_t* src, long long srcImgPitch, int srcStride, int w0,
-                             int h0, uint8_t* mid, long long midImgPitch, int midStride, int w1,
-                             int h1, const int* xo1, const void* al1, const int* yo1,
-                             const void* be1, uint8_t* dst, long long dstImgPitch, int dstStride,
-                             int w2, int h2, const int* xo2, const void* al2, const int* yo2,
-                             const void* be2, int nimg, hipStream_t s);
-int orb_k_pyr_resize2_fits(int w0, int h0, int w1, int h1, const int* xo1, const int* yo1, int w2,
-                           int h2, const int* xo2, const int* yo2);
-hipError_t orb_k_fast_cells(const uint8_t* img0, long long img0Pitch, int img0Stride,
-                            const uint8_t* arena, long long arenaPitch, const OrbPlanDesc* plan,
-                            const OrbCellDesc* cells, uint32_t* cellKeys, int32_t* cellCount,
-                            int32_t* errFlag, int cellBeg, int cellEnd, int nimg, hipStream_t s);
-hipError_t orb_k_fast_band(const uint8_t* img0, long long img0Pitch, int img0Stride,
-                           const uint8_t* arena, long long arenaPitch, const OrbPlanDesc* plan,
-                           const OrbBandDesc* bands, int nbands, const OrbCellDesc* cells,
-                           uint32_t* cellKeys, int32_t* cellCount, int32_t* errFlag, int nimg,
-                           hipStream_t s);
-size_t orb_k_octree_lds(int nodeCapMax, int maxCellsPerLevel, int ldsKeyCap);
-hipError_t orb_k_octree(const OrbPlanDesc* plan, const int32_t* cellCount,
-                        const uint32_t* cellKeys, uint32_t* gKeys, uint16_t* gNid, int ldsKeyCap,
-                        int nodeCapMax, int maxCellsPerLevel, uint32_t* outKeys,
-                        int32_t* outCount, int32_t* errFlag, int levelBeg, int levelEnd, int nimg,
-                        uint8_t* gNodes, long long nodeStride, hipStream_t s);
-hipError_t orb_k_blur_levels(const uint8_t* img0, long long img0Pitch, int img0Stride,
-                             const uint8_t* arena, long long arenaPitch, const OrbPlanDesc* plan,
-                             const OrbTileDesc* tiles, uint8_t* blur, long long blurPitch,
-                             int nimg, hipStream_t s);
-hipError_t orb_k_orient_desc(const uint8_t* img0, long long img0Pitch, int img0Stride,
-                             const uint8_t* arena, long long arenaPitch, const OrbPlanDesc* plan,
-                             const uint32_t* outKeys, const int32_t* outCount,
-                             const int32_t* errFlag, orb_keypoint_t* kps, uint8_t* desc,
-                             int capacity, int32_t* counts, int nimg, int levelBeg,
-                             int levelEnd, hipStream_t s);
-hipError_t orb_k_hamming(const uint8_t* a, const uint8_t* b, int n, int32_t* out, hipStream_t s);
-hipError_t orb_k_grid_build(const orb_keypoint_t* keys, const int32_t* nkeys, int kpStride,
-                            float minX, float minY, float invW, float invH, int32_t* cellStart,
-                            int32_t* cellIdx, int nproblems, hipStream_t s);
-hipError_t orb_k_proj_candidates(const orb_keypoint_t* keys, const uint8_t* desc,
-                                 const float* uright, const uint8_t* locked, int kpStride,
-                                 const int32_t* nkeys, const orb_mp_track_t* mps,
-                                 const uint8_t* mpDesc,
-                                 const int32_t* nmps, int mpStride, int mpMax,
-                                 const int32_t* cellStart, const int32_t* cellIdx,
-                                 const void* stagedGrid, const void* params, uint32_t* topk,
-                                 int32_t* ncand, int nproblems, hipStream_t s);
-hipError_t orb_k_grid_build_staged(const orb_keypoint_t* keys, const int32_t* nkeys,
-                                   const uint8_t* locked, const float* uright, int kpStride,
-                                   float minX, float minY, float invW, float invH,
-                                   int32_t* cellStart, int32_t* cellIdx, void* staged,
-                                   int nproblems, hipStream_t s);
-int orb_k_grid_stage_max(void);
-hipError_t orb_k_proj_resolve(const orb_keypoint_t* keys, const uint8_t* desc,
-                              const float* uright, const uint8_t* locked, const int32_t* nkeys,
-                              int kpStride, const orb_mp_track_t* mps, const uint8_t* mpDesc,
-                              const int32_t* nmps, int mpStride, const int32_t* cellStart,
-                              const int32_t* cellIdx, const void* params, const uint32_t* topk,
-                              const int32_t* ncand, int32_t* kpMatch, int32_t* nmatches,
-                              int nproblems, int schedule, int jacobiRounds, int32_t* jacScratch,
-                              hipStream_t s);
-int orb_k_proj_resolve_kernel(int nproblems, int kpStride, int mpStride, int schedule);
-size_t orb_k_proj_jacobi_bytes(int kpStride, int mpStride, int nproblems, int schedule);
-size_t orb_k_proj_params_size(void);
-size_t orb_k_proj_ovf_bytes(int nproblems);
-size_t orb_k_stereo_params_size(void);
-hipError_t orb_k_stereo(const orb_keypoint_t* lkeys, const uint8_t* ldesc, const int32_t* nleft,
-                        const orb_keypoint_t* rkeys, const uint8_t* rdesc, const int32_t* nright,
-                        int kpStride, int maxLeft, const void* pyr, const void* params,
-                        float* uRight, float* depth, int32_t* sad, int npairs,
-                        int32_t* rowStart, int32_t* rowIdx, hipStream_t s);
-void orb_k_stereo_scratch(const void* params, int kpStride, size_t* startInts, size_t* idxInts);
-size_t orb_k_frame_params_size(void);
-size_t orb_k_frustum_params_size(void);
-hipError_t orb_k_frustum(const orb_map_point_t* mps, const int32_t* nmps, int mpStride,
-                         int mpMax, const orb_pose_t* poses, const void* params,
-                         orb_mp_track_t* tracks, int32_t* nInView, int nproblems, hipStream_t s);
-hipError_t orb_k_frame_proj(const orb_keypoint_t* keys, const uint8_t* desc, const float* uright,
-                            const uint8_t* locked, int nkeys, const orb_last_mp_t* last,
-                            const uint8_t* lastDesc, int nlast, const int32_t* cellStart,
-                            const int32_t* cellIdx, const void* params, uint32_t* topk,
-                            int32_t* ncand, int32_t* kpMatch, int32_t* nmatches, hipStream_t s);
-hipError_t orb_k_bow(const uint8_t* kfDesc, const float* kfAngle, const int32_t* kfMp,
-                     const uint8_t* kfBad, int kfNodes, const uint32_t* kfNodeIds,
-                     const int32_t* kfOffs, const uint32_t* kfFeats, int nKfFeats,
-                     const uint8_t* fDesc, const float* fAngle, int fNodes,
-                     const uint32_t* fNodeIds, const int32_t* fOffs, const uint32_t* fFeats,
-                     int nF, const int32_t* fMp, const uint8_t* fBad, int thLow,
-                     float nnratio, int checkOri, int32_t* fMatch, int32_t* accF,
-                     int32_t* nmatches, hipStream_t s);
-size_t orb_k_pp_params_size(void);
-size_t orb_k_pp_rec_size(void);
-size_t orb_k_tri_params_size(void);
-size_t orb_k_pp_resolve_lds(int nkeys, int n);
-hipError_t orb_k_pp_match(int mode, const orb_map_point_t* mps, const uint8_t* mpValid,
-                          const uint8_t* mpSkip, const uint8_t* mpDesc, int n,
-                          const orb_keypoint_t* keys, const uint8_t* desc, const float* uright,
-                          const int32_t* cellStart, const int32_t* cellIdx, const void* params,
-                          void* recs, int32_t* best, uint32_t* topk, int32_t* ncand,
-                          hipStream_t s);
-hipError_t orb_k_pp_resolve(const orb_keypoint_t* keys, const uint8_t* desc, int nkeys,
-                            const uint8_t* kpLocked, const uint8_t* mpDesc, const float* mpAngle,
-                            int n, const int32_t* cellStart, const int32_t* cellIdx,
-                            const void* params, const void* recs, const uint32_t* topk,
-                            const int32_t* ncand, int32_t* kpMatch, int32_t* nmatches,
-                            hipStream_t s);
-hipError_t orb_k_sim3_mutual(const int32_t* m1, int n1, const int32_t* m2, int32_t* match12,
-                             int32_t* nfound, hipStream_t s);
-hipError_t orb_k_triangulation(const orb_keypoint_t* k1, const uint8_t* d1, const float* ur1,
-                               const uint8_t* hasMp1, int nodes1, const uint32_t* ids1,
-                               const int32_t* offs1, const uint32_t* feats1, int nFeats1,
-                               const orb_keypoint_t* k2, const uint8_t* d2, const float* ur2,
-                               const uint8_t* hasMp2, int nodes2, const uint32_t* ids2,
-                               const int32_t* offs2, const uint32_t* feats2, const void* params,
-                               int32_t* match12, int32_t* acc, int32_t* nmatches, hipStream_t s);
-size_t orb_k_init_params_size(void);
-size_t orb_k_init_list_len(void);
-size_t orb_k_init_topk(void);
-size_t orb_k_init_lds(int kpStride);
-hipError_t orb_k_search_init(const orb_keypoint_t* keys1, const uint8_t* desc1, const int32_t* n1,
-                             const orb_keypoint_t* keys2, const uint8_t* desc2, const int32_t* n2,
-                             int kpStride, float* prev, const int32_t* cellStart,
-                             const int32_t* cellIdx, const void* params, int32_t* qList,
-                             int32_t* qOrder, int32_t* nQ, void* stage, int32_t* nStage, uint32_t* topk,
-                             uint32_t* list, int32_t* ncand, int32_t* m12, int32_t* nmatches,
-                             int nproblems, hipStream_t s);
-size_t orb_k_init_key_size(void);
-hipError_t orb_k_distinctive(const int32_t* offs, const uint8_t* desc, int nmp, int32_t* best,
-                             uint8_t* out, hipStream_t s);
-hipError_t orb_k_voc_descend(const void* info, const void* ndesc, const uint32_t* nword,
-                             const double* nweight, const uint32_t* norig, int nidLevel,
-                             const uint8_t* desc, const int32_t* counts, int nSingle, int stride,
-                             int nFrames, uint32_t* fword, double* fweight, uint32_t* fnode,
-                             hipStream_t s);
-int orb_k_voc_max_features(void);
-hipError_t orb_k_undistort_points(const void* params, int n, const float* in, float* out,
-                                  hipStream_t s);
-hipError_t orb_k_undistort_keys(const void* params, int nFrames, const int32_t* counts,
-                                int nSingle, int stride, const void* in, void* out, int copyOnly,
-                                hipStream_t s);
-size_t orb_k_undistort_params_size(void);
-hipError_t orb_k_voc_vectors(const uint32_t* fword, const double* fweight, const uint32_t* fnode,
-                             const int32_t* counts, int nSingle, int stride, int tf, int must,
-                             int l2, int nFrames, uint32_t* bowWords, double* bowValues,
-                             int32_t* nWords, uint32_t* fvNodes, int32_t* fvOffs,
-                             uint32_t* fvFeats, int32_t* nFv, hipStream_t s);
-hipError_t orb_k_bow_score(int type, int nPairs, const int32_t* aOffs, const uint32_t* aWords,
-                           const double* aValues, const int32_t* bOffs, const uint32_t* bWords,
-                           const double* bValues, double* out, hipStream_t s);
-size_t orb_k_db_slot_size(void);
-size_t orb_k_db_key_scratch(int nSlots);
-size_t orb_k_db_query_args_size(void);
-hipError_t orb_k_db_query(const void* args, hipStream_t s);
-}
 
 namespace {
 
@@ -270,10 +103,15 @@ static hipError_t stream_wait(hipStream_t s) {
   }
 }
 
-// Growable device buffer.
+// Growable device buffer, freed with the handle that owns it (the handle's
+// destroy function sets the device and drains its stream first).
 struct DevBuf {
   void* p = nullptr;
   size_t bytes = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() { release(); }
   orb_status_t ensure(size_t n) {
     if (n <= bytes) return ORB_OK;
     if (p) hipFree(p);
@@ -297,6 +135,10 @@ struct DevBuf {
 struct HostBuf {
   void* p = nullptr;
   size_t bytes = 0;
+  HostBuf() = default;
+  HostBuf(const HostBuf&) = delete;
+  HostBuf& operator=(const HostBuf&) = delete;
+  ~HostBuf() { release(); }
   orb_status_t ensure(size_t n) {
     if (n <= bytes) return ORB_OK;
     if (p) hipHostFree(p);
@@ -1178,23 +1020,18 @@ void orb_extractor_destroy(orb_extractor_t* h) {
   hipSetDevice(h->device);
   if (h->stream) hipStreamSynchronize(h->stream);
   if (h->lastStream) hipEventSynchronize(h->evBatch);  // a batch call on a caller's stream
-  DevBuf* bufs[] = {&h->dCells, &h->dRtab, &h->dTiles, &h->dBlur, &h->dArena, &h->dCellKeys, &h->dCellCount, &h->dOctNodes,
-                    &h->dGKeys, &h->dGNid, &h->dOutKeys, &h->dOutCount, &h->dErr,
-                    &h->dImg, &h->dOne};
-  for (DevBuf* b : bufs) b->release();
-  h->hImg.release();
-  h->hOut.release();
-  h->hLvl.release();
-  h->hPyr.release();
-  if (h->oneExec) hipGraphExecDestroy(h->oneExec);
   h->prof.destroy();
-  if (h->ownStream && h->stream) hipStreamDestroy(h->stream);
-  if (h->privSide) hipStreamDestroy(h->privSide);
-  if (h->evL0Fork) hipEventDestroy(h->evL0Fork);
-  if (h->evL0Join) hipEventDestroy(h->evL0Join);
-  if (h->evLvl) hipEventDestroy(h->evLvl);
-  if (h->evBatch) hipEventDestroy(h->evBatch);
+  // the handle's buffers go with it (DevBuf, HostBuf), before its graph,
+  // streams and events
+  const hipGraphExec_t exec = h->oneExec;
+  const hipStream_t streams[] = {h->ownStream ? h->stream : nullptr, h->privSide};
+  const hipEvent_t events[] = {h->evL0Fork, h->evL0Join, h->evLvl, h->evBatch};
   delete h;
+  if (exec) hipGraphExecDestroy(exec);
+  for (hipStream_t s : streams)
+    if (s) hipStreamDestroy(s);
+  for (hipEvent_t e : events)
+    if (e) hipEventDestroy(e);
 }
 
 int orb_extractor_get_levels(const orb_extractor_t* h) { return h ? h->nlevels : 0; }
@@ -1518,17 +1355,10 @@ orb_status_t orb_extractor_profile_read(orb_extractor_t* h, int stage, double* t
 }  // extern "C"
 
 // ================================================================== matcher
-struct FrustumParamsHost {  // mirrors FrustumParams in matcher_kernels.hip
-  float fx, fy, cx, cy, bf;
-  float minX, maxX, minY, maxY;
-  float cosLimit, logScale;
-  int nLevels;
-};
-
-static FrustumParamsHost frustum_params(const orb_camera_t* cam, float min_x, float max_x,
-                                        float min_y, float max_y, float cos_limit,
-                                        float log_scale, int n_levels) {
-  FrustumParamsHost f;
+static FrustumParams frustum_params(const orb_camera_t* cam, float min_x, float max_x,
+                                    float min_y, float max_y, float cos_limit, float log_scale,
+                                    int n_levels) {
+  FrustumParams f;
   f.fx = cam->fx;
   f.fy = cam->fy;
   f.cx = cam->cx;
@@ -1544,56 +1374,17 @@ static FrustumParamsHost frustum_params(const orb_camera_t* cam, float min_x, fl
   return f;
 }
 
-struct ProjParamsHost {  // mirrors ProjParams in matcher_common.h
-  float minX, minY, invW, invH;
-  float th, nnratio;
-  int nLevels;
-  float scale[ORB_MAX_LEVELS];
-  uint32_t* ovf;
-  uint32_t* ovfCtr;
-  uint32_t gen;
-};
-
-struct StereoParamsHost {  // mirrors StereoParams in matcher_kernels.hip
-  int nLevels;
-  float bf, fx;
-  int w[ORB_MAX_LEVELS], h[ORB_MAX_LEVELS];
-  int strideL[ORB_MAX_LEVELS], strideR[ORB_MAX_LEVELS];
-  float scale[ORB_MAX_LEVELS], invScale[ORB_MAX_LEVELS];
-};
-struct StereoPairLevelsHost {
-  const uint8_t* L[ORB_MAX_LEVELS];
-  const uint8_t* R[ORB_MAX_LEVELS];
-};
-struct FrameProjParamsHost {  // mirrors FrameProjParams
-  float minX, maxX, minY, maxY, invW, invH;
-  float fx, fy, cx, cy, bf;
-  float th;
-  int fwd, bwd, checkOri;
-  float scale[ORB_MAX_LEVELS];
-};
-
-struct PPParamsHost {  // mirrors PPParams in projection_kernels.hip
-  float R[9], t[3], Ow[3];
-  float R2[9], t2[3];
-  float fx, fy, cx, cy, bf;
-  float minX, maxX, minY, maxY, invW, invH;
-  float th, logScale;
-  int nLevels, thr, checkOri;
-  float scale[ORB_MAX_LEVELS], invSigma2[ORB_MAX_LEVELS];
-};
-
-struct TriParamsHost {  // mirrors TriParams
-  float F[9];
-  float ex, ey;
-  int onlyStereo, checkOri;
-  float scale[ORB_MAX_LEVELS], sigma2[ORB_MAX_LEVELS];
-};
-
-struct InitParamsHost {  // mirrors InitParams in mapping_kernels.hip
-  float minX, minY, invW, invH;
-  float r, nnratio;
-  int checkOri;
+// orb_matcher::sx, the scratch of the projection-window variants (PP_*), of
+// KF-KF SearchByBoW (BW_*) and of SearchForTriangulation (TR_*): three calls
+// that never overlap name the same buffers.
+enum MatcherSlot {
+  PP_FRAME0 = 0, PP_FRAME1 = 4,  // two searched (key)frames: keys, desc, n, grid (PPFrame)
+  PP_MPS = 8, PP_MPDESC, PP_VALID, PP_SKIP, PP_ANGLE, PP_URIGHT, PP_RECS, PP_TOPK, PP_NCAND,
+  PP_BEST, PP_LOCKED, PP_KPMATCH, PP_COUNT, PP_BEST12, PP_BEST21, PP_MUTUAL, SX_COUNT,
+  BW_DESC1 = 0, BW_ANGLE1, BW_MP1, BW_BAD1, BW_IDS1, BW_OFFS1, BW_FEATS1,
+  BW_DESC2, BW_ANGLE2, BW_MP2, BW_BAD2, BW_IDS2, BW_OFFS2, BW_FEATS2, BW_MATCH, BW_ACC, BW_COUNT,
+  TR_KEYS1 = 0, TR_DESC1, TR_UR1, TR_HASMP1, TR_IDS1, TR_OFFS1, TR_FEATS1,
+  TR_KEYS2, TR_DESC2, TR_UR2, TR_HASMP2, TR_IDS2, TR_OFFS2, TR_FEATS2, TR_MATCH, TR_ACC, TR_COUNT
 };
 
 struct orb_matcher {
@@ -1628,7 +1419,7 @@ struct orb_matcher {
   // SearchForInitialization / ComputeDistinctiveDescriptors scratch
   DevBuf dK1, dD1, dK2, dD2, dN1, dN2, dPrev, dList, dM12, dOffs, dObsDesc, dBest, dBestDesc,
       dInitQ, dInitStage, dInitCounts;
-  DevBuf sx[24];  // projection / triangulation / KF-KF BoW scratch
+  DevBuf sx[SX_COUNT];  // projection / triangulation / KF-KF BoW scratch (MatcherSlot)
   std::vector<uint8_t> hostScratch;
 };
 
@@ -1652,14 +1443,6 @@ orb_status_t orb_matcher_create(int device, orb_matcher_t** out) {
   *out = nullptr;
   orb_status_t st = check_device(device);
   if (st) return st;
-  if (orb_k_proj_params_size() != sizeof(ProjParamsHost) ||
-      orb_k_stereo_params_size() != sizeof(StereoParamsHost) ||
-      orb_k_frame_params_size() != sizeof(FrameProjParamsHost) ||
-      orb_k_frustum_params_size() != sizeof(FrustumParamsHost) ||
-      orb_k_init_params_size() != sizeof(InitParamsHost) ||
-      orb_k_pp_params_size() != sizeof(PPParamsHost) ||
-      orb_k_tri_params_size() != sizeof(TriParamsHost))
-    return ORB_EINVAL;
   orb_matcher* m = new orb_matcher();
   m->device = device;
   m->prof.nStages = 3;
@@ -1686,26 +1469,12 @@ void orb_matcher_destroy(orb_matcher_t* m) {
   hipSetDevice(m->device);
   hipStreamSynchronize(m->stream);
   if (m->lastStream) hipEventSynchronize(m->evLast);  // a batch call on a caller's stream
-  DevBuf* bufs[] = {&m->dKeys, &m->dDesc, &m->dUr, &m->dLocked, &m->dNKeys, &m->dMps,
-                    &m->dMpDesc, &m->dNMps, &m->dCellStart, &m->dCellIdx, &m->dTopk,
-                    &m->dNcand, &m->dKpMatch, &m->dNMatch, &m->dA, &m->dB, &m->dOut, &m->dJac,
-                    &m->dRKeys, &m->dRDesc, &m->dNR, &m->dPyr, &m->dPairLv, &m->dDepth,
-                    &m->dSad, &m->dStRowStart, &m->dStRowIdx, &m->dProjStage, &m->dBowA, &m->dBowB, &m->dBowC, &m->dBowD, &m->dBowE,
-                    &m->dBowF, &m->dBowG, &m->dBowH, &m->dBowI, &m->dBowJ, &m->dBowK,
-                    &m->dMapPts, &m->dPose, &m->dTracks, &m->dNInView, &m->dK1, &m->dD1,
-                    &m->dK2, &m->dD2, &m->dN1, &m->dN2, &m->dPrev, &m->dList, &m->dM12,
-                    &m->dOffs, &m->dObsDesc, &m->dBest, &m->dBestDesc, &m->dInitQ,
-                    &m->dInitStage, &m->dInitCounts, &m->dOvf, &m->dOvfCtr};
-  for (DevBuf* b : bufs) b->release();
-  m->hPyr.release();
-  m->hIn.release();
-  m->hOutM.release();
-  m->dIn.release();
-  for (DevBuf& b : m->sx) b.release();
   m->prof.destroy();
-  hipStreamDestroy(m->stream);
-  hipEventDestroy(m->evLast);
-  delete m;
+  const hipStream_t stream = m->stream;
+  const hipEvent_t evLast = m->evLast;
+  delete m;  // frees every buffer (DevBuf, HostBuf)
+  hipStreamDestroy(stream);
+  hipEventDestroy(evLast);
 }
 
 void* orb_matcher_stream(orb_matcher_t* m) { return m ? (void*)m->stream : nullptr; }
@@ -1718,9 +1487,9 @@ orb_status_t orb_hamming_batch(orb_matcher_t* m, const uint8_t* d_a, const uint8
   return ORB_OK;
 }
 
-static ProjParamsHost proj_params(float min_x, float max_x, float min_y, float max_y,
+static ProjParams proj_params(float min_x, float max_x, float min_y, float max_y,
                                   int n_levels, const float* scale, float th, float nnratio) {
-  ProjParamsHost P;
+  ProjParams P;
   memset(&P, 0, sizeof(P));
   P.minX = min_x;
   P.minY = min_y;
@@ -1737,7 +1506,7 @@ static ProjParamsHost proj_params(float min_x, float max_x, float min_y, float m
 // The candidate-list pool of n problems for this call (ProjParams.ovf): the
 // per-problem slot counters are tagged with the call's gen, so they need no
 // reset between calls -- only a zero fill when (re)allocated.
-static orb_status_t ovf_pool(orb_matcher_t* m, int nproblems, ProjParamsHost& P, hipStream_t s) {
+static orb_status_t ovf_pool(orb_matcher_t* m, int nproblems, ProjParams& P, hipStream_t s) {
   orb_status_t st;
   if ((st = m->dOvf.ensure(orb_k_proj_ovf_bytes(nproblems)))) return st;
   const size_t oldBytes = m->dOvfCtr.bytes;  // (a reallocation may return the old address)
@@ -1769,7 +1538,7 @@ orb_status_t orb_match_projection_local_batch(
   hipStream_t s = stream ? (hipStream_t)stream : m->stream;
   CallOrder order(m->evLast, &m->lastStream, s);
   if (order.status) return order.status;
-  ProjParamsHost P =
+  ProjParams P =
       proj_params(min_x, max_x, min_y, max_y, n_levels, scale_factors, th, nnratio);
   orb_status_t st;
   if ((st = ovf_pool(m, n_problems, P, s))) return st;
@@ -1922,7 +1691,7 @@ static orb_status_t local_ensure(orb_matcher_t* m, int N, int M, const LocalLayo
 }
 
 // DMA of bytes [b0, b1) of the block, then (b0 == 0) the keypoint grid
-static orb_status_t local_front(orb_matcher_t* m, int N, const LocalLayout& L, const ProjParamsHost& P,
+static orb_status_t local_front(orb_matcher_t* m, int N, const LocalLayout& L, const ProjParams& P,
                                 bool urOn, bool lkOn, size_t b1, hipStream_t s) {
   HIP_TRY(orb_k_copy_pinned(m->dIn.p, m->hIn.p, b1, s));
   uint8_t* din = m->dIn.as<uint8_t>();
@@ -1950,7 +1719,7 @@ static orb_status_t local_run(orb_matcher_t* m, int N, int M, const orb_frame_t*
   hipStream_t s = m->stream;
   CallOrder order(m->evLast, &m->lastStream, s);
   if (order.status) return order.status;
-  ProjParamsHost P = proj_params(F->min_x, F->max_x, F->min_y, F->max_y, F->n_levels,
+  ProjParams P = proj_params(F->min_x, F->max_x, F->min_y, F->max_y, F->n_levels,
                                  F->scale_factors, th, nnratio);
   if ((st = ovf_pool(m, 1, P, s))) return st;
   if (!begun) {
@@ -2055,7 +1824,7 @@ orb_status_t orb_match_projection_local_begin(orb_matcher_t* m, const orb_frame_
   CallOrder order(m->evLast, &m->lastStream, s);
   if (order.status) return order.status;
   // (th and nnratio do not enter the grid)
-  const ProjParamsHost P = proj_params(frame->min_x, frame->max_x, frame->min_y, frame->max_y,
+  const ProjParams P = proj_params(frame->min_x, frame->max_x, frame->min_y, frame->max_y,
                                        frame->n_levels, frame->scale_factors, 1.f, 0.f);
   if ((st = local_front(m, N, L, P, stereo != 0, locked != 0, L.oMps, s))) return st;
   m->begun = true;
@@ -2112,8 +1881,8 @@ orb_status_t orb_frustum(orb_matcher_t* m, int n_mp, const orb_map_point_t* mps,
   HIP_TRY(hipMemcpyAsync(m->dPose.p, pose, sizeof(orb_pose_t), hipMemcpyHostToDevice, s));
   const int32_t nm = n_mp;
   HIP_TRY(hipMemcpyAsync(m->dNMps.p, &nm, 4, hipMemcpyHostToDevice, s));
-  const FrustumParamsHost fp = frustum_params(cam, min_x, max_x, min_y, max_y, viewing_cos_limit,
-                                              log_scale_factor, n_levels);
+  const FrustumParams fp = frustum_params(cam, min_x, max_x, min_y, max_y, viewing_cos_limit,
+                                          log_scale_factor, n_levels);
   HIP_TRY(orb_k_frustum(m->dMapPts.as<orb_map_point_t>(), m->dNMps.as<int32_t>(), n_mp, n_mp,
                         m->dPose.as<orb_pose_t>(), &fp, m->dTracks.as<orb_mp_track_t>(),
                         m->dNInView.as<int32_t>(), 1, s));
@@ -2138,8 +1907,8 @@ orb_status_t orb_frustum_batch(orb_matcher_t* m, int n_problems, const orb_map_p
     return ORB_EINVAL;
   hipSetDevice(m->device);
   hipStream_t s = stream ? (hipStream_t)stream : m->stream;
-  const FrustumParamsHost fp = frustum_params(cam, min_x, max_x, min_y, max_y, viewing_cos_limit,
-                                              log_scale_factor, n_levels);
+  const FrustumParams fp = frustum_params(cam, min_x, max_x, min_y, max_y, viewing_cos_limit,
+                                          log_scale_factor, n_levels);
   HIP_TRY(orb_k_frustum(d_mps, d_nmps, mp_stride, mp_stride, d_poses, &fp, d_tracks, d_n_in_view,
                         n_problems, s));
   return ORB_OK;
@@ -2154,7 +1923,8 @@ static orb_status_t upload(DevBuf& b, const void* src, size_t n, hipStream_t s) 
 }
 
 // the row-index scratch of orb_k_stereo for n_pairs pairs
-static orb_status_t stereo_scratch(orb_matcher* m, const void* params, int kpStride, int npairs) {
+static orb_status_t stereo_scratch(orb_matcher* m, const StereoParams* params, int kpStride,
+                                   int npairs) {
   size_t a = 0, b = 0;
   orb_k_stereo_scratch(params, kpStride, &a, &b);
   orb_status_t st = m->dStRowStart.ensure(std::max<size_t>(a * npairs, 1) * 4);
@@ -2195,7 +1965,7 @@ orb_status_t orb_stereo_match(orb_matcher_t* m, const orb_stereo_input_t* in, fl
   if ((st = upload(m->dNKeys, &nl, 4, s))) return st;
   if ((st = upload(m->dNR, &nr, 4, s))) return st;
   // both pyramids, packed with 64-byte pitches
-  StereoParamsHost P;
+  StereoParams P;
   memset(&P, 0, sizeof(P));
   P.nLevels = L;
   P.bf = in->bf;
@@ -2212,7 +1982,7 @@ orb_status_t orb_stereo_match(orb_matcher_t* m, const orb_stereo_input_t* in, fl
     total += 2 * (size_t)P.strideL[l] * P.h[l];
   }
   if ((st = m->dPyr.ensure(total))) return st;
-  StereoPairLevelsHost lv;
+  StereoPairLevels lv;
   memset(&lv, 0, sizeof(lv));
   uint8_t* base = m->dPyr.as<uint8_t>();
   // both pyramids -> pinned staging in the device layout -> one DMA (2-D copies
@@ -2238,7 +2008,8 @@ orb_status_t orb_stereo_match(orb_matcher_t* m, const orb_stereo_input_t* in, fl
   if ((st = stereo_scratch(m, &P, stride, 1))) return st;
   HIP_TRY(orb_k_stereo(m->dKeys.as<orb_keypoint_t>(), m->dDesc.as<uint8_t>(),
                        m->dNKeys.as<int32_t>(), m->dRKeys.as<orb_keypoint_t>(),
-                       m->dRDesc.as<uint8_t>(), m->dNR.as<int32_t>(), stride, NL, m->dPairLv.p, &P,
+                       m->dRDesc.as<uint8_t>(), m->dNR.as<int32_t>(), stride, NL,
+                       m->dPairLv.as<StereoPairLevels>(), &P,
                        m->dUr.as<float>(), m->dDepth.as<float>(), m->dSad.as<int32_t>(), 1,
                        m->dStRowStart.as<int32_t>(), m->dStRowIdx.as<int32_t>(), s));
   HIP_TRY(hipMemcpyAsync(u_right, m->dUr.p, (size_t)NL * 4, hipMemcpyDeviceToHost, s));
@@ -2265,16 +2036,16 @@ orb_status_t orb_stereo_match_batch(orb_matcher_t* m, int n_pairs, orb_extractor
   hipStream_t s = stream ? (hipStream_t)stream : m->stream;
   CallOrder order(m->evLast, &m->lastStream, s);
   if (order.status) return order.status;
-  StereoParamsHost P;
+  StereoParams P;
   memset(&P, 0, sizeof(P));
   P.nLevels = L;
   P.bf = bf;
   P.fx = fx;
   orb_extractor_get_scale_factors(left_ext, P.scale);
   orb_extractor_get_inverse_scale_factors(left_ext, P.invScale);
-  std::vector<StereoPairLevelsHost> lv(n_pairs);
+  std::vector<StereoPairLevels> lv(n_pairs);
   for (int i = 0; i < n_pairs; ++i) {
-    memset(&lv[i], 0, sizeof(StereoPairLevelsHost));
+    memset(&lv[i], 0, sizeof(StereoPairLevels));
     for (int l = 0; l < L; ++l) {
       int wl, hl, wr, hr;
       size_t sl, sr;
@@ -2289,13 +2060,13 @@ orb_status_t orb_stereo_match_batch(orb_matcher_t* m, int n_pairs, orb_extractor
       P.strideR[l] = (int)sr;
     }
   }
-  orb_status_t st = m->dPairLv.ensure(lv.size() * sizeof(StereoPairLevelsHost));
+  orb_status_t st = m->dPairLv.ensure(lv.size() * sizeof(StereoPairLevels));
   if (st) return st;
-  HIP_TRY(hipMemcpyAsync(m->dPairLv.p, lv.data(), lv.size() * sizeof(StereoPairLevelsHost),
+  HIP_TRY(hipMemcpyAsync(m->dPairLv.p, lv.data(), lv.size() * sizeof(StereoPairLevels),
                          hipMemcpyHostToDevice, s));
   if ((st = stereo_scratch(m, &P, kp_stride, n_pairs))) return st;
   HIP_TRY(orb_k_stereo(d_left_keys, d_left_desc, d_left_n, d_right_keys, d_right_desc, d_right_n,
-                       kp_stride, kp_stride, m->dPairLv.p, &P, d_u_right, d_depth, d_sad,
+                       kp_stride, kp_stride, m->dPairLv.as<StereoPairLevels>(), &P, d_u_right, d_depth, d_sad,
                        n_pairs, m->dStRowStart.as<int32_t>(), m->dStRowIdx.as<int32_t>(), s));
   // the pair-level pointer table must outlive the asynchronous launch
   HIP_TRY(stream_wait(s));
@@ -2339,14 +2110,14 @@ orb_status_t orb_stereo_match_extracted(orb_matcher_t* m, orb_extractor_t* left_
   if (order.status) return order.status;
   HIP_TRY(hipStreamWaitEvent(s, left_ext->evBatch, 0));
   HIP_TRY(hipStreamWaitEvent(s, right_ext->evBatch, 0));
-  StereoParamsHost P;
+  StereoParams P;
   memset(&P, 0, sizeof(P));
   P.nLevels = L;
   P.bf = bf;
   P.fx = fx;
   std::copy(left_ext->scale.begin(), left_ext->scale.end(), P.scale);
   std::copy(left_ext->invScale.begin(), left_ext->invScale.end(), P.invScale);
-  StereoPairLevelsHost lv;
+  StereoPairLevels lv;
   memset(&lv, 0, sizeof(lv));
   for (int l = 0; l < L; ++l) {
     const OrbLevelDesc& dl = left_ext->plan.lv[l];
@@ -2385,7 +2156,8 @@ orb_status_t orb_stereo_match_extracted(orb_matcher_t* m, orb_extractor_t* left_
                        reinterpret_cast<const int32_t*>(l1),
                        reinterpret_cast<const orb_keypoint_t*>(r1 + 16),
                        r1 + 16 + (size_t)right_ext->oneCap * sizeof(orb_keypoint_t),
-                       reinterpret_cast<const int32_t*>(r1), stride, nL, m->dPairLv.p, &P,
+                       reinterpret_cast<const int32_t*>(r1), stride, nL,
+                       m->dPairLv.as<StereoPairLevels>(), &P,
                        m->dUr.as<float>(), m->dDepth.as<float>(), m->dSad.as<int32_t>(), 1,
                        m->dStRowStart.as<int32_t>(), m->dStRowIdx.as<int32_t>(), s));
   HIP_TRY(hipMemcpyAsync(m->hPyr.p, m->dUr.p, (size_t)nL * 4, hipMemcpyDeviceToHost, s));
@@ -2433,7 +2205,7 @@ orb_status_t orb_match_projection_frame(orb_matcher_t* m, const orb_frame_t* C,
   if ((st = m->dNcand.ensure((size_t)std::max(M, 1) * 4))) return st;
   if ((st = m->dKpMatch.ensure((size_t)N * 4))) return st;
   if ((st = m->dNMatch.ensure(16))) return st;
-  FrameProjParamsHost P;
+  FrameProjParams P;
   memset(&P, 0, sizeof(P));
   P.minX = C->min_x; P.maxX = C->max_x; P.minY = C->min_y; P.maxY = C->max_y;
   P.invW = (float)ORB_GRID_COLS / (C->max_x - C->min_x);
@@ -2519,7 +2291,7 @@ static orb_status_t search_init_device(orb_matcher_t* m, int P, const orb_keypoi
                                        float max_x, float min_y, float max_y, int window_size,
                                        float nnratio, int check_orientation, float* d_prev,
                                        int32_t* d_m12, int32_t* d_nmatches, hipStream_t s) {
-  InitParamsHost ip;
+  InitParams ip;
   memset(&ip, 0, sizeof(ip));
   ip.minX = min_x;
   ip.minY = min_y;
@@ -2536,7 +2308,7 @@ static orb_status_t search_init_device(orb_matcher_t* m, int P, const orb_keypoi
   if ((st = m->dList.ensure(slots * orb_k_init_list_len() * 4))) return st;
   if ((st = m->dNcand.ensure(slots * 4))) return st;
   if ((st = m->dInitQ.ensure(slots * 8))) return st;
-  if ((st = m->dInitStage.ensure(slots * orb_k_init_key_size()))) return st;
+  if ((st = m->dInitStage.ensure(slots * sizeof(InitKey)))) return st;
   if ((st = m->dInitCounts.ensure((size_t)P * 8))) return st;
   HIP_TRY(orb_k_grid_build(d_keys2, d_n2, kp_stride, ip.minX, ip.minY, ip.invW, ip.invH,
                            m->dCellStart.as<int32_t>(), m->dCellIdx.as<int32_t>(), P, s));
@@ -2544,7 +2316,7 @@ static orb_status_t search_init_device(orb_matcher_t* m, int P, const orb_keypoi
                             m->dCellStart.as<int32_t>(), m->dCellIdx.as<int32_t>(), &ip,
                             m->dInitQ.as<int32_t>(), m->dInitQ.as<int32_t>() + slots,
                             m->dInitCounts.as<int32_t>(),
-                            m->dInitStage.p, m->dInitCounts.as<int32_t>() + P,
+                            m->dInitStage.as<InitKey>(), m->dInitCounts.as<int32_t>() + P,
                             m->dTopk.as<uint32_t>(), m->dList.as<uint32_t>(),
                             m->dNcand.as<int32_t>(), d_m12, d_nmatches, P, s));
   return ORB_OK;
@@ -2691,7 +2463,7 @@ static void sim3_normalise(const float* S, float* R, float* t, float* Ow) {
   rt_center(R, t, Ow);
 }
 
-static orb_status_t pp_base(PPParamsHost& P, const orb_frame_t* K, const orb_camera_t* cam,
+static orb_status_t pp_base(PPParams& P, const orb_frame_t* K, const orb_camera_t* cam,
                             float logScale, float th, int thr) {
   memset(&P, 0, sizeof(P));
   if (!K || !cam || K->n_levels <= 0 || K->n_levels > ORB_MAX_LEVELS || !K->scale_factors ||
@@ -2709,32 +2481,34 @@ static orb_status_t pp_base(PPParamsHost& P, const orb_frame_t* K, const orb_cam
   return ORB_OK;
 }
 
-// upload the searched (key)frame and build its grid; slots 0..3
-static orb_status_t pp_frame(orb_matcher_t* m, const orb_frame_t* K, const PPParamsHost& P,
+// the buffers of a searched (key)frame: slot PP_FRAME0 or PP_FRAME1 of m->sx
+struct PPFrame {
+  DevBuf &keys, &desc, &n, &grid;  // grid: cell starts, then the cell-ordered indices
+  PPFrame(orb_matcher_t* m, int slot)
+      : keys(m->sx[slot]), desc(m->sx[slot + 1]), n(m->sx[slot + 2]), grid(m->sx[slot + 3]) {}
+  int32_t* cells() const { return grid.as<int32_t>(); }
+  int32_t* cellidx() const { return grid.as<int32_t>() + ORB_GRID_COLS * ORB_GRID_ROWS + 1; }
+};
+
+// upload the searched (key)frame and build its grid
+static orb_status_t pp_frame(orb_matcher_t* m, const orb_frame_t* K, const PPParams& P,
                              int slot, hipStream_t s) {
   orb_status_t st;
   const int n = K->n;
+  const PPFrame f(m, slot);
   if (n > 0 && (!K->keys || !K->descriptors)) return ORB_EINVAL;
-  if ((st = upload(m->sx[slot], K->keys, (size_t)n * sizeof(orb_keypoint_t), s))) return st;
-  if ((st = upload(m->sx[slot + 1], K->descriptors, (size_t)n * 32, s))) return st;
-  if ((st = upload(m->sx[slot + 2], &n, 4, s))) return st;
-  if ((st = m->sx[slot + 3].ensure(((size_t)(ORB_GRID_COLS * ORB_GRID_ROWS + 1) + n + 1) * 4)))
-    return st;
-  int32_t* cs = m->sx[slot + 3].as<int32_t>();
-  HIP_TRY(orb_k_grid_build(m->sx[slot].as<orb_keypoint_t>(), m->sx[slot + 2].as<int32_t>(),
-                           std::max(n, 1), P.minX, P.minY, P.invW, P.invH, cs,
-                           cs + ORB_GRID_COLS * ORB_GRID_ROWS + 1, 1, s));
+  if ((st = upload(f.keys, K->keys, (size_t)n * sizeof(orb_keypoint_t), s))) return st;
+  if ((st = upload(f.desc, K->descriptors, (size_t)n * 32, s))) return st;
+  if ((st = upload(f.n, &n, 4, s))) return st;
+  if ((st = f.grid.ensure(((size_t)(ORB_GRID_COLS * ORB_GRID_ROWS + 1) + n + 1) * 4))) return st;
+  HIP_TRY(orb_k_grid_build(f.keys.as<orb_keypoint_t>(), f.n.as<int32_t>(), std::max(n, 1),
+                           P.minX, P.minY, P.invW, P.invH, f.cells(), f.cellidx(), 1, s));
   return ORB_OK;
-}
-
-static int32_t* pp_cells(orb_matcher_t* m, int slot) { return m->sx[slot + 3].as<int32_t>(); }
-static int32_t* pp_cellidx(orb_matcher_t* m, int slot) {
-  return m->sx[slot + 3].as<int32_t>() + ORB_GRID_COLS * ORB_GRID_ROWS + 1;
 }
 
 // Per-point matching of n_mp map points into the frame at `slot`; claiming
 // modes replay the first-come order into kp_match (host in/out, nkeys).
-static orb_status_t pp_run(orb_matcher_t* m, int mode, const PPParamsHost& P, int slot,
+static orb_status_t pp_run(orb_matcher_t* m, int mode, const PPParams& P, int slot,
                            const orb_frame_t* K, const uint8_t* kpLocked, int n_mp,
                            const orb_map_point_t* mps, const uint8_t* valid,
                            const uint8_t* skip, const uint8_t* mpDesc, const float* mpAngle,
@@ -2742,43 +2516,47 @@ static orb_status_t pp_run(orb_matcher_t* m, int mode, const PPParamsHost& P, in
                            hipStream_t s, int32_t* best_dev = nullptr) {
   orb_status_t st;
   const bool claims = mode <= 1;
+  const PPFrame f(m, slot);
+  DevBuf* b = m->sx;
   if (n_mp > 0 && (!mps || !mpDesc)) return ORB_EINVAL;
-  if ((st = upload(m->sx[8], mps, (size_t)n_mp * sizeof(orb_map_point_t), s))) return st;
-  if ((st = upload(m->sx[9], mpDesc, (size_t)n_mp * 32, s))) return st;
-  if (valid && (st = upload(m->sx[10], valid, (size_t)n_mp, s))) return st;
-  if (skip && (st = upload(m->sx[11], skip, (size_t)n_mp, s))) return st;
-  if (mpAngle && (st = upload(m->sx[12], mpAngle, (size_t)n_mp * 4, s))) return st;
-  if (K->u_right && (st = upload(m->sx[13], K->u_right, (size_t)K->n * 4, s))) return st;
-  if ((st = m->sx[14].ensure((size_t)std::max(n_mp, 1) * orb_k_pp_rec_size()))) return st;
-  if ((st = m->sx[15].ensure((size_t)std::max(n_mp, 1) * 16))) return st;   // topk
-  if ((st = m->sx[16].ensure((size_t)std::max(n_mp, 1) * 4))) return st;    // ncand
+  if ((st = upload(b[PP_MPS], mps, (size_t)n_mp * sizeof(orb_map_point_t), s))) return st;
+  if ((st = upload(b[PP_MPDESC], mpDesc, (size_t)n_mp * 32, s))) return st;
+  if (valid && (st = upload(b[PP_VALID], valid, (size_t)n_mp, s))) return st;
+  if (skip && (st = upload(b[PP_SKIP], skip, (size_t)n_mp, s))) return st;
+  if (mpAngle && (st = upload(b[PP_ANGLE], mpAngle, (size_t)n_mp * 4, s))) return st;
+  if (K->u_right && (st = upload(b[PP_URIGHT], K->u_right, (size_t)K->n * 4, s))) return st;
+  if ((st = b[PP_RECS].ensure((size_t)std::max(n_mp, 1) * sizeof(PPRec)))) return st;
+  if ((st = b[PP_TOPK].ensure((size_t)std::max(n_mp, 1) * 16))) return st;
+  if ((st = b[PP_NCAND].ensure((size_t)std::max(n_mp, 1) * 4))) return st;
   int32_t* best = best_dev;
   if (!best) {
-    if ((st = m->sx[17].ensure((size_t)std::max(n_mp, 1) * 4))) return st;
-    best = m->sx[17].as<int32_t>();
+    if ((st = b[PP_BEST].ensure((size_t)std::max(n_mp, 1) * 4))) return st;
+    best = b[PP_BEST].as<int32_t>();
   }
-  HIP_TRY(orb_k_pp_match(mode, m->sx[8].as<orb_map_point_t>(),
-                         valid ? m->sx[10].as<uint8_t>() : nullptr,
-                         skip ? m->sx[11].as<uint8_t>() : nullptr, m->sx[9].as<uint8_t>(), n_mp,
-                         m->sx[slot].as<orb_keypoint_t>(), m->sx[slot + 1].as<uint8_t>(),
-                         K->u_right ? m->sx[13].as<float>() : nullptr, pp_cells(m, slot),
-                         pp_cellidx(m, slot), &P, m->sx[14].p, best, m->sx[15].as<uint32_t>(),
-                         m->sx[16].as<int32_t>(), s));
+  HIP_TRY(orb_k_pp_match(mode, b[PP_MPS].as<orb_map_point_t>(),
+                         valid ? b[PP_VALID].as<uint8_t>() : nullptr,
+                         skip ? b[PP_SKIP].as<uint8_t>() : nullptr,
+                         b[PP_MPDESC].as<uint8_t>(), n_mp, f.keys.as<orb_keypoint_t>(),
+                         f.desc.as<uint8_t>(),
+                         K->u_right ? b[PP_URIGHT].as<float>() : nullptr, f.cells(),
+                         f.cellidx(), &P, b[PP_RECS].as<PPRec>(), best, b[PP_TOPK].as<uint32_t>(),
+                         b[PP_NCAND].as<int32_t>(), s));
   if (claims) {
     const size_t lds = orb_k_pp_resolve_lds(K->n, n_mp);
     if (lds > 160 * 1024) return ORB_ECAPACITY;
-    if (kpLocked && (st = upload(m->sx[18], kpLocked, (size_t)K->n, s))) return st;
-    if ((st = upload(m->sx[19], kp_match_host, (size_t)K->n * 4, s))) return st;
-    if ((st = m->sx[20].ensure(16))) return st;
-    HIP_TRY(orb_k_pp_resolve(m->sx[slot].as<orb_keypoint_t>(), m->sx[slot + 1].as<uint8_t>(),
-                             K->n, kpLocked ? m->sx[18].as<uint8_t>() : nullptr,
-                             m->sx[9].as<uint8_t>(), mpAngle ? m->sx[12].as<float>() : nullptr,
-                             n_mp, pp_cells(m, slot), pp_cellidx(m, slot), &P, m->sx[14].p,
-                             m->sx[15].as<uint32_t>(), m->sx[16].as<int32_t>(),
-                             m->sx[19].as<int32_t>(), m->sx[20].as<int32_t>(), s));
-    HIP_TRY(hipMemcpyAsync(kp_match_host, m->sx[19].p, (size_t)K->n * 4, hipMemcpyDeviceToHost,
+    if (kpLocked && (st = upload(b[PP_LOCKED], kpLocked, (size_t)K->n, s))) return st;
+    if ((st = upload(b[PP_KPMATCH], kp_match_host, (size_t)K->n * 4, s))) return st;
+    if ((st = b[PP_COUNT].ensure(16))) return st;
+    HIP_TRY(orb_k_pp_resolve(f.keys.as<orb_keypoint_t>(), f.desc.as<uint8_t>(), K->n,
+                             kpLocked ? b[PP_LOCKED].as<uint8_t>() : nullptr,
+                             b[PP_MPDESC].as<uint8_t>(),
+                             mpAngle ? b[PP_ANGLE].as<float>() : nullptr, n_mp, f.cells(),
+                             f.cellidx(), &P, b[PP_RECS].as<PPRec>(),
+                             b[PP_TOPK].as<uint32_t>(), b[PP_NCAND].as<int32_t>(),
+                             b[PP_KPMATCH].as<int32_t>(), b[PP_COUNT].as<int32_t>(), s));
+    HIP_TRY(hipMemcpyAsync(kp_match_host, b[PP_KPMATCH].p, (size_t)K->n * 4, hipMemcpyDeviceToHost,
                            s));
-    HIP_TRY(hipMemcpyAsync(count_host, m->sx[20].p, 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(count_host, b[PP_COUNT].p, 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(stream_wait(s));
   } else if (best_host) {
     HIP_TRY(hipMemcpyAsync(best_host, best, (size_t)n_mp * 4, hipMemcpyDeviceToHost, s));
@@ -2800,7 +2578,7 @@ orb_status_t orb_search_by_projection_reloc(orb_matcher_t* m, const orb_frame_t*
   if (!m || !frame || !pose || !nmatches || n_mp < 0 || frame->n < 0 ||
       (frame->n > 0 && !kp_match) || (n_mp > 0 && check_orientation && !kf_angle))
     return ORB_EINVAL;
-  PPParamsHost P;
+  PPParams P;
   orb_status_t st = pp_base(P, frame, cam, log_scale_factor, th, orb_dist);
   if (st) return st;
   memcpy(P.R, pose->rcw, sizeof(P.R));
@@ -2815,8 +2593,8 @@ orb_status_t orb_search_by_projection_reloc(orb_matcher_t* m, const orb_frame_t*
   hipStream_t s = m->stream;
   CallOrder order(m->evLast, &m->lastStream, s);
   if (order.status) return order.status;
-  if ((st = pp_frame(m, frame, P, 0, s))) return st;
-  return pp_run(m, 0, P, 0, frame, kp_locked, n_mp, mps, nullptr, nullptr, mp_desc,
+  if ((st = pp_frame(m, frame, P, PP_FRAME0, s))) return st;
+  return pp_run(m, 0, P, PP_FRAME0, frame, kp_locked, n_mp, mps, nullptr, nullptr, mp_desc,
                 check_orientation ? kf_angle : nullptr, nullptr, kp_match, nmatches, s);
 }
 
@@ -2827,7 +2605,7 @@ orb_status_t orb_search_by_projection_sim3(orb_matcher_t* m, const orb_frame_t* 
                                            float th, int32_t* kp_matched, int32_t* nmatches) {
   if (!m || !kf || !scw || !nmatches || n_mp < 0 || kf->n < 0 || (kf->n > 0 && !kp_matched))
     return ORB_EINVAL;
-  PPParamsHost P;
+  PPParams P;
   orb_status_t st = pp_base(P, kf, cam, log_scale_factor, th, 50);
   if (st) return st;
   sim3_normalise(scw, P.R, P.t, P.Ow);
@@ -2838,9 +2616,9 @@ orb_status_t orb_search_by_projection_sim3(orb_matcher_t* m, const orb_frame_t* 
   hipStream_t s = m->stream;
   CallOrder order(m->evLast, &m->lastStream, s);
   if (order.status) return order.status;
-  if ((st = pp_frame(m, kf, P, 0, s))) return st;
-  return pp_run(m, 1, P, 0, kf, nullptr, n_mp, mps, nullptr, nullptr, mp_desc, nullptr, nullptr,
-                kp_matched, nmatches, s);
+  if ((st = pp_frame(m, kf, P, PP_FRAME0, s))) return st;
+  return pp_run(m, 1, P, PP_FRAME0, kf, nullptr, n_mp, mps, nullptr, nullptr, mp_desc, nullptr,
+                nullptr, kp_matched, nmatches, s);
 }
 
 orb_status_t orb_fuse(orb_matcher_t* m, const orb_frame_t* kf, const float* inv_level_sigma2,
@@ -2850,7 +2628,7 @@ orb_status_t orb_fuse(orb_matcher_t* m, const orb_frame_t* kf, const float* inv_
   if (!m || !kf || !pose || !inv_level_sigma2 || !n_fuse || n_mp < 0 || kf->n < 0 ||
       (n_mp > 0 && !fuse_idx))
     return ORB_EINVAL;
-  PPParamsHost P;
+  PPParams P;
   orb_status_t st = pp_base(P, kf, cam, log_scale_factor, th, 50);
   if (st) return st;
   memcpy(P.R, pose->rcw, sizeof(P.R));
@@ -2865,8 +2643,8 @@ orb_status_t orb_fuse(orb_matcher_t* m, const orb_frame_t* kf, const float* inv_
   hipStream_t s = m->stream;
   CallOrder order(m->evLast, &m->lastStream, s);
   if (order.status) return order.status;
-  if ((st = pp_frame(m, kf, P, 0, s))) return st;
-  return pp_run(m, 2, P, 0, kf, nullptr, n_mp, mps, nullptr, nullptr, mp_desc, nullptr,
+  if ((st = pp_frame(m, kf, P, PP_FRAME0, s))) return st;
+  return pp_run(m, 2, P, PP_FRAME0, kf, nullptr, n_mp, mps, nullptr, nullptr, mp_desc, nullptr,
                 fuse_idx, nullptr, n_fuse, s);
 }
 
@@ -2876,7 +2654,7 @@ orb_status_t orb_fuse_sim3(orb_matcher_t* m, const orb_frame_t* kf, const float*
                            int32_t* fuse_idx, int32_t* n_fuse) {
   if (!m || !kf || !scw || !n_fuse || n_mp < 0 || kf->n < 0 || (n_mp > 0 && !fuse_idx))
     return ORB_EINVAL;
-  PPParamsHost P;
+  PPParams P;
   orb_status_t st = pp_base(P, kf, cam, log_scale_factor, th, 50);
   if (st) return st;
   sim3_normalise(scw, P.R, P.t, P.Ow);
@@ -2888,8 +2666,8 @@ orb_status_t orb_fuse_sim3(orb_matcher_t* m, const orb_frame_t* kf, const float*
   hipStream_t s = m->stream;
   CallOrder order(m->evLast, &m->lastStream, s);
   if (order.status) return order.status;
-  if ((st = pp_frame(m, kf, P, 0, s))) return st;
-  return pp_run(m, 3, P, 0, kf, nullptr, n_mp, mps, nullptr, nullptr, mp_desc, nullptr,
+  if ((st = pp_frame(m, kf, P, PP_FRAME0, s))) return st;
+  return pp_run(m, 3, P, PP_FRAME0, kf, nullptr, n_mp, mps, nullptr, nullptr, mp_desc, nullptr,
                 fuse_idx, nullptr, n_fuse, s);
 }
 
@@ -2907,7 +2685,7 @@ orb_status_t orb_search_by_sim3(orb_matcher_t* m, const orb_frame_t* kf1, const 
       kf1->n < 0 || kf2->n < 0 || (kf1->n > 0 && (!mps1 || !valid1 || !mp_desc1 || !match12)) ||
       (kf2->n > 0 && (!mps2 || !valid2 || !mp_desc2)))
     return ORB_EINVAL;
-  PPParamsHost P1, P2;  // P1: KF1 points into KF2, P2: KF2 points into KF1
+  PPParams P1, P2;  // P1: KF1 points into KF2, P2: KF2 points into KF1
   orb_status_t st;
   if ((st = pp_base(P1, kf2, cam, log_scale_factor, th, 100))) return st;
   if ((st = pp_base(P2, kf1, cam, log_scale_factor, th, 100))) return st;
@@ -2929,22 +2707,22 @@ orb_status_t orb_search_by_sim3(orb_matcher_t* m, const orb_frame_t* kf1, const 
   hipStream_t s = m->stream;
   CallOrder order(m->evLast, &m->lastStream, s);
   if (order.status) return order.status;
-  if ((st = pp_frame(m, kf2, P1, 0, s))) return st;
-  if ((st = pp_frame(m, kf1, P2, 4, s))) return st;
-  if ((st = m->sx[21].ensure((size_t)kf1->n * 4))) return st;
-  if ((st = m->sx[22].ensure((size_t)kf2->n * 4))) return st;
-  if ((st = m->sx[23].ensure((size_t)kf1->n * 4 + 16))) return st;
+  if ((st = pp_frame(m, kf2, P1, PP_FRAME0, s))) return st;
+  if ((st = pp_frame(m, kf1, P2, PP_FRAME1, s))) return st;
+  if ((st = m->sx[PP_BEST12].ensure((size_t)kf1->n * 4))) return st;
+  if ((st = m->sx[PP_BEST21].ensure((size_t)kf2->n * 4))) return st;
+  if ((st = m->sx[PP_MUTUAL].ensure((size_t)kf1->n * 4 + 16))) return st;
   // direction 1 runs to completion before its point buffers are reused
-  if ((st = pp_run(m, 4, P1, 0, kf2, nullptr, kf1->n, mps1, valid1, already1, mp_desc1, nullptr,
-                   nullptr, nullptr, nullptr, s, m->sx[21].as<int32_t>())))
+  if ((st = pp_run(m, 4, P1, PP_FRAME0, kf2, nullptr, kf1->n, mps1, valid1, already1, mp_desc1,
+                   nullptr, nullptr, nullptr, nullptr, s, m->sx[PP_BEST12].as<int32_t>())))
     return st;
   HIP_TRY(stream_wait(s));
-  if ((st = pp_run(m, 4, P2, 4, kf1, nullptr, kf2->n, mps2, valid2, already2, mp_desc2, nullptr,
-                   nullptr, nullptr, nullptr, s, m->sx[22].as<int32_t>())))
+  if ((st = pp_run(m, 4, P2, PP_FRAME1, kf1, nullptr, kf2->n, mps2, valid2, already2, mp_desc2,
+                   nullptr, nullptr, nullptr, nullptr, s, m->sx[PP_BEST21].as<int32_t>())))
     return st;
-  int32_t* out = m->sx[23].as<int32_t>();
-  HIP_TRY(orb_k_sim3_mutual(m->sx[21].as<int32_t>(), kf1->n, m->sx[22].as<int32_t>(), out,
-                            out + kf1->n, s));
+  int32_t* out = m->sx[PP_MUTUAL].as<int32_t>();
+  HIP_TRY(orb_k_sim3_mutual(m->sx[PP_BEST12].as<int32_t>(), kf1->n,
+                            m->sx[PP_BEST21].as<int32_t>(), out, out + kf1->n, s));
   HIP_TRY(hipMemcpyAsync(match12, out, (size_t)kf1->n * 4, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipMemcpyAsync(nfound, out + kf1->n, 4, hipMemcpyDeviceToHost, s));
   HIP_TRY(stream_wait(s));
@@ -2976,33 +2754,35 @@ orb_status_t orb_match_bow_kf(orb_matcher_t* m, int n1, const uint8_t* desc1,
   if (order.status) return order.status;
   orb_status_t st;
   DevBuf* b = m->sx;
-  if ((st = upload(b[0], desc1, (size_t)n1 * 32, s))) return st;
-  if ((st = upload(b[1], angle1, (size_t)n1 * 4, s))) return st;
-  if ((st = upload(b[2], mp1, (size_t)n1 * 4, s))) return st;
-  if (mp1_bad && (st = upload(b[3], mp1_bad, (size_t)n1, s))) return st;
-  if ((st = upload(b[4], node_ids1, (size_t)nodes1 * 4, s))) return st;
-  if ((st = upload(b[5], offs1, (size_t)(nodes1 + 1) * 4, s))) return st;
-  if ((st = upload(b[6], feats1, (size_t)nF1 * 4, s))) return st;
-  if ((st = upload(b[7], desc2, (size_t)n2 * 32, s))) return st;
-  if ((st = upload(b[8], angle2, (size_t)n2 * 4, s))) return st;
-  if ((st = upload(b[9], mp2, (size_t)n2 * 4, s))) return st;
-  if (mp2_bad && (st = upload(b[10], mp2_bad, (size_t)n2, s))) return st;
-  if ((st = upload(b[11], node_ids2, (size_t)nodes2 * 4, s))) return st;
-  if ((st = upload(b[12], offs2, (size_t)(nodes2 + 1) * 4, s))) return st;
-  if ((st = upload(b[13], feats2, (size_t)nF2 * 4, s))) return st;
-  if ((st = b[14].ensure((size_t)n1 * 4))) return st;
-  if ((st = b[15].ensure((size_t)std::max(nF1, 1) * 4))) return st;
-  if ((st = b[16].ensure(16))) return st;
-  HIP_TRY(hipMemsetAsync(b[14].p, 0xFF, (size_t)n1 * 4, s));
-  HIP_TRY(orb_k_bow(b[0].as<uint8_t>(), b[1].as<float>(), b[2].as<int32_t>(),
-                    mp1_bad ? b[3].as<uint8_t>() : nullptr, nodes1, b[4].as<uint32_t>(),
-                    b[5].as<int32_t>(), b[6].as<uint32_t>(), nF1, b[7].as<uint8_t>(),
-                    b[8].as<float>(), nodes2, b[11].as<uint32_t>(), b[12].as<int32_t>(),
-                    b[13].as<uint32_t>(), n2, b[9].as<int32_t>(),
-                    mp2_bad ? b[10].as<uint8_t>() : nullptr, 49, nnratio, check_orientation,
-                    b[14].as<int32_t>(), b[15].as<int32_t>(), b[16].as<int32_t>(), s));
-  HIP_TRY(hipMemcpyAsync(match12, b[14].p, (size_t)n1 * 4, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipMemcpyAsync(nmatches, b[16].p, 4, hipMemcpyDeviceToHost, s));
+  if ((st = upload(b[BW_DESC1], desc1, (size_t)n1 * 32, s))) return st;
+  if ((st = upload(b[BW_ANGLE1], angle1, (size_t)n1 * 4, s))) return st;
+  if ((st = upload(b[BW_MP1], mp1, (size_t)n1 * 4, s))) return st;
+  if (mp1_bad && (st = upload(b[BW_BAD1], mp1_bad, (size_t)n1, s))) return st;
+  if ((st = upload(b[BW_IDS1], node_ids1, (size_t)nodes1 * 4, s))) return st;
+  if ((st = upload(b[BW_OFFS1], offs1, (size_t)(nodes1 + 1) * 4, s))) return st;
+  if ((st = upload(b[BW_FEATS1], feats1, (size_t)nF1 * 4, s))) return st;
+  if ((st = upload(b[BW_DESC2], desc2, (size_t)n2 * 32, s))) return st;
+  if ((st = upload(b[BW_ANGLE2], angle2, (size_t)n2 * 4, s))) return st;
+  if ((st = upload(b[BW_MP2], mp2, (size_t)n2 * 4, s))) return st;
+  if (mp2_bad && (st = upload(b[BW_BAD2], mp2_bad, (size_t)n2, s))) return st;
+  if ((st = upload(b[BW_IDS2], node_ids2, (size_t)nodes2 * 4, s))) return st;
+  if ((st = upload(b[BW_OFFS2], offs2, (size_t)(nodes2 + 1) * 4, s))) return st;
+  if ((st = upload(b[BW_FEATS2], feats2, (size_t)nF2 * 4, s))) return st;
+  if ((st = b[BW_MATCH].ensure((size_t)n1 * 4))) return st;
+  if ((st = b[BW_ACC].ensure((size_t)std::max(nF1, 1) * 4))) return st;
+  if ((st = b[BW_COUNT].ensure(16))) return st;
+  HIP_TRY(hipMemsetAsync(b[BW_MATCH].p, 0xFF, (size_t)n1 * 4, s));
+  HIP_TRY(orb_k_bow(b[BW_DESC1].as<uint8_t>(), b[BW_ANGLE1].as<float>(), b[BW_MP1].as<int32_t>(),
+                    mp1_bad ? b[BW_BAD1].as<uint8_t>() : nullptr, nodes1,
+                    b[BW_IDS1].as<uint32_t>(), b[BW_OFFS1].as<int32_t>(),
+                    b[BW_FEATS1].as<uint32_t>(), nF1, b[BW_DESC2].as<uint8_t>(),
+                    b[BW_ANGLE2].as<float>(), nodes2, b[BW_IDS2].as<uint32_t>(),
+                    b[BW_OFFS2].as<int32_t>(), b[BW_FEATS2].as<uint32_t>(), n2,
+                    b[BW_MP2].as<int32_t>(), mp2_bad ? b[BW_BAD2].as<uint8_t>() : nullptr, 49,
+                    nnratio, check_orientation, b[BW_MATCH].as<int32_t>(),
+                    b[BW_ACC].as<int32_t>(), b[BW_COUNT].as<int32_t>(), s));
+  HIP_TRY(hipMemcpyAsync(match12, b[BW_MATCH].p, (size_t)n1 * 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(nmatches, b[BW_COUNT].p, 4, hipMemcpyDeviceToHost, s));
   HIP_TRY(stream_wait(s));
   return ORB_OK;
 }
@@ -3021,7 +2801,7 @@ orb_status_t orb_search_for_triangulation(
       (kf2->n > 0 && (!kf2->keys || !kf2->descriptors || !has_mp2)) ||
       (nodes1 > 0 && (!node_ids1 || !offs1)) || (nodes2 > 0 && (!node_ids2 || !offs2)))
     return ORB_EINVAL;
-  TriParamsHost T;
+  TriParams T;
   memset(&T, 0, sizeof(T));
   memcpy(T.F, f12, sizeof(T.F));
   float C2[3];
@@ -3047,33 +2827,34 @@ orb_status_t orb_search_for_triangulation(
   orb_status_t st;
   DevBuf* b = m->sx;
   const int n1 = kf1->n, n2 = kf2->n;
-  if ((st = upload(b[0], kf1->keys, (size_t)n1 * sizeof(orb_keypoint_t), s))) return st;
-  if ((st = upload(b[1], kf1->descriptors, (size_t)n1 * 32, s))) return st;
-  if (kf1->u_right && (st = upload(b[2], kf1->u_right, (size_t)n1 * 4, s))) return st;
-  if ((st = upload(b[3], has_mp1, (size_t)n1, s))) return st;
-  if ((st = upload(b[4], node_ids1, (size_t)nodes1 * 4, s))) return st;
-  if ((st = upload(b[5], offs1, (size_t)(nodes1 + 1) * 4, s))) return st;
-  if ((st = upload(b[6], feats1, (size_t)nF1 * 4, s))) return st;
-  if ((st = upload(b[7], kf2->keys, (size_t)n2 * sizeof(orb_keypoint_t), s))) return st;
-  if ((st = upload(b[8], kf2->descriptors, (size_t)n2 * 32, s))) return st;
-  if (kf2->u_right && (st = upload(b[9], kf2->u_right, (size_t)n2 * 4, s))) return st;
-  if ((st = upload(b[10], has_mp2, (size_t)n2, s))) return st;
-  if ((st = upload(b[11], node_ids2, (size_t)nodes2 * 4, s))) return st;
-  if ((st = upload(b[12], offs2, (size_t)(nodes2 + 1) * 4, s))) return st;
-  if ((st = upload(b[13], feats2, (size_t)nF2 * 4, s))) return st;
-  if ((st = b[14].ensure((size_t)n1 * 4))) return st;
-  if ((st = b[15].ensure((size_t)std::max(nF1, 1) * 4))) return st;
-  if ((st = b[16].ensure(16))) return st;
-  HIP_TRY(hipMemsetAsync(b[14].p, 0xFF, (size_t)n1 * 4, s));
+  if ((st = upload(b[TR_KEYS1], kf1->keys, (size_t)n1 * sizeof(orb_keypoint_t), s))) return st;
+  if ((st = upload(b[TR_DESC1], kf1->descriptors, (size_t)n1 * 32, s))) return st;
+  if (kf1->u_right && (st = upload(b[TR_UR1], kf1->u_right, (size_t)n1 * 4, s))) return st;
+  if ((st = upload(b[TR_HASMP1], has_mp1, (size_t)n1, s))) return st;
+  if ((st = upload(b[TR_IDS1], node_ids1, (size_t)nodes1 * 4, s))) return st;
+  if ((st = upload(b[TR_OFFS1], offs1, (size_t)(nodes1 + 1) * 4, s))) return st;
+  if ((st = upload(b[TR_FEATS1], feats1, (size_t)nF1 * 4, s))) return st;
+  if ((st = upload(b[TR_KEYS2], kf2->keys, (size_t)n2 * sizeof(orb_keypoint_t), s))) return st;
+  if ((st = upload(b[TR_DESC2], kf2->descriptors, (size_t)n2 * 32, s))) return st;
+  if (kf2->u_right && (st = upload(b[TR_UR2], kf2->u_right, (size_t)n2 * 4, s))) return st;
+  if ((st = upload(b[TR_HASMP2], has_mp2, (size_t)n2, s))) return st;
+  if ((st = upload(b[TR_IDS2], node_ids2, (size_t)nodes2 * 4, s))) return st;
+  if ((st = upload(b[TR_OFFS2], offs2, (size_t)(nodes2 + 1) * 4, s))) return st;
+  if ((st = upload(b[TR_FEATS2], feats2, (size_t)nF2 * 4, s))) return st;
+  if ((st = b[TR_MATCH].ensure((size_t)n1 * 4))) return st;
+  if ((st = b[TR_ACC].ensure((size_t)std::max(nF1, 1) * 4))) return st;
+  if ((st = b[TR_COUNT].ensure(16))) return st;
+  HIP_TRY(hipMemsetAsync(b[TR_MATCH].p, 0xFF, (size_t)n1 * 4, s));
   HIP_TRY(orb_k_triangulation(
-      b[0].as<orb_keypoint_t>(), b[1].as<uint8_t>(), kf1->u_right ? b[2].as<float>() : nullptr,
-      b[3].as<uint8_t>(), nodes1, b[4].as<uint32_t>(), b[5].as<int32_t>(), b[6].as<uint32_t>(),
-      nF1, b[7].as<orb_keypoint_t>(), b[8].as<uint8_t>(),
-      kf2->u_right ? b[9].as<float>() : nullptr, b[10].as<uint8_t>(), nodes2,
-      b[11].as<uint32_t>(), b[12].as<int32_t>(), b[13].as<uint32_t>(), &T, b[14].as<int32_t>(),
-      b[15].as<int32_t>(), b[16].as<int32_t>(), s));
-  HIP_TRY(hipMemcpyAsync(match12, b[14].p, (size_t)n1 * 4, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipMemcpyAsync(nmatches, b[16].p, 4, hipMemcpyDeviceToHost, s));
+      b[TR_KEYS1].as<orb_keypoint_t>(), b[TR_DESC1].as<uint8_t>(),
+      kf1->u_right ? b[TR_UR1].as<float>() : nullptr, b[TR_HASMP1].as<uint8_t>(), nodes1,
+      b[TR_IDS1].as<uint32_t>(), b[TR_OFFS1].as<int32_t>(), b[TR_FEATS1].as<uint32_t>(), nF1,
+      b[TR_KEYS2].as<orb_keypoint_t>(), b[TR_DESC2].as<uint8_t>(),
+      kf2->u_right ? b[TR_UR2].as<float>() : nullptr, b[TR_HASMP2].as<uint8_t>(), nodes2,
+      b[TR_IDS2].as<uint32_t>(), b[TR_OFFS2].as<int32_t>(), b[TR_FEATS2].as<uint32_t>(), &T,
+      b[TR_MATCH].as<int32_t>(), b[TR_ACC].as<int32_t>(), b[TR_COUNT].as<int32_t>(), s));
+  HIP_TRY(hipMemcpyAsync(match12, b[TR_MATCH].p, (size_t)n1 * 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(nmatches, b[TR_COUNT].p, 4, hipMemcpyDeviceToHost, s));
   HIP_TRY(stream_wait(s));
   return ORB_OK;
 }
@@ -3083,8 +2864,9 @@ orb_status_t orb_search_for_triangulation(
 // (Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:1362-1448) and its transform
 // (:1128-1283), the producer of Frame/KeyFrame::mBowVec and mFeatVec
 // (src/Frame.cc:439-449, src/KeyFrame.cc:60-71).  The tree lives on the
-// device, renumbered breadth-first (vocab_kernels.hip).
-struct orb_vocabulary {
+// device, renumbered breadth-first (vocab_kernels.hip).  (Hidden: its implicit
+// destructor, which frees the buffers, is no export of the library.)
+struct __attribute__((visibility("hidden"))) orb_vocabulary {
   int device = 0;
   hipStream_t stream = nullptr;
   std::mutex mu;
@@ -3114,8 +2896,7 @@ static orb_status_t vocab_build(orb_vocabulary* V, int n_nodes, const int32_t* p
     if (leaf[i]) wordOf[i] = (uint32_t)nw++;
   // breadth-first renumbering: children of the node at position p occupy
   // consecutive positions, in child order
-  struct Info { int32_t first, count; };
-  std::vector<Info> info(n_nodes);
+  std::vector<VocNodeInfo> info(n_nodes);
   std::vector<int32_t> orig(n_nodes);
   std::vector<uint8_t> ddesc((size_t)n_nodes * 32);
   std::vector<uint32_t> dword(n_nodes);
@@ -3136,7 +2917,7 @@ static orb_status_t vocab_build(orb_vocabulary* V, int n_nodes, const int32_t* p
   V->nWords = nw;
   hipStream_t s = V->stream;
   orb_status_t st;
-  if ((st = upload(V->dInfo, info.data(), info.size() * sizeof(Info), s))) return st;
+  if ((st = upload(V->dInfo, info.data(), info.size() * sizeof(VocNodeInfo), s))) return st;
   if ((st = upload(V->dDesc, ddesc.data(), ddesc.size(), s))) return st;
   if ((st = upload(V->dWord, dword.data(), dword.size() * 4, s))) return st;
   if ((st = upload(V->dWeight, dweight.data(), dweight.size() * 8, s))) return st;
@@ -3253,13 +3034,9 @@ void orb_vocabulary_destroy(orb_vocabulary_t* V) {
   if (!V) return;
   hipSetDevice(V->device);
   hipStreamSynchronize(V->stream);
-  DevBuf* bufs[] = {&V->dInfo, &V->dDesc, &V->dWord, &V->dWeight, &V->dOrig, &V->dIn,
-                    &V->dCounts, &V->dFWord, &V->dFWeight, &V->dFNode, &V->dBowW, &V->dBowV,
-                    &V->dNW, &V->dFvN, &V->dFvO, &V->dFvF, &V->dNFv};
-  for (DevBuf* b : bufs) b->release();
-  for (DevBuf& b : V->dScore) b.release();
-  hipStreamDestroy(V->stream);
-  delete V;
+  const hipStream_t stream = V->stream;
+  delete V;  // frees every buffer (DevBuf)
+  hipStreamDestroy(stream);
 }
 
 orb_status_t orb_vocabulary_info(const orb_vocabulary_t* V, int32_t* info6) {
@@ -3286,7 +3063,7 @@ static orb_status_t vocab_launch(orb_vocabulary* V, int n_frames, const int32_t*
       HIP_TRY(hipMemsetAsync(fvo + (size_t)f * (stride + 1), 0, 4, s));
     return ORB_OK;
   }
-  HIP_TRY(orb_k_voc_descend(V->dInfo.p, V->dDesc.p, V->dWord.as<uint32_t>(),
+  HIP_TRY(orb_k_voc_descend(V->dInfo.as<VocNodeInfo>(), V->dDesc.p, V->dWord.as<uint32_t>(),
                             V->dWeight.as<double>(), V->dOrig.as<uint32_t>(), V->L - levelsup,
                             d_desc, d_counts, n_single, stride, n_frames, fword, fweight, fnode,
                             s));
@@ -3430,42 +3207,6 @@ orb_status_t orb_vocabulary_score_batch(orb_vocabulary_t* V, int n_pairs, const 
 // is the add sequence number the list order needs (placerec_kernels.hip).
 // The host keeps what resolves ids (id -> slot, who names whom as a
 // neighbour); BowVectors, covisibility slots and scores stay on the device.
-#define KFDB_NEIGH 10
-
-struct KfSlotHost {  // PrSlot
-  long long off;
-  int32_t len;
-  int32_t live;
-};
-
-struct KfQueryArgs {  // PrQueryArgs
-  int type, loop;
-  float minScore;
-  int nSlots, nq, nConnected;
-  const void* slots;
-  const uint32_t* words;
-  const double* values;
-  const int32_t* neigh;
-  const long long* ids;
-  float* stored;
-  const uint32_t* qWords;
-  const double* qValues;
-  const int32_t* connSlots;
-  uint8_t* connected;
-  int32_t* common;
-  uint32_t* first;
-  int32_t* firstPos;
-  unsigned long long* keys;
-  uint32_t* list;
-  int32_t* hdr;
-  uint8_t* scored;
-  float* acc;
-  uint32_t* best;
-  uint8_t* valid;
-  long long* out;
-  int stage;
-};
-
 struct orb_kf_database {
   orb_vocabulary* voc = nullptr;
   int device = 0;
@@ -3474,7 +3215,7 @@ struct orb_kf_database {
   // host side of the slot table
   std::vector<int64_t> slotId;
   std::vector<uint8_t> slotLive;
-  std::vector<std::array<int64_t, KFDB_NEIGH>> neighIds;
+  std::vector<std::array<int64_t, PR_NEIGH>> neighIds;
   std::vector<int> neighN;
   std::unordered_map<int64_t, int> slotOf;  // live keyframes
   // neighbour id -> (slot, position) of every live keyframe that names it
@@ -3489,7 +3230,7 @@ struct orb_kf_database {
   uint64_t lastId[2] = {0, 0};
   int lastKind = -1, lastSlots = 0, lastN = 0;
   bool argsValid = false;
-  KfQueryArgs args;
+  PrQueryArgs args;
 };
 
 // Grows b to hold `need` bytes, keeping its first `used` bytes.
@@ -3529,7 +3270,7 @@ static orb_status_t kfdb_patch_neighbours(orb_kf_database* D, int64_t id, const 
                                           hipStream_t s) {
   auto range = D->namedBy.equal_range(id);
   for (auto it = range.first; it != range.second; ++it) {
-    const size_t at = (size_t)it->second.first * KFDB_NEIGH + it->second.second;
+    const size_t at = (size_t)it->second.first * PR_NEIGH + it->second.second;
     HIP_TRY(hipMemcpyAsync(D->dNeigh.as<int32_t>() + at, slot, 4, hipMemcpyHostToDevice, s));
   }
   return ORB_OK;
@@ -3539,9 +3280,6 @@ orb_status_t orb_kf_database_create(orb_vocabulary_t* V, orb_kf_database_t** out
   if (!out) return ORB_EINVAL;
   *out = nullptr;
   if (!V || V->scoring == ORB_VOC_KL) return ORB_EINVAL;
-  if (orb_k_db_slot_size() != sizeof(KfSlotHost) ||
-      orb_k_db_query_args_size() != sizeof(KfQueryArgs))
-    return ORB_EINVAL;
   orb_kf_database* D = new orb_kf_database();
   D->voc = V;
   D->device = V->device;
@@ -3558,13 +3296,9 @@ void orb_kf_database_destroy(orb_kf_database_t* D) {
   if (!D) return;
   hipSetDevice(D->device);
   hipStreamSynchronize(D->stream);
-  DevBuf* bufs[] = {&D->dWords, &D->dValues, &D->dSlots, &D->dNeigh, &D->dIds, &D->dStored[0],
-                    &D->dStored[1], &D->dQW, &D->dQV, &D->dConnSlots, &D->dConn, &D->dCommon,
-                    &D->dFirst, &D->dFirstPos, &D->dKeys, &D->dList, &D->dHdr, &D->dScored,
-                    &D->dAcc, &D->dBest, &D->dValid, &D->dOut};
-  for (DevBuf* b : bufs) b->release();
-  hipStreamDestroy(D->stream);
-  delete D;
+  const hipStream_t stream = D->stream;
+  delete D;  // frees every buffer (DevBuf)
+  hipStreamDestroy(stream);
 }
 
 orb_status_t orb_kf_database_clear(orb_kf_database_t* D) {
@@ -3604,14 +3338,14 @@ orb_status_t orb_kf_database_add(orb_kf_database_t* D, int64_t kf_id, int n_word
   orb_status_t st;
   if ((st = grow_keep(D->dWords, e0 * 4, e1 * 4, s)) ||
       (st = grow_keep(D->dValues, e0 * 8, e1 * 8, s)) ||
-      (st = grow_keep(D->dSlots, slot * sizeof(KfSlotHost), (slot + 1) * sizeof(KfSlotHost), s)) ||
-      (st = grow_keep(D->dNeigh, slot * KFDB_NEIGH * 4, (slot + 1) * KFDB_NEIGH * 4, s)) ||
+      (st = grow_keep(D->dSlots, slot * sizeof(PrSlot), (slot + 1) * sizeof(PrSlot), s)) ||
+      (st = grow_keep(D->dNeigh, slot * PR_NEIGH * 4, (slot + 1) * PR_NEIGH * 4, s)) ||
       (st = grow_keep(D->dIds, slot * 8, (slot + 1) * 8, s)) ||
       (st = grow_keep(D->dStored[0], slot * 4, (slot + 1) * 4, s)) ||
       (st = grow_keep(D->dStored[1], slot * 4, (slot + 1) * 4, s)))
     return st;
-  const KfSlotHost rec{(long long)e0, n_words, 1};
-  int32_t none[KFDB_NEIGH];
+  const PrSlot rec{(long long)e0, n_words, 1};
+  int32_t none[PR_NEIGH];
   for (int32_t& v : none) v = -1;
   const long long id = kf_id;
   const int32_t self = (int32_t)slot;
@@ -3621,9 +3355,9 @@ orb_status_t orb_kf_database_add(orb_kf_database_t* D, int64_t kf_id, int n_word
     HIP_TRY(hipMemcpyAsync(D->dValues.as<double>() + e0, values, (size_t)n_words * 8,
                            hipMemcpyHostToDevice, s));
   }
-  HIP_TRY(hipMemcpyAsync(D->dSlots.as<KfSlotHost>() + slot, &rec, sizeof(rec),
+  HIP_TRY(hipMemcpyAsync(D->dSlots.as<PrSlot>() + slot, &rec, sizeof(rec),
                          hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(D->dNeigh.as<int32_t>() + slot * KFDB_NEIGH, none, sizeof(none),
+  HIP_TRY(hipMemcpyAsync(D->dNeigh.as<int32_t>() + slot * PR_NEIGH, none, sizeof(none),
                          hipMemcpyHostToDevice, s));
   HIP_TRY(hipMemcpyAsync(D->dIds.as<long long>() + slot, &id, 8, hipMemcpyHostToDevice, s));
   HIP_TRY(hipMemsetAsync(D->dStored[0].as<float>() + slot, 0, 4, s));  // never scored: 0.0f
@@ -3650,7 +3384,7 @@ orb_status_t orb_kf_database_erase(orb_kf_database_t* D, int64_t kf_id) {
   hipStream_t s = D->stream;
   const int slot = it->second;
   const int32_t dead = 0, none = -1;
-  HIP_TRY(hipMemcpyAsync(&D->dSlots.as<KfSlotHost>()[slot].live, &dead, 4, hipMemcpyHostToDevice,
+  HIP_TRY(hipMemcpyAsync(&D->dSlots.as<PrSlot>()[slot].live, &dead, 4, hipMemcpyHostToDevice,
                          s));
   orb_status_t st = kfdb_patch_neighbours(D, kf_id, &none, s);
   if (st) return st;
@@ -3665,22 +3399,22 @@ orb_status_t orb_kf_database_erase(orb_kf_database_t* D, int64_t kf_id) {
 
 orb_status_t orb_kf_database_set_covisibility(orb_kf_database_t* D, int64_t kf_id, int n,
                                               const int64_t* neighbour_ids) {
-  if (!D || n < 0 || n > KFDB_NEIGH || (n > 0 && !neighbour_ids)) return ORB_EINVAL;
+  if (!D || n < 0 || n > PR_NEIGH || (n > 0 && !neighbour_ids)) return ORB_EINVAL;
   std::lock_guard<std::mutex> g(D->mu);
   auto it = D->slotOf.find(kf_id);
   if (it == D->slotOf.end()) return ORB_EINVAL;
   hipSetDevice(D->device);
   hipStream_t s = D->stream;
   const int slot = it->second;
-  int32_t resolved[KFDB_NEIGH];
-  for (int j = 0; j < KFDB_NEIGH; ++j) {
+  int32_t resolved[PR_NEIGH];
+  for (int j = 0; j < PR_NEIGH; ++j) {
     resolved[j] = -1;
     if (j < n) {
       auto f = D->slotOf.find(neighbour_ids[j]);
       if (f != D->slotOf.end()) resolved[j] = f->second;
     }
   }
-  HIP_TRY(hipMemcpyAsync(D->dNeigh.as<int32_t>() + (size_t)slot * KFDB_NEIGH, resolved,
+  HIP_TRY(hipMemcpyAsync(D->dNeigh.as<int32_t>() + (size_t)slot * PR_NEIGH, resolved,
                          sizeof(resolved), hipMemcpyHostToDevice, s));
   HIP_TRY(hipStreamSynchronize(s));
   kfdb_unname(D, slot);
@@ -3733,14 +3467,14 @@ static orb_status_t kfdb_query(orb_kf_database* D, int kind, uint64_t query_id, 
       (st = D->dAcc.ensure(N * 4)) || (st = D->dBest.ensure(N * 4)) ||
       (st = D->dValid.ensure(N)) || (st = D->dOut.ensure(N * 8)))
     return st;
-  KfQueryArgs& A = D->args;
+  PrQueryArgs& A = D->args;
   A.type = D->voc->scoring;
   A.loop = kind;
   A.minScore = min_score;
   A.nSlots = nSlots;
   A.nq = n_words;
   A.nConnected = (int)conn.size();
-  A.slots = D->dSlots.p;
+  A.slots = D->dSlots.as<PrSlot>();
   A.words = D->dWords.as<uint32_t>();
   A.values = D->dValues.as<double>();
   A.neigh = D->dNeigh.as<int32_t>();
@@ -3835,7 +3569,7 @@ orb_status_t orb_kf_database_profile(orb_kf_database_t* D, int stage, int reps, 
   hipEvent_t e0, e1;
   HIP_TRY(hipEventCreate(&e0));
   HIP_TRY(hipEventCreate(&e1));
-  KfQueryArgs A = D->args;
+  PrQueryArgs A = D->args;
   A.stage = stage;
   hipError_t e = hipEventRecord(e0, s);
   for (int i = 0; i < reps && e == hipSuccess; ++i) e = orb_k_db_query(&A, s);
@@ -3856,16 +3590,8 @@ orb_status_t orb_kf_database_profile(orb_kf_database_t* D, int stage, int reps, 
 // Frame::UndistortKeyPoints / ComputeImageBounds (src/Frame.cc:452-514); the
 // double parameter block of camera_kernels.hip (cvConvert of the CV_32F
 // matrices, ifx = 1./fx, RR = mK * I).
-struct UndistortParamsHost {
-  double fx, fy, cx, cy, ifx, ify;
-  double rr[9];
-  double k[12];
-};
-
 static orb_status_t undistort_params(const float* K, const float* dist, int n_dist,
-                                     UndistortParamsHost& P) {
-  static_assert(sizeof(UndistortParamsHost) == 27 * 8, "parameter block layout");
-  if (orb_k_undistort_params_size() != sizeof(UndistortParamsHost)) return ORB_EINVAL;
+                                     UndistortParams& P) {
   if (!K || !dist || !(n_dist == 4 || n_dist == 5 || n_dist == 8 || n_dist == 12))
     return ORB_EINVAL;
   memset(&P, 0, sizeof(P));
@@ -3880,7 +3606,7 @@ static orb_status_t undistort_params(const float* K, const float* dist, int n_di
 orb_status_t orb_undistort_points(orb_matcher_t* m, int n, const float* xy, const float* K,
                                   const float* dist, int n_dist, float* out_xy) {
   if (!m || n < 0 || (n > 0 && (!xy || !out_xy))) return ORB_EINVAL;
-  UndistortParamsHost P;
+  UndistortParams P;
   orb_status_t st = undistort_params(K, dist, n_dist, P);
   if (st) return st;
   if (n == 0) return ORB_OK;
@@ -3900,7 +3626,7 @@ orb_status_t orb_undistort_keypoints(orb_matcher_t* m, int n, const orb_keypoint
                                      const float* K, const float* dist, int n_dist,
                                      orb_keypoint_t* keys_un) {
   if (!m || n < 0 || (n > 0 && (!keys || !keys_un))) return ORB_EINVAL;
-  UndistortParamsHost P;
+  UndistortParams P;
   orb_status_t st = undistort_params(K, dist, n_dist, P);
   if (st) return st;
   if (n == 0) return ORB_OK;
@@ -3924,7 +3650,7 @@ orb_status_t orb_undistort_keypoints(orb_matcher_t* m, int n, const orb_keypoint
 orb_status_t orb_compute_image_bounds(orb_matcher_t* m, int cols, int rows, const float* K,
                                       const float* dist, int n_dist, float* bounds) {
   if (!m || !bounds || cols < 0 || rows < 0) return ORB_EINVAL;
-  UndistortParamsHost P;
+  UndistortParams P;
   orb_status_t st = undistort_params(K, dist, n_dist, P);
   if (st) return st;
   if (dist[0] == 0.0f) {  // :506-512
@@ -3949,7 +3675,7 @@ orb_status_t orb_undistort_keypoints_batch(orb_matcher_t* m, int n_frames, const
                                            const float* K, const float* dist, int n_dist,
                                            orb_keypoint_t* d_keys_un, void* stream) {
   if (!m || n_frames < 0 || stride <= 0) return ORB_EINVAL;
-  UndistortParamsHost P;
+  UndistortParams P;
   orb_status_t st = undistort_params(K, dist, n_dist, P);
   if (st) return st;
   if (n_frames == 0) return ORB_OK;

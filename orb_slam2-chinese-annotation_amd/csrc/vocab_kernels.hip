@@ -23,14 +23,10 @@
 // normalisation sum runs sequentially in word order so every double rounds
 // exactly as BowVector::normalize's loop does.
 #include "orb_device.h"
+#include "orb_kernels.h"
 
 #define VOC_GROUP 16
 #define VOC_STOP 0xFFFFFFFFu
-
-struct VocNodeInfo {
-  int32_t first;  // device position of the first child
-  int32_t count;  // number of children (0 = Node::isLeaf)
-};
 
 __global__ __launch_bounds__(256) void k_voc_descend(
     const VocNodeInfo* __restrict__ info, const uint4* __restrict__ ndesc,
@@ -230,7 +226,8 @@ __global__ __launch_bounds__(256) void k_voc_vectors(
   }
 }
 
-extern "C" hipError_t orb_k_voc_descend(const void* info, const void* ndesc, const uint32_t* nword,
+extern "C" hipError_t orb_k_voc_descend(const VocNodeInfo* info, const void* ndesc,
+                                        const uint32_t* nword,
                                         const double* nweight, const uint32_t* norig,
                                         int nidLevel, const uint8_t* desc, const int32_t* counts,
                                         int nSingle, int stride, int nFrames, uint32_t* fword,
@@ -239,7 +236,7 @@ extern "C" hipError_t orb_k_voc_descend(const void* info, const void* ndesc, con
   if (groups <= 0) return hipSuccess;
   const long long blocks = (groups + (256 / VOC_GROUP) - 1) / (256 / VOC_GROUP);
   hipLaunchKernelGGL(k_voc_descend, dim3((unsigned)blocks), dim3(256), 0, s,
-                     (const VocNodeInfo*)info, (const uint4*)ndesc, nword, nweight, norig,
+                     info, (const uint4*)ndesc, nword, nweight, norig,
                      nidLevel, desc, counts, nSingle, stride, nFrames, fword, fweight, fnode);
   return hipGetLastError();
 }
