@@ -59,6 +59,14 @@
  *   orb_undistort_points / orb_undistort_keypoints(_batch) / orb_compute_image_bounds
  *                                  cv::undistortPoints in Frame::UndistortKeyPoints
  *                                  src/Frame.cc:452-482 and ComputeImageBounds :484-514
+ *   orb_match_projection_local_batch_stereo  the batched SearchByProjection(F, localMap)
+ *                                  with mvuRight (src/ORBmatcher.cc:95-100)
+ *   orb_stereo_from_rgbd(_batch)   Frame::ComputeStereoFromRGBD src/Frame.cc:707-728 with
+ *                                  Tracking::GrabImageRGBD's convertTo src/Tracking.cc:229-230
+ *   orb_unproject_stereo(_batch)   Frame::UnprojectStereo src/Frame.cc:730-744
+ *   orb_close_points(_batch)       the closest-point selection of Tracking::UpdateLastFrame
+ *                                  src/Tracking.cc:969-1021 and CreateNewKeyFrame :1263-1318,
+ *                                  the counts of NeedNewKeyFrame :1181-1197
  *   orb_vocabulary_create / _load_text / _destroy
  *                                  DBoW2 TemplatedVocabulary ctor + loadFromTextFile
  *                                  Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:1362-1448
@@ -387,6 +395,21 @@ orb_status_t orb_match_projection_local_batch(
     const float* scale_factors, float th, float nnratio, int32_t* d_kp_match,
     int32_t* d_nmatches, void* stream);
 
+/* The same for stereo / RGB-D frames: d_u_right + p*kp_stride is problem p's
+ * mvuRight (-1 = no right coordinate; e.g. orb_stereo_from_rgbd_batch's or
+ * orb_stereo_match_batch's output), read by the staged grid build, the
+ * candidate scan and every resolve, which apply the reference's check
+ * (src/ORBmatcher.cc:95-100: a keypoint with mvuRight > 0 is skipped when
+ * |mTrackProjXR - mvuRight| > r * scale[octave]).  Every other argument as
+ * above; every resolve schedule and routed kernel is supported. */
+orb_status_t orb_match_projection_local_batch_stereo(
+    orb_matcher_t* m, int n_problems, const orb_keypoint_t* d_keys, const uint8_t* d_desc,
+    const float* d_u_right, const int32_t* d_nkeys, const uint8_t* d_locked, int kp_stride,
+    const orb_mp_track_t* d_mps, const uint8_t* d_mp_desc, const int32_t* d_nmps,
+    int mp_stride, float min_x, float max_x, float min_y, float max_y, int n_levels,
+    const float* scale_factors, float th, float nnratio, int32_t* d_kp_match,
+    int32_t* d_nmatches, void* stream);
+
 /* Tracking::SearchLocalPoints' frustum pass: for each local MapPoint in order,
  * skip it if seen or bad, else Frame::isInFrustum(pMP, viewing_cos_limit)
  * (src/Tracking.cc:1360-1377, src/Frame.cc:303-366, MapPoint::PredictScale
@@ -659,6 +682,107 @@ orb_status_t orb_undistort_keypoints_batch(orb_matcher_t* m, int n_frames, const
                                            const orb_keypoint_t* d_keys, int stride,
                                            const float* K, const float* dist, int n_dist,
                                            orb_keypoint_t* d_keys_un, void* stream);
+
+/* ------------------------------------------------------------- RGB-D depth */
+
+/* Frame::ComputeStereoFromRGBD (src/Frame.cc:707-728) on the depth image as
+ * the caller holds it, with Tracking::GrabImageRGBD's conversion
+ * (src/Tracking.cc:229-230) applied to the sampled element only; no converted
+ * image is written.
+ *   Conversion.  The host evaluates the reference's condition exactly,
+ *     fabs(depth_map_factor - 1.0f) > 1e-5 || depth_type != ORB_DEPTH_F32.
+ *     False: the F32 element's bits are used as they are.  True:
+ *     d = (float)src * depth_map_factor, OpenCV's cvtScale_<T, float, float>
+ *     with scale and shift narrowed to float (the + 0.0f shift cannot change a
+ *     value that passes d > 0).  depth_map_factor is Tracking::mDepthMapFactor
+ *     as Tracking holds it, i.e. already inverted (src/Tracking.cc:143-147).
+ *   Sample position.  imDepth.at<float>(v, u) takes float arguments: row =
+ *     (int)mvKeys[i].pt.y, column = (int)mvKeys[i].pt.x, truncated toward zero
+ *     (both are fractional on levels >= 1).
+ *   Outputs.  d > 0: mvDepth = d, mvuRight = mvKeysUn[i].pt.x - bf / d (one
+ *     correctly rounded float divide, one subtract).  Anything else (0,
+ *     negative, NaN): -1 / -1.
+ *   Outside the image.  A keypoint whose truncated position lies outside
+ *     cols x rows (or is NaN / beyond int range) is undefined behaviour in the
+ *     reference; here it yields -1 / -1 and nothing is read.
+ * depth: rows of `row_bytes` bytes (any pitch >= cols x element size that is
+ * a multiple of the element size; the pointer aligned to the element size).
+ * Both conversion pins are unpinned against a real OpenCV.  Host buffers. */
+#define ORB_DEPTH_U16 0 /* CV_16U */
+#define ORB_DEPTH_F32 1 /* CV_32F */
+orb_status_t orb_stereo_from_rgbd(orb_matcher_t* m, int n, const orb_keypoint_t* keys,
+                                  const orb_keypoint_t* keys_un, const void* depth,
+                                  int depth_type, int cols, int rows, size_t row_bytes,
+                                  float depth_map_factor, float bf, float* u_right,
+                                  float* depth_out);
+/* Device-batched form: frame f has d_n[f] keypoints, mvKeys at d_keys +
+ * f * kp_stride and mvKeysUn at d_keys_un + f * kp_stride, and its depth image
+ * at d_depth + f * image_bytes; writes d_u_right / d_depth_out at
+ * f * kp_stride (slots past d_n[f] are left untouched).  Asynchronous on
+ * `stream`; uses no handle scratch. */
+orb_status_t orb_stereo_from_rgbd_batch(orb_matcher_t* m, int n_frames, const int32_t* d_n,
+                                        const orb_keypoint_t* d_keys,
+                                        const orb_keypoint_t* d_keys_un, int kp_stride,
+                                        const void* d_depth, int depth_type, int cols, int rows,
+                                        size_t row_bytes, size_t image_bytes,
+                                        float depth_map_factor, float bf, float* d_u_right,
+                                        float* d_depth_out, void* stream);
+
+/* Frame::UnprojectStereo (src/Frame.cc:730-744; KeyFrame::UnprojectStereo,
+ * src/KeyFrame.cc:640, is the same arithmetic) for every keypoint of a frame.
+ * z = depth[i] <= 0 (or NaN): valid[i] = 0, x3d = 0 (the reference returns an
+ * empty Mat).  Otherwise valid[i] = 1, x = (u - cx) * z * invfx,
+ * y = (v - cy) * z * invfy with invfx = 1.0f / fx computed on the host
+ * (src/Frame.cc:115), and mRwc * x3Dc + mOw with mRwc = rcw transposed, each
+ * component float products summed left to right, then + ow:
+ * X = ((rcw[0]*x + rcw[3]*y) + rcw[6]*z) + ow[0] (the product order is
+ * unpinned against a real OpenCV).  x3d: 3 floats per keypoint.  Host buffers. */
+orb_status_t orb_unproject_stereo(orb_matcher_t* m, int n, const orb_keypoint_t* keys_un,
+                                  const float* depth, const orb_pose_t* pose,
+                                  const orb_camera_t* cam, float* x3d, uint8_t* valid);
+/* Device-batched form: frame f uses d_poses[f]; keypoints, depths, x3d
+ * (3 floats per slot) and valid at f * kp_stride.  Asynchronous on `stream`. */
+orb_status_t orb_unproject_stereo_batch(orb_matcher_t* m, int n_frames, const int32_t* d_n,
+                                        const orb_keypoint_t* d_keys_un, const float* d_depth,
+                                        int kp_stride, const orb_pose_t* d_poses,
+                                        const orb_camera_t* cam, float* d_x3d, uint8_t* d_valid,
+                                        void* stream);
+
+/* The closest-point selection of Tracking::UpdateLastFrame (src/Tracking.cc:
+ * 969-1021) and Tracking::CreateNewKeyFrame (:1263-1318) and the close-point
+ * counts of Tracking::NeedNewKeyFrame (:1181-1197) for one frame.
+ * In: depth = mvDepth; mp_state[i] = 0 mvpMapPoints[i] is NULL, 1 non-NULL
+ * with Observations() < 1, 2 non-NULL with observations (NULL: all 0);
+ * outlier = mvbOutlier (NULL: all false); th_depth = mThDepth.
+ * Out: counts->n_sorted = vDepthIdx.size() (keypoints with z > 0);
+ * order[0 .. n_sorted) = the keypoint index at each position of the sorted
+ * vector<pair<float,int>> (ascending z, ties by ascending index; +inf sorts
+ * last), -1 beyond; counts->n_visit = the positions the loop processes before
+ * its break (it breaks after position j when z_j > th_depth && nPoints > 100,
+ * nPoints counting every processed position); create[j] = 1 for j < n_visit
+ * where mp_state is 0 or 1 (bCreateNew), 0 elsewhere; n_tracked_close /
+ * n_non_tracked_close over z > 0 && z < th_depth (strict: z == th_depth is
+ * neither close nor a reason to break), tracked = mp_state != 0 && !outlier.
+ * The caller applies the side effects in `order` (new MapPoint,
+ * AddObservation, the NULL reset at :1294).  order and create hold n entries.
+ * Frames of up to orb_close_points_lds_keys() keypoint slots sort in LDS,
+ * larger ones in the handle's device scratch.  Host buffers. */
+typedef struct orb_close_counts {
+  int32_t n_sorted, n_visit, n_tracked_close, n_non_tracked_close;
+} orb_close_counts_t;
+orb_status_t orb_close_points(orb_matcher_t* m, int n, const float* depth,
+                              const uint8_t* mp_state, const uint8_t* outlier, float th_depth,
+                              int32_t* order, uint8_t* create, orb_close_counts_t* counts);
+/* Device-batched form: everything per frame at f * kp_stride (order and create
+ * are written for all kp_stride slots), counts at d_counts[f].  kp_stride <
+ * 2^19.  Asynchronous on `stream`. */
+orb_status_t orb_close_points_batch(orb_matcher_t* m, int n_frames, const int32_t* d_n,
+                                    const float* d_depth, const uint8_t* d_mp_state,
+                                    const uint8_t* d_outlier, int kp_stride, float th_depth,
+                                    int32_t* d_order, uint8_t* d_create,
+                                    orb_close_counts_t* d_counts, void* stream);
+/* Largest keypoint-slot count (n, kp_stride) whose keys sort in LDS. */
+int orb_close_points_lds_keys(void);
 
 /* ------------------------------------------------------ DBoW2 vocabulary */
 

@@ -46,6 +46,9 @@ MAP_POINT_DTYPE = np.dtype([("pos", "<f4", (3,)), ("normal", "<f4", (3,)), ("min
                             ("max_distance", "<f4"), ("bad", "u1"), ("seen", "u1"),
                             ("has_obs", "u1"), ("_pad", "u1")])
 POSE_DTYPE = np.dtype([("rcw", "<f4", (9,)), ("tcw", "<f4", (3,)), ("ow", "<f4", (3,))])
+CLOSE_COUNTS_DTYPE = np.dtype([("n_sorted", "<i4"), ("n_visit", "<i4"),
+                               ("n_tracked_close", "<i4"), ("n_non_tracked_close", "<i4")])
+ORB_DEPTH_U16, ORB_DEPTH_F32 = 0, 1
 
 
 class OrbError(RuntimeError):
@@ -183,6 +186,17 @@ def lib() -> ctypes.CDLL:
         "orb_undistort_keypoints": (i32, [vp, i32, vp, vp, vp, i32, vp]),
         "orb_compute_image_bounds": (i32, [vp, i32, i32, vp, vp, i32, vp]),
         "orb_undistort_keypoints_batch": (i32, [vp, i32, vp, vp, i32, vp, vp, i32, vp, vp]),
+        "orb_match_projection_local_batch_stereo": (
+            i32, [vp, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp, i32, f32, f32, f32, f32, i32, vp,
+                  f32, f32, vp, vp, vp]),
+        "orb_stereo_from_rgbd": (i32, [vp, i32, vp, vp, vp, i32, i32, i32, sz, f32, f32, vp, vp]),
+        "orb_stereo_from_rgbd_batch": (i32, [vp, i32, vp, vp, vp, i32, vp, i32, i32, i32, sz, sz,
+                                             f32, f32, vp, vp, vp]),
+        "orb_unproject_stereo": (i32, [vp, i32, vp, vp, vp, vp, vp, vp]),
+        "orb_unproject_stereo_batch": (i32, [vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp]),
+        "orb_close_points": (i32, [vp, i32, vp, vp, vp, f32, vp, vp, vp]),
+        "orb_close_points_batch": (i32, [vp, i32, vp, vp, vp, vp, i32, f32, vp, vp, vp, vp]),
+        "orb_close_points_lds_keys": (i32, []),
         "orb_synth_image": (None, [ctypes.c_uint64, i32, i32, i32, i32, vp, sz]),
         "orb_synth_local_map": (None, [ctypes.c_uint64, vp, vp, i32, i32, i32, i32, vp, vp, vp]),
     }
@@ -923,6 +937,126 @@ class ORBmatcher:
         _check(lib().orb_undistort_keypoints_batch(self._h, n_frames, d_n, d_keys, stride, _ptr(K),
                                                    _ptr(dist), len(dist), d_keys_un,
                                                    stream or None), "undistort_keypoints_batch")
+
+    # ------------------------------------------------------- RGB-D depth (Frame)
+    def search_by_projection_batch_stereo(self, n_problems, d_keys, d_desc, d_u_right, d_nkeys,
+                                          d_locked, kp_stride, d_mps, d_mp_desc, d_nmps,
+                                          mp_stride, width, height, scale_factors, th,
+                                          d_kp_match, d_nmatches, stream: int = 0, min_x=0.0,
+                                          min_y=0.0):
+        """search_by_projection_batch for stereo / RGB-D frames: d_u_right holds
+        mvuRight per problem at p * kp_stride (src/ORBmatcher.cc:95-100)."""
+        sc = np.ascontiguousarray(scale_factors, np.float32)
+        _check(lib().orb_match_projection_local_batch_stereo(
+            self._h, n_problems, d_keys, d_desc, d_u_right, d_nkeys, d_locked or None, kp_stride,
+            d_mps, d_mp_desc, d_nmps, mp_stride, min_x, float(width), min_y, float(height),
+            len(sc), _ptr(sc), th, self.mfNNratio, d_kp_match, d_nmatches, stream or None),
+            "orb_match_projection_local_batch_stereo")
+
+    @staticmethod
+    def _depth_image(imDepth):
+        """(array, depth_type) of a CV_16U / CV_32F depth image; rows may be padded."""
+        im = np.asarray(imDepth)
+        if im.ndim != 2 or im.dtype not in (np.dtype(np.uint16), np.dtype(np.float32)):
+            raise OrbError(ORB_EINVAL, "depth image must be 2-D uint16 or float32")
+        if im.strides[1] != im.itemsize or im.strides[0] < im.shape[1] * im.itemsize:
+            im = np.ascontiguousarray(im)
+        return im, (ORB_DEPTH_U16 if im.dtype == np.uint16 else ORB_DEPTH_F32)
+
+    def ComputeStereoFromRGBD(self, mvKeys, mvKeysUn, imDepth, mDepthMapFactor, mbf):
+        """Frame::ComputeStereoFromRGBD (src/Frame.cc:707-728) on the depth image
+        as GrabImageRGBD receives it (src/Tracking.cc:229-230; uint16 or float32,
+        mDepthMapFactor already inverted): returns (mvuRight, mvDepth)."""
+        keys = np.ascontiguousarray(mvKeys, KEYPOINT_DTYPE)
+        un = np.ascontiguousarray(mvKeysUn, KEYPOINT_DTYPE)
+        if len(un) != len(keys):
+            raise OrbError(ORB_EINVAL, "mvKeys and mvKeysUn differ in length")
+        im, typ = self._depth_image(imDepth)
+        n = len(keys)
+        ur = np.full(n, -1, np.float32)
+        dp = np.full(n, -1, np.float32)
+        _check(lib().orb_stereo_from_rgbd(
+            self._h, n, _ptr(keys) if n else None, _ptr(un) if n else None, _ptr(im), typ,
+            im.shape[1], im.shape[0], im.strides[0], float(mDepthMapFactor), float(mbf),
+            _ptr(ur) if n else None, _ptr(dp) if n else None), "ComputeStereoFromRGBD")
+        return ur, dp
+
+    def stereo_from_rgbd_batch(self, n_frames, d_n, d_keys, d_keys_un, kp_stride, d_depth,
+                               depth_type, cols, rows, row_bytes, image_bytes, depth_map_factor,
+                               bf, d_u_right, d_depth_out, stream: int = 0):
+        """Device-batched ComputeStereoFromRGBD (orb_stereo_from_rgbd_batch)."""
+        _check(lib().orb_stereo_from_rgbd_batch(
+            self._h, n_frames, d_n, d_keys, d_keys_un, kp_stride, d_depth, depth_type, cols, rows,
+            row_bytes, image_bytes, float(depth_map_factor), float(bf), d_u_right, d_depth_out,
+            stream or None), "stereo_from_rgbd_batch")
+
+    @staticmethod
+    def _camera(cam):
+        return cam if isinstance(cam, _Camera) else _Camera(*[float(v) for v in cam])
+
+    def UnprojectStereo(self, mvKeysUn, mvDepth, pose, cam):
+        """Frame::UnprojectStereo (src/Frame.cc:730-744) for every keypoint:
+        returns (x3D (n, 3) float32, valid (n,) uint8; invalid rows are 0).
+        pose: POSE_DTYPE record; cam: (fx, fy, cx, cy, bf, mb)."""
+        un = np.ascontiguousarray(mvKeysUn, KEYPOINT_DTYPE)
+        z = np.ascontiguousarray(mvDepth, np.float32)
+        if len(z) != len(un):
+            raise OrbError(ORB_EINVAL, "mvKeysUn and mvDepth differ in length")
+        pose = np.ascontiguousarray(pose, POSE_DTYPE).reshape(1)
+        c = self._camera(cam)
+        n = len(un)
+        x3d = np.zeros((n, 3), np.float32)
+        valid = np.zeros(n, np.uint8)
+        _check(lib().orb_unproject_stereo(
+            self._h, n, _ptr(un) if n else None, _ptr(z) if n else None, _ptr(pose),
+            ctypes.addressof(c), _ptr(x3d) if n else None, _ptr(valid) if n else None),
+            "UnprojectStereo")
+        return x3d, valid
+
+    def unproject_stereo_batch(self, n_frames, d_n, d_keys_un, d_depth, kp_stride, d_poses, cam,
+                               d_x3d, d_valid, stream: int = 0):
+        """Device-batched UnprojectStereo (orb_unproject_stereo_batch)."""
+        c = self._camera(cam)
+        _check(lib().orb_unproject_stereo_batch(
+            self._h, n_frames, d_n, d_keys_un, d_depth, kp_stride, d_poses, ctypes.addressof(c),
+            d_x3d, d_valid, stream or None), "unproject_stereo_batch")
+
+    def ClosePoints(self, mvDepth, mp_state, outlier, mThDepth):
+        """The closest-point selection of Tracking::UpdateLastFrame /
+        CreateNewKeyFrame and the counts of NeedNewKeyFrame
+        (src/Tracking.cc:969-1021, :1263-1318, :1181-1197).  mp_state: 0 no
+        MapPoint, 1 one without observations, 2 one with.  Returns (order
+        [n_sorted], create [n_visit], n_tracked_close, n_non_tracked_close)."""
+        z = np.ascontiguousarray(mvDepth, np.float32)
+        n = len(z)
+        ms = None if mp_state is None else np.ascontiguousarray(mp_state, np.uint8)
+        ol = None if outlier is None else np.ascontiguousarray(outlier, np.uint8)
+        if (ms is not None and len(ms) != n) or (ol is not None and len(ol) != n):
+            raise OrbError(ORB_EINVAL, "mp_state / outlier differ in length from mvDepth")
+        order = np.full(n, -1, np.int32)
+        create = np.zeros(n, np.uint8)
+        counts = np.zeros(1, CLOSE_COUNTS_DTYPE)
+        _check(lib().orb_close_points(
+            self._h, n, _ptr(z) if n else None, _ptr(ms) if ms is not None and n else None,
+            _ptr(ol) if ol is not None and n else None, float(mThDepth),
+            _ptr(order) if n else None, _ptr(create) if n else None, _ptr(counts)),
+            "ClosePoints")
+        c = counts[0]
+        return (order[: c["n_sorted"]].copy(), create[: c["n_visit"]].copy(),
+                int(c["n_tracked_close"]), int(c["n_non_tracked_close"]))
+
+    def close_points_batch(self, n_frames, d_n, d_depth, d_mp_state, d_outlier, kp_stride,
+                           th_depth, d_order, d_create, d_counts, stream: int = 0):
+        """Device-batched ClosePoints (orb_close_points_batch); d_counts holds
+        n_frames CLOSE_COUNTS_DTYPE records."""
+        _check(lib().orb_close_points_batch(
+            self._h, n_frames, d_n, d_depth, d_mp_state or None, d_outlier or None, kp_stride,
+            float(th_depth), d_order, d_create, d_counts, stream or None), "close_points_batch")
+
+    @staticmethod
+    def close_points_lds_keys() -> int:
+        """Largest keypoint-slot count whose keys k_close_points sorts in LDS."""
+        return lib().orb_close_points_lds_keys()
 
     # ------------------------------------------ MapPoint::ComputeDistinctiveDescriptors
     def ComputeDistinctiveDescriptors(self, obs_offs, obs_desc, descriptors=None):

@@ -1,6 +1,6 @@
 // orb_kernel_params.h -- the parameter blocks and records the host runtime
-// fills and the matcher / mapping / vocabulary / place-recognition / camera
-// kernels read: one definition for both sides, as orb_plan.h is for the
+// fills and the matcher / mapping / vocabulary / place-recognition / camera /
+// depth kernels read: one definition for both sides, as orb_plan.h is for the
 // extractor.  Plain C++ (no HIP): a host and a device compile both include it.
 // The blocks marked "by value" are kernel arguments, so their names are part
 // of the kernels' mangled symbols.
@@ -116,6 +116,29 @@ struct UndistortParams {
   double k[12];                     // k1 k2 p1 p2 k3 k4 k5 k6 s1 s2 s3 s4
 };
 static_assert(sizeof(UndistortParams) == 27 * 8, "parameter block layout");
+
+// -------------------------------------------------------- depth_kernels.hip
+// Frame::ComputeStereoFromRGBD over n_frames x stride keypoint slots (by value)
+struct RgbdParams {
+  int nFrames, stride;
+  int depthType;  // ORB_DEPTH_U16 / ORB_DEPTH_F32
+  int convert;    // GrabImageRGBD's condition (src/Tracking.cc:229), evaluated on the host
+  int cols, rows;
+  long long rowBytes, imageBytes;
+  float factor;  // mDepthMapFactor
+  float bf;
+};
+
+// Frame::UnprojectStereo (by value): invfx = 1.0f / fx as src/Frame.cc:115
+struct UnprojectParams {
+  int nFrames, stride;
+  float cx, cy, invfx, invfy;
+};
+
+// k_close_points sorts up to this many 8-byte keys in LDS (32 KiB; the next
+// power of two, 64 KiB of keys plus the counters, exceeds the 64 KiB a
+// workgroup gets without opting in)
+#define CP_LDS_KEYS 4096
 
 // ----------------------------------------------------- placerec_kernels.hip
 #define PR_NEIGH 10  // covisibility neighbours stored per keyframe

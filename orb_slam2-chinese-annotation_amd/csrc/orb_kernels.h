@@ -178,4 +178,20 @@ hipError_t orb_k_undistort_points(const UndistortParams* params, int n, const fl
 hipError_t orb_k_undistort_keys(const UndistortParams* params, int nFrames,
                                 const int32_t* counts, int nSingle, int stride, const void* in,
                                 void* out, int copyOnly, hipStream_t s);
+
+// -------------------------------------------------------- depth_kernels.hip
+hipError_t orb_k_stereo_from_rgbd(const RgbdParams* params, const int32_t* counts, int nSingle,
+                                  const orb_keypoint_t* keys, const orb_keypoint_t* keysUn,
+                                  const void* depth, float* uRight, float* depthOut,
+                                  hipStream_t s);
+hipError_t orb_k_unproject_stereo(const UnprojectParams* params, const int32_t* counts,
+                                  int nSingle, const orb_keypoint_t* keysUn, const float* depth,
+                                  const orb_pose_t* poses, float* x3d, uint8_t* valid,
+                                  hipStream_t s);
+// bytes of global key scratch a call needs (0: the keys sort in LDS)
+size_t orb_k_close_points_scratch(int nFrames, int stride);
+hipError_t orb_k_close_points(int nFrames, const int32_t* counts, int nSingle, int stride,
+                              const float* depth, const uint8_t* mpState, const uint8_t* outlier,
+                              float thDepth, int32_t* order, uint8_t* create,
+                              orb_close_counts_t* out, void* scratch, hipStream_t s);
 }

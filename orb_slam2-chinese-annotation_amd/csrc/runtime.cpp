@@ -1398,6 +1398,7 @@ struct orb_matcher {
   DevBuf dKeys, dDesc, dUr, dLocked, dNKeys, dMps, dMpDesc, dNMps, dCellStart, dCellIdx, dTopk,
       dNcand, dKpMatch, dNMatch, dA, dB, dOut;
   DevBuf dJac;  // Jacobi-resolve scratch (ORB_RESOLVE_JACOBI)
+  DevBuf dCpKeys;  // k_close_points' key scratch for frames above CP_LDS_KEYS slots
   DevBuf dOvf, dOvfCtr;  // candidate lists of SearchByProjection(F, localMap) (ProjParams.ovf)
   uint32_t ovfGen = 0;
   int stagedN = -1, stagedM = -1;  // orb_match_projection_local_stage's layout
@@ -1521,9 +1522,10 @@ static orb_status_t ovf_pool(orb_matcher_t* m, int nproblems, ProjParams& P, hip
   return ORB_OK;
 }
 
-orb_status_t orb_match_projection_local_batch(
+// d_u_right: mvuRight per problem at p * kp_stride, or null (monocular)
+static orb_status_t local_batch(
     orb_matcher_t* m, int n_problems, const orb_keypoint_t* d_keys, const uint8_t* d_desc,
-    const int32_t* d_nkeys, const uint8_t* d_locked, int kp_stride,
+    const float* d_u_right, const int32_t* d_nkeys, const uint8_t* d_locked, int kp_stride,
     const orb_mp_track_t* d_mps, const uint8_t* d_mp_desc, const int32_t* d_nmps,
     int mp_stride, float min_x, float max_x, float min_y, float max_y, int n_levels,
     const float* scale_factors, float th, float nnratio, int32_t* d_kp_match,
@@ -1556,7 +1558,7 @@ orb_status_t orb_match_projection_local_batch(
   PROF_REC(ev, pf.t0(ev), s);
   PROF_REC(ev, pf.b(ev, 0), s);
   if (stage)
-    HIP_TRY(orb_k_grid_build_staged(d_keys, d_nkeys, d_locked, nullptr, kp_stride, P.minX, P.minY,
+    HIP_TRY(orb_k_grid_build_staged(d_keys, d_nkeys, d_locked, d_u_right, kp_stride, P.minX, P.minY,
                                     P.invW, P.invH, m->dCellStart.as<int32_t>(),
                                     m->dCellIdx.as<int32_t>(), m->dProjStage.p, n_problems, s));
   else
@@ -1565,14 +1567,14 @@ orb_status_t orb_match_projection_local_batch(
                              s));
   PROF_REC(ev, pf.e(ev, 0), s);
   PROF_REC(ev, pf.b(ev, 1), s);
-  HIP_TRY(orb_k_proj_candidates(d_keys, d_desc, nullptr, d_locked, kp_stride, d_nkeys, d_mps, d_mp_desc,
+  HIP_TRY(orb_k_proj_candidates(d_keys, d_desc, d_u_right, d_locked, kp_stride, d_nkeys, d_mps, d_mp_desc,
                                 d_nmps, mp_stride, mp_stride, m->dCellStart.as<int32_t>(),
                                 m->dCellIdx.as<int32_t>(), stage ? m->dProjStage.p : nullptr,
                                 &P, m->dTopk.as<uint32_t>(),
                                 m->dNcand.as<int32_t>(), n_problems, s));
   PROF_REC(ev, pf.e(ev, 1), s);
   PROF_REC(ev, pf.b(ev, 2), s);
-  HIP_TRY(orb_k_proj_resolve(d_keys, d_desc, nullptr, d_locked, d_nkeys, kp_stride, d_mps,
+  HIP_TRY(orb_k_proj_resolve(d_keys, d_desc, d_u_right, d_locked, d_nkeys, kp_stride, d_mps,
                              d_mp_desc, d_nmps, mp_stride, m->dCellStart.as<int32_t>(),
                              m->dCellIdx.as<int32_t>(), &P, m->dTopk.as<uint32_t>(),
                              m->dNcand.as<int32_t>(), d_kp_match, d_nmatches, n_problems,
@@ -1580,6 +1582,31 @@ orb_status_t orb_match_projection_local_batch(
   PROF_REC(ev, pf.e(ev, 2), s);
   PROF_REC(ev, pf.t1(ev), s);
   return ORB_OK;
+}
+
+orb_status_t orb_match_projection_local_batch(
+    orb_matcher_t* m, int n_problems, const orb_keypoint_t* d_keys, const uint8_t* d_desc,
+    const int32_t* d_nkeys, const uint8_t* d_locked, int kp_stride,
+    const orb_mp_track_t* d_mps, const uint8_t* d_mp_desc, const int32_t* d_nmps,
+    int mp_stride, float min_x, float max_x, float min_y, float max_y, int n_levels,
+    const float* scale_factors, float th, float nnratio, int32_t* d_kp_match,
+    int32_t* d_nmatches, void* stream) {
+  return local_batch(m, n_problems, d_keys, d_desc, nullptr, d_nkeys, d_locked, kp_stride, d_mps,
+                     d_mp_desc, d_nmps, mp_stride, min_x, max_x, min_y, max_y, n_levels,
+                     scale_factors, th, nnratio, d_kp_match, d_nmatches, stream);
+}
+
+orb_status_t orb_match_projection_local_batch_stereo(
+    orb_matcher_t* m, int n_problems, const orb_keypoint_t* d_keys, const uint8_t* d_desc,
+    const float* d_u_right, const int32_t* d_nkeys, const uint8_t* d_locked, int kp_stride,
+    const orb_mp_track_t* d_mps, const uint8_t* d_mp_desc, const int32_t* d_nmps,
+    int mp_stride, float min_x, float max_x, float min_y, float max_y, int n_levels,
+    const float* scale_factors, float th, float nnratio, int32_t* d_kp_match,
+    int32_t* d_nmatches, void* stream) {
+  if (!d_u_right) return ORB_EINVAL;  // (the monocular form is orb_match_projection_local_batch)
+  return local_batch(m, n_problems, d_keys, d_desc, d_u_right, d_nkeys, d_locked, kp_stride,
+                     d_mps, d_mp_desc, d_nmps, mp_stride, min_x, max_x, min_y, max_y, n_levels,
+                     scale_factors, th, nnratio, d_kp_match, d_nmatches, stream);
 }
 
 orb_status_t orb_matcher_set_resolve(orb_matcher_t* m, int schedule, int jacobi_rounds) {
@@ -3683,6 +3710,207 @@ orb_status_t orb_undistort_keypoints_batch(orb_matcher_t* m, int n_frames, const
   hipSetDevice(m->device);
   HIP_TRY(orb_k_undistort_keys(&P, n_frames, d_n, 0, stride, d_keys, d_keys_un,
                                dist[0] == 0.0f ? 1 : 0, stream ? (hipStream_t)stream : m->stream));
+  return ORB_OK;
+}
+
+// ------------------------------------------------------------- RGB-D depth
+// Frame::ComputeStereoFromRGBD with GrabImageRGBD's conversion
+// (src/Frame.cc:707-728, src/Tracking.cc:229-230); depth_kernels.hip.
+static orb_status_t rgbd_params(int n_frames, int stride, int depth_type, int cols, int rows,
+                                size_t row_bytes, size_t image_bytes, float factor, float bf,
+                                const void* depth, RgbdParams& P) {
+  if (depth_type != ORB_DEPTH_U16 && depth_type != ORB_DEPTH_F32) return ORB_EINVAL;
+  const size_t es = depth_type == ORB_DEPTH_U16 ? 2 : 4;
+  if (cols <= 0 || rows <= 0 || row_bytes < (size_t)cols * es || row_bytes % es ||
+      image_bytes % es || ((uintptr_t)depth % es))
+    return ORB_EINVAL;
+  if (n_frames > 1 && image_bytes < (size_t)(rows - 1) * row_bytes + (size_t)cols * es)
+    return ORB_EINVAL;
+  P.nFrames = n_frames;
+  P.stride = stride;
+  P.depthType = depth_type;
+  // the reference's condition as written: fabs(mDepthMapFactor-1.0f)>1e-5 || type != CV_32F
+  P.convert = (fabs(factor - 1.0f) > 1e-5 || depth_type != ORB_DEPTH_F32) ? 1 : 0;
+  P.cols = cols;
+  P.rows = rows;
+  P.rowBytes = (long long)row_bytes;
+  P.imageBytes = (long long)image_bytes;
+  P.factor = factor;
+  P.bf = bf;
+  return ORB_OK;
+}
+
+orb_status_t orb_stereo_from_rgbd(orb_matcher_t* m, int n, const orb_keypoint_t* keys,
+                                  const orb_keypoint_t* keys_un, const void* depth,
+                                  int depth_type, int cols, int rows, size_t row_bytes,
+                                  float depth_map_factor, float bf, float* u_right,
+                                  float* depth_out) {
+  if (!m || n < 0 || !depth || (n > 0 && (!keys || !keys_un || !u_right || !depth_out)))
+    return ORB_EINVAL;
+  RgbdParams P;
+  orb_status_t st = rgbd_params(1, n, depth_type, cols, rows, row_bytes, 0, depth_map_factor, bf,
+                                depth, P);
+  if (st) return st;
+  if (n == 0) return ORB_OK;
+  std::lock_guard<std::mutex> g(m->mu);
+  hipSetDevice(m->device);
+  hipStream_t s = m->stream;
+  CallOrder order(m->evLast, &m->lastStream, s);
+  if (order.status) return order.status;
+  const size_t kb = (size_t)n * sizeof(orb_keypoint_t);
+  if ((st = upload(m->dA, keys, kb, s)) || (st = upload(m->dB, keys_un, kb, s)) ||
+      (st = upload(m->dIn, depth, (size_t)rows * row_bytes, s)) ||
+      (st = m->dOut.ensure((size_t)n * 8)))
+    return st;
+  float* out = m->dOut.as<float>();
+  HIP_TRY(orb_k_stereo_from_rgbd(&P, nullptr, n, m->dA.as<orb_keypoint_t>(),
+                                 m->dB.as<orb_keypoint_t>(), m->dIn.p, out, out + n, s));
+  HIP_TRY(hipMemcpyAsync(u_right, out, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(depth_out, out + n, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(stream_wait(s));
+  order.settled();
+  return ORB_OK;
+}
+
+orb_status_t orb_stereo_from_rgbd_batch(orb_matcher_t* m, int n_frames, const int32_t* d_n,
+                                        const orb_keypoint_t* d_keys,
+                                        const orb_keypoint_t* d_keys_un, int kp_stride,
+                                        const void* d_depth, int depth_type, int cols, int rows,
+                                        size_t row_bytes, size_t image_bytes,
+                                        float depth_map_factor, float bf, float* d_u_right,
+                                        float* d_depth_out, void* stream) {
+  if (!m || n_frames < 0 || kp_stride <= 0) return ORB_EINVAL;
+  if (n_frames == 0) return ORB_OK;
+  if (!d_n || !d_keys || !d_keys_un || !d_depth || !d_u_right || !d_depth_out) return ORB_EINVAL;
+  RgbdParams P;
+  orb_status_t st = rgbd_params(n_frames, kp_stride, depth_type, cols, rows, row_bytes,
+                                image_bytes, depth_map_factor, bf, d_depth, P);
+  if (st) return st;
+  hipSetDevice(m->device);
+  HIP_TRY(orb_k_stereo_from_rgbd(&P, d_n, 0, d_keys, d_keys_un, d_depth, d_u_right, d_depth_out,
+                                 stream ? (hipStream_t)stream : m->stream));
+  return ORB_OK;
+}
+
+// Frame::UnprojectStereo (src/Frame.cc:730-744)
+static UnprojectParams unproject_params(int n_frames, int stride, const orb_camera_t* cam) {
+  UnprojectParams P;
+  P.nFrames = n_frames;
+  P.stride = stride;
+  P.cx = cam->cx;
+  P.cy = cam->cy;
+  P.invfx = 1.0f / cam->fx;  // src/Frame.cc:115-116
+  P.invfy = 1.0f / cam->fy;
+  return P;
+}
+
+orb_status_t orb_unproject_stereo(orb_matcher_t* m, int n, const orb_keypoint_t* keys_un,
+                                  const float* depth, const orb_pose_t* pose,
+                                  const orb_camera_t* cam, float* x3d, uint8_t* valid) {
+  if (!m || n < 0 || !pose || !cam || (n > 0 && (!keys_un || !depth || !x3d || !valid)))
+    return ORB_EINVAL;
+  if (n == 0) return ORB_OK;
+  const UnprojectParams P = unproject_params(1, n, cam);
+  std::lock_guard<std::mutex> g(m->mu);
+  hipSetDevice(m->device);
+  hipStream_t s = m->stream;
+  CallOrder order(m->evLast, &m->lastStream, s);
+  if (order.status) return order.status;
+  orb_status_t st;
+  if ((st = upload(m->dA, keys_un, (size_t)n * sizeof(orb_keypoint_t), s)) ||
+      (st = upload(m->dB, depth, (size_t)n * 4, s)) ||
+      (st = upload(m->dPose, pose, sizeof(orb_pose_t), s)) ||
+      (st = m->dOut.ensure((size_t)n * 16)))
+    return st;
+  float* out = m->dOut.as<float>();
+  uint8_t* dv = (uint8_t*)(out + 3 * (size_t)n);
+  HIP_TRY(orb_k_unproject_stereo(&P, nullptr, n, m->dA.as<orb_keypoint_t>(), m->dB.as<float>(),
+                                 m->dPose.as<orb_pose_t>(), out, dv, s));
+  HIP_TRY(hipMemcpyAsync(x3d, out, (size_t)n * 12, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(valid, dv, (size_t)n, hipMemcpyDeviceToHost, s));
+  HIP_TRY(stream_wait(s));
+  order.settled();
+  return ORB_OK;
+}
+
+orb_status_t orb_unproject_stereo_batch(orb_matcher_t* m, int n_frames, const int32_t* d_n,
+                                        const orb_keypoint_t* d_keys_un, const float* d_depth,
+                                        int kp_stride, const orb_pose_t* d_poses,
+                                        const orb_camera_t* cam, float* d_x3d, uint8_t* d_valid,
+                                        void* stream) {
+  if (!m || n_frames < 0 || kp_stride <= 0 || !cam) return ORB_EINVAL;
+  if (n_frames == 0) return ORB_OK;
+  if (!d_n || !d_keys_un || !d_depth || !d_poses || !d_x3d || !d_valid) return ORB_EINVAL;
+  const UnprojectParams P = unproject_params(n_frames, kp_stride, cam);
+  hipSetDevice(m->device);
+  HIP_TRY(orb_k_unproject_stereo(&P, d_n, 0, d_keys_un, d_depth, d_poses, d_x3d, d_valid,
+                                 stream ? (hipStream_t)stream : m->stream));
+  return ORB_OK;
+}
+
+// The closest-point selection and close-point counts (src/Tracking.cc:969-1021,
+// :1263-1318, :1181-1197); k_close_points.
+int orb_close_points_lds_keys(void) { return CP_LDS_KEYS; }
+
+orb_status_t orb_close_points(orb_matcher_t* m, int n, const float* depth,
+                              const uint8_t* mp_state, const uint8_t* outlier, float th_depth,
+                              int32_t* order, uint8_t* create, orb_close_counts_t* counts) {
+  if (!m || n < 0 || n >= (1 << 19) || !counts || (n > 0 && (!depth || !order || !create)))
+    return ORB_EINVAL;
+  memset(counts, 0, sizeof(*counts));
+  if (n == 0) return ORB_OK;
+  std::lock_guard<std::mutex> g(m->mu);
+  hipSetDevice(m->device);
+  hipStream_t s = m->stream;
+  CallOrder co(m->evLast, &m->lastStream, s);
+  if (co.status) return co.status;
+  orb_status_t st;
+  // dOut: order (n x 4), counts (16), create (n)
+  if ((st = upload(m->dA, depth, (size_t)n * 4, s)) ||
+      (mp_state && (st = upload(m->dB, mp_state, (size_t)n, s))) ||
+      (outlier && (st = upload(m->dLocked, outlier, (size_t)n, s))) ||
+      (st = m->dOut.ensure((size_t)n * 5 + 16)))
+    return st;
+  const size_t sb = orb_k_close_points_scratch(1, n);
+  if (sb && (st = m->dCpKeys.ensure(sb))) return st;
+  int32_t* dOrder = m->dOut.as<int32_t>();
+  orb_close_counts_t* dCounts = (orb_close_counts_t*)(dOrder + n);
+  uint8_t* dCreate = (uint8_t*)(dCounts + 1);
+  HIP_TRY(orb_k_close_points(1, nullptr, n, n, m->dA.as<float>(),
+                             mp_state ? m->dB.as<uint8_t>() : nullptr,
+                             outlier ? m->dLocked.as<uint8_t>() : nullptr, th_depth, dOrder,
+                             dCreate, dCounts, sb ? m->dCpKeys.p : nullptr, s));
+  HIP_TRY(hipMemcpyAsync(order, dOrder, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(create, dCreate, (size_t)n, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(counts, dCounts, sizeof(*counts), hipMemcpyDeviceToHost, s));
+  HIP_TRY(stream_wait(s));
+  co.settled();
+  return ORB_OK;
+}
+
+orb_status_t orb_close_points_batch(orb_matcher_t* m, int n_frames, const int32_t* d_n,
+                                    const float* d_depth, const uint8_t* d_mp_state,
+                                    const uint8_t* d_outlier, int kp_stride, float th_depth,
+                                    int32_t* d_order, uint8_t* d_create,
+                                    orb_close_counts_t* d_counts, void* stream) {
+  if (!m || n_frames < 0 || kp_stride <= 0 || kp_stride >= (1 << 19)) return ORB_EINVAL;
+  if (n_frames == 0) return ORB_OK;
+  if (!d_n || !d_depth || !d_order || !d_create || !d_counts) return ORB_EINVAL;
+  hipSetDevice(m->device);
+  hipStream_t s = stream ? (hipStream_t)stream : m->stream;
+  const size_t sb = orb_k_close_points_scratch(n_frames, kp_stride);
+  if (!sb) {  // the keys sort in LDS: no handle scratch, nothing to order
+    HIP_TRY(orb_k_close_points(n_frames, d_n, 0, kp_stride, d_depth, d_mp_state, d_outlier,
+                               th_depth, d_order, d_create, d_counts, nullptr, s));
+    return ORB_OK;
+  }
+  std::lock_guard<std::mutex> g(m->mu);
+  CallOrder co(m->evLast, &m->lastStream, s);
+  if (co.status) return co.status;
+  orb_status_t st = m->dCpKeys.ensure(sb);
+  if (st) return st;
+  HIP_TRY(orb_k_close_points(n_frames, d_n, 0, kp_stride, d_depth, d_mp_state, d_outlier,
+                             th_depth, d_order, d_create, d_counts, m->dCpKeys.p, s));
   return ORB_OK;
 }
 

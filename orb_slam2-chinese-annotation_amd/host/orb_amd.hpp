@@ -653,6 +653,119 @@ class ORBmatcher {
     F.mnMaxY = b[3];
   }
 
+  // A depth image as Tracking::GrabImageRGBD receives it: CV_16U or CV_32F
+  // (type = ORB_DEPTH_U16 / ORB_DEPTH_F32), rows `step` bytes apart.
+  struct DepthView {
+    const void* data = nullptr;
+    int type = ORB_DEPTH_F32;
+    int cols = 0, rows = 0;
+    size_t step = 0;
+  };
+
+  // Frame::ComputeStereoFromRGBD (src/Frame.cc:707-728) with GrabImageRGBD's
+  // conversion (src/Tracking.cc:229-230) applied to the sampled elements:
+  // mDepthMapFactor as Tracking holds it (already inverted).  A keypoint outside
+  // the image gives -1 / -1 (undefined in the reference).
+  void ComputeStereoFromRGBD(const std::vector<KeyPoint>& mvKeys,
+                             const std::vector<KeyPoint>& mvKeysUn, const DepthView& imDepth,
+                             float mDepthMapFactor, float mbf, std::vector<float>& mvuRight,
+                             std::vector<float>& mvDepth) {
+    assert(mvKeys.size() == mvKeysUn.size());
+    mvuRight.assign(mvKeys.size(), -1.0f);
+    mvDepth.assign(mvKeys.size(), -1.0f);
+    check(orb_stereo_from_rgbd(h_, (int)mvKeys.size(), mvKeys.data(), mvKeysUn.data(),
+                               imDepth.data, imDepth.type, imDepth.cols, imDepth.rows,
+                               imDepth.step, mDepthMapFactor, mbf, mvuRight.data(),
+                               mvDepth.data()),
+          "ComputeStereoFromRGBD");
+  }
+  void stereo_from_rgbd_batch(int n_frames, const int32_t* d_n, const KeyPoint* d_keys,
+                              const KeyPoint* d_keys_un, int kp_stride, const void* d_depth,
+                              int depth_type, int cols, int rows, size_t row_bytes,
+                              size_t image_bytes, float mDepthMapFactor, float mbf,
+                              float* d_u_right, float* d_depth_out, void* stream = nullptr) {
+    check(orb_stereo_from_rgbd_batch(h_, n_frames, d_n, d_keys, d_keys_un, kp_stride, d_depth,
+                                     depth_type, cols, rows, row_bytes, image_bytes,
+                                     mDepthMapFactor, mbf, d_u_right, d_depth_out, stream),
+          "stereo_from_rgbd_batch");
+  }
+
+  // Frame::UnprojectStereo (src/Frame.cc:730-744) for every keypoint: x3D holds
+  // 3 floats per keypoint (zeros where the reference returns an empty Mat,
+  // valid[i] = 0).
+  void UnprojectStereo(const std::vector<KeyPoint>& mvKeysUn, const std::vector<float>& mvDepth,
+                       const orb_pose_t& pose, const orb_camera_t& cam, std::vector<float>& x3D,
+                       std::vector<uint8_t>& valid) {
+    assert(mvKeysUn.size() == mvDepth.size());
+    x3D.assign(mvKeysUn.size() * 3, 0.0f);
+    valid.assign(mvKeysUn.size(), 0);
+    check(orb_unproject_stereo(h_, (int)mvKeysUn.size(), mvKeysUn.data(), mvDepth.data(), &pose,
+                               &cam, x3D.data(), valid.data()),
+          "UnprojectStereo");
+  }
+  void unproject_stereo_batch(int n_frames, const int32_t* d_n, const KeyPoint* d_keys_un,
+                              const float* d_depth, int kp_stride, const orb_pose_t* d_poses,
+                              const orb_camera_t& cam, float* d_x3d, uint8_t* d_valid,
+                              void* stream = nullptr) {
+    check(orb_unproject_stereo_batch(h_, n_frames, d_n, d_keys_un, d_depth, kp_stride, d_poses,
+                                     &cam, d_x3d, d_valid, stream),
+          "unproject_stereo_batch");
+  }
+
+  // The closest-point selection of Tracking::UpdateLastFrame / CreateNewKeyFrame
+  // (src/Tracking.cc:969-1021, :1263-1318) and NeedNewKeyFrame's counts
+  // (:1181-1197).  mpState[i]: 0 no MapPoint, 1 one with Observations() < 1,
+  // 2 one with observations.  order = the sorted vDepthIdx's keypoint indices,
+  // create = bCreateNew at each position the loop processes before its break;
+  // the caller applies the side effects in that order.
+  struct ClosePointsResult {
+    std::vector<int32_t> order;
+    std::vector<uint8_t> create;
+    int nTrackedClose = 0, nNonTrackedClose = 0;
+  };
+  ClosePointsResult ClosePoints(const std::vector<float>& mvDepth,
+                                const std::vector<uint8_t>& mpState,
+                                const std::vector<uint8_t>& mvbOutlier, float mThDepth) {
+    assert(mpState.size() == mvDepth.size() && mvbOutlier.size() == mvDepth.size());
+    ClosePointsResult r;
+    r.order.resize(mvDepth.size());
+    r.create.resize(mvDepth.size());
+    orb_close_counts_t c;
+    check(orb_close_points(h_, (int)mvDepth.size(), mvDepth.data(), mpState.data(),
+                           mvbOutlier.data(), mThDepth, r.order.data(), r.create.data(), &c),
+          "ClosePoints");
+    r.order.resize(c.n_sorted);
+    r.create.resize(c.n_visit);
+    r.nTrackedClose = c.n_tracked_close;
+    r.nNonTrackedClose = c.n_non_tracked_close;
+    return r;
+  }
+  void close_points_batch(int n_frames, const int32_t* d_n, const float* d_depth,
+                          const uint8_t* d_mp_state, const uint8_t* d_outlier, int kp_stride,
+                          float mThDepth, int32_t* d_order, uint8_t* d_create,
+                          orb_close_counts_t* d_counts, void* stream = nullptr) {
+    check(orb_close_points_batch(h_, n_frames, d_n, d_depth, d_mp_state, d_outlier, kp_stride,
+                                 mThDepth, d_order, d_create, d_counts, stream),
+          "close_points_batch");
+  }
+
+  // Device-batched SearchByProjection(F, vpMapPoints, th) for stereo / RGB-D
+  // frames: d_u_right = mvuRight per problem at p * kp_stride
+  // (orb_match_projection_local_batch_stereo).
+  void search_by_projection_batch_stereo(
+      int n_problems, const KeyPoint* d_keys, const uint8_t* d_desc, const float* d_u_right,
+      const int32_t* d_nkeys, const uint8_t* d_locked, int kp_stride, const orb_mp_track_t* d_mps,
+      const uint8_t* d_mp_desc, const int32_t* d_nmps, int mp_stride, float min_x, float max_x,
+      float min_y, float max_y, const std::vector<float>& mvScaleFactors, float th,
+      int32_t* d_kp_match, int32_t* d_nmatches, void* stream = nullptr) {
+    check(orb_match_projection_local_batch_stereo(
+              h_, n_problems, d_keys, d_desc, d_u_right, d_nkeys, d_locked, kp_stride, d_mps,
+              d_mp_desc, d_nmps, mp_stride, min_x, max_x, min_y, max_y,
+              (int)mvScaleFactors.size(), mvScaleFactors.data(), th, mfNNratio, d_kp_match,
+              d_nmatches, stream),
+          "search_by_projection_batch_stereo");
+  }
+
   float mfNNratio;
   bool mbCheckOrientation;
   orb_matcher_t* handle() { return h_; }

@@ -28,8 +28,14 @@ results table:
       4,096 keyframes of about 1,000 words each on an ORBvoc-shaped synthetic
       vocabulary (k 10, L 6), one query per call (queries/s), each kernel's
       isolated time, bytes/s against 12 B per database entry + exact check
+  R1  RGB-D: 640x480 (TUM1 intrinsics and distortion, DepthMapFactor 5000),
+      1000 features, 256 frames per launch, device-resident: extract ->
+      undistort -> ComputeStereoFromRGBD -> closest points + UnprojectStereo ->
+      stereo batch SearchByProjection against 3,000-point maps (frames/s), the
+      same pipeline without the RGB-D stages (monocular matcher), each new
+      kernel alone by HIP events with its algorithmic bytes + exact check
 
-Usage: python tools/bench_configs.py [--configs C1,C2,C3,C5,F1,F3,P1] [--steps K]
+Usage: python tools/bench_configs.py [--configs C1,C2,C3,C5,F1,F3,P1,R1] [--steps K]
 The oracle (CPU restatement) is used only for the CPU rows and parity checks.
 """
 import argparse
@@ -392,6 +398,160 @@ def p1(args, orb, oracle, torch):
             "alg_GBps_kernels": entries * 12 / (k_us * 1e-6) / 1e9, "bit_exact": bool(exact)}
 
 
+def r1(args, orb, oracle, torch):
+    import rgbd_ref
+    import scenarios
+    W, H, NF, B, M, U = 640, 480, 1000, 256, 3000, 16
+    K, D = scenarios.cameras()["tum1"]
+    fx, fy, cx, cy = float(K[0, 0]), float(K[1, 1]), float(K[0, 2]), float(K[1, 2])
+    bf, factor = np.float32(40.0), 1.0 / 5000.0
+    th_depth = np.float32(bf * np.float32(40.0) / np.float32(fx))  # ThDepth 40 (TUM1.yaml)
+    rng = np.random.default_rng(21)
+    imgs = np.stack([orb.synth_image(SEED + f % U, f // U, W, H) for f in range(U)])
+    # synthetic u16 depth: a slanted plane plus the frame's shapes, about 10 % zeros
+    yy, xx = np.mgrid[0:H, 0:W]
+    depth = np.stack([(5000 + 8 * xx + 12 * yy + 3000 * (imgs[f] > 128)).astype(np.uint16)
+                      for f in range(U)])
+    depth[rng.random(depth.shape) < 0.1] = 0
+    ext = orb.ORBextractor(NF, 1.2, 8, 20, 7)
+    mt = orb.ORBmatcher(0.8)
+    scale = np.float32(ext.GetScaleFactors())
+    cap = ext.capacity(W, H)
+    # the local maps: over each unique frame's undistorted keypoints, mTrackProjXR
+    # from the depth under the projection
+    mps = np.zeros((U, M), orb.MP_TRACK_DTYPE)
+    mpd = np.zeros((U, M, 32), np.uint8)
+    lk = np.zeros((U, cap), np.uint8)
+    host = []
+    for f in range(U):
+        k, d = ext(imgs[f])
+        un = mt.UndistortKeyPoints(k, K, D)
+        a, b, c = orb.synth_local_map(SEED + f, un, d, M, W, H)
+        px = np.clip(a["proj_x"].astype(np.int64), 0, W - 1)
+        py = np.clip(a["proj_y"].astype(np.int64), 0, H - 1)
+        z = depth[f][py, px].astype(np.float32) * np.float32(factor)
+        a["proj_xr"] = np.where(z > 0, a["proj_x"] - bf / np.where(z > 0, z, 1), a["proj_x"] - 20)
+        mps[f], mpd[f], lk[f, :len(k)] = a, b, c
+        host.append((k, d, un))
+    tile = lambda x: np.ascontiguousarray(np.concatenate([x] * (B // U)))
+    t = lambda x: torch.from_numpy(np.ascontiguousarray(x).view(np.uint8).reshape(-1)).cuda()
+    d_img, d_depth, d_mps, d_mpd, d_lk = (t(tile(x)) for x in (imgs, depth, mps, mpd, lk))
+    d_state = t(rng.choice(np.array([0, 1, 2], np.uint8), (B, cap), p=[0.2, 0.1, 0.7]))
+    d_outl = t((rng.random((B, cap)) < 0.05).astype(np.uint8))
+    poses = np.zeros(B, orb.POSE_DTYPE)
+    for f in range(B):
+        R, tt, ow = scenarios.pose(rng)
+        poses[f]["rcw"], poses[f]["tcw"], poses[f]["ow"] = R.reshape(9), tt, ow
+    d_pose = t(poses)
+    z8 = lambda n: torch.zeros(n, dtype=torch.uint8, device="cuda")
+    i32 = lambda n: torch.zeros(n, dtype=torch.int32, device="cuda")
+    f32 = lambda n: torch.zeros(n, dtype=torch.float32, device="cuda")
+    d_keys, d_un, d_desc, d_n = z8(B * cap * 28), z8(B * cap * 28), z8(B * cap * 32), i32(B)
+    d_ur, d_z, d_x3d, d_valid = f32(B * cap), f32(B * cap), f32(B * cap * 3), z8(B * cap)
+    d_order, d_create, d_counts = i32(B * cap), z8(B * cap), i32(B * 4)
+    d_nm = torch.full((B,), M, dtype=torch.int32, device="cuda")
+    d_km, d_nmatch = i32(B * cap), i32(B)
+    s = torch.cuda.Stream().cuda_stream
+    cam = (fx, fy, cx, cy, float(bf), float(bf) / fx)
+    P = lambda x: x.data_ptr()
+
+    def extract():
+        ext.extract_batch(P(d_img), B, W, H, W, W * H, P(d_keys), P(d_desc), cap, P(d_n), s)
+        mt.undistort_keypoints_batch(B, P(d_n), P(d_keys), cap, K, D, P(d_un), s)
+
+    def rgbd():
+        mt.stereo_from_rgbd_batch(B, P(d_n), P(d_keys), P(d_un), cap, P(d_depth),
+                                  orb.ORB_DEPTH_U16, W, H, W * 2, W * H * 2, factor, bf, P(d_ur),
+                                  P(d_z), s)
+
+    def close():
+        mt.close_points_batch(B, P(d_n), P(d_z), P(d_state), P(d_outl), cap, th_depth, P(d_order),
+                              P(d_create), P(d_counts), s)
+
+    def unproject():
+        mt.unproject_stereo_batch(B, P(d_n), P(d_un), P(d_z), cap, P(d_pose), cam, P(d_x3d),
+                                  P(d_valid), s)
+
+    def match_stereo():
+        mt.search_by_projection_batch_stereo(B, P(d_un), P(d_desc), P(d_ur), P(d_n), P(d_lk), cap,
+                                             P(d_mps), P(d_mpd), P(d_nm), M, W, H, scale, 3.0,
+                                             P(d_km), P(d_nmatch), s)
+
+    def match_mono():
+        mt.search_by_projection_batch(B, P(d_un), P(d_desc), P(d_n), P(d_lk), cap, P(d_mps),
+                                      P(d_mpd), P(d_nm), M, W, H, scale, 3.0, P(d_km),
+                                      P(d_nmatch), s)
+
+    def full():
+        extract(); rgbd(); close(); unproject(); match_stereo()
+
+    def mono():
+        extract(); match_mono()
+
+    steps = max(args.steps, 20)
+    sec_mono = timed(mono, steps, 3, torch)
+    sec_full = timed(full, steps, 3, torch)
+    # parity of frame 0 through the oracle and the restatement
+    k, d, un = host[0]
+    kr, dr, _ = oracle.extract(imgs[0], NF)
+    ur_ref, z_ref = rgbd_ref.stereo_from_rgbd(kr, oracle.undistort_keypoints(kr, K, D), depth[0],
+                                              factor, bf)
+    n0 = len(kr)
+    nr, kmr = oracle.match_projection_local(un, d, scale, W, H, mps[0], mpd[0], 3.0, 0.8,
+                                            lk[0, :n0], ur_ref)
+    h = lambda x, dt: x.cpu().numpy().view(dt)
+    order_ref, create_ref = rgbd_ref.close_points(z_ref, h(d_state, np.uint8)[:n0], th_depth)
+    cnt = h(d_counts, np.int32)[:4]
+    exact = (int(d_n[0].item()) == n0 and h(d_ur, np.float32)[:n0].tobytes() == ur_ref.tobytes()
+             and h(d_z, np.float32)[:n0].tobytes() == z_ref.tobytes()
+             and int(d_nmatch[0].item()) == nr and np.array_equal(h(d_km, np.int32)[:n0], kmr)
+             and cnt[0] == len(order_ref) and cnt[1] == len(create_ref)
+             and np.array_equal(h(d_order, np.int32)[:cnt[0]], order_ref))
+
+    cnts = h(d_counts, np.int32).reshape(B, 4)
+    means = {"mean_n_sorted": float(cnts[:, 0].mean()), "mean_n_visit": float(cnts[:, 1].mean()),
+             "mean_matches": float(h(d_nmatch, np.int32).mean())}
+
+    enqueue_us = {}  # the host's time to queue one call: a kernel shorter than this is
+    # timed at the host's pace, so its figure is an upper bound
+
+    def alone(fn, reps=50):
+        """microseconds per call by HIP events on the stream, after a warm-up"""
+        ts = torch.cuda.ExternalStream(s)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        for _ in range(5):
+            fn()
+        e0.record(ts)
+        t0 = time.perf_counter()
+        for _ in range(reps):
+            fn()
+        enqueue_us[fn.__name__] = (time.perf_counter() - t0) * 1e6 / reps
+        e1.record(ts)
+        e1.synchronize()
+        return e0.elapsed_time(e1) * 1e3 / reps
+
+    kp = int(d_n.sum().item())
+    slots = B * cap
+    # (2,000 launches of the short kernels: a timed window of tens of milliseconds)
+    us = {"k_stereo_from_rgbd": alone(rgbd, 2000), "k_unproject_stereo": alone(unproject, 2000),
+          "k_close_points": alone(close, 2000), "match_stereo": alone(match_stereo),
+          "match_mono": alone(match_mono)}
+    # algorithmic bytes: what each kernel must read and write per valid keypoint
+    # (rgbd: mvKeys x, y + mvKeysUn x + one u16 + two floats out; unproject: x, y,
+    # z + 13 out; close points: z, state, outlier in, order + create out per slot)
+    alg = {"k_stereo_from_rgbd": kp * (8 + 4 + 2 + 8), "k_unproject_stereo": kp * (8 + 4 + 13) + B * 60,
+           "k_close_points": kp * 6 + slots * 5 + B * 16}
+    return {"config": "R1", "workload": f"RGB-D 640x480 TUM1, DepthMapFactor 5000, {NF} feat, "
+            f"{B} frames per launch: extract -> undistort -> ComputeStereoFromRGBD -> close "
+            f"points + UnprojectStereo -> stereo SearchByProjection, {M}-point maps",
+            "unit": "frames/s", "value": B / sec_full, "ms_per_step": sec_full * 1e3,
+            "without_rgbd_stages_frames_per_s": B / sec_mono, "without_rgbd_ms_per_step": sec_mono * 1e3,
+            "kernel_us_isolated": us, "host_enqueue_us": enqueue_us, "alg_bytes": alg,
+            "alg_GBps": {k_: alg[k_] / (us[k_] * 1e-6) / 1e9 for k_ in alg},
+            "keypoints_per_launch": kp, "kp_stride": cap, "resolve_kernel": mt.resolve_kernel(B, cap, M),
+            "bit_exact_frame_0": bool(exact), **means}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--configs", default="C1,C2,C3,C5")
@@ -422,6 +582,8 @@ def main():
             r = f3(args, orb, oracle, torch)
         elif c == "P1":
             r = p1(args, orb, oracle, torch)
+        elif c == "R1":
+            r = r1(args, orb, oracle, torch)
         else:
             raise SystemExit(f"unknown config {c}")
         print(json.dumps(r), flush=True)
