@@ -784,6 +784,71 @@ orb_status_t orb_close_points_batch(orb_matcher_t* m, int n_frames, const int32_
 /* Largest keypoint-slot count (n, kp_stride) whose keys sort in LDS. */
 int orb_close_points_lds_keys(void);
 
+/* Optimizer::PoseOptimization (src/Optimizer.cc:243-477): the motion-only
+ * optimisation Tracking runs after each SearchByProjection and in
+ * Relocalization, one SE3 vertex and one unary edge per matched keypoint,
+ * with the g2o parts it reaches restated literally (four rounds that each
+ * restart from pose_in, Levenberg-Marquardt exactly as
+ * OptimizationAlgorithmLevenberg::solve writes it, the dense pivoted LDLT,
+ * Huber for the first three rounds, classification from the edges' last
+ * computed error).  k_pose_optimization, one launch.
+ * In: keys_un = mvKeysUn (pt and octave are read), u_right = mvuRight (NULL:
+ * monocular, every edge is a mono edge), point_index[i] >= 0 when
+ * mvpMapPoints[i] is non-null, its GetWorldPos() being the three floats at
+ * points + point_index[i] * point_stride_bytes (12 for packed float3, sizeof(
+ * orb_map_point_t) for the matchers' map points); inv_level_sigma2 =
+ * mvInvLevelSigma2 (n_levels <= 16 host floats); pose_in = mTcw.
+ * Out: pose_out = the pose SetPose receives, with ow as
+ * Frame::UpdatePoseMatrices computes it; outlier[i] = mvbOutlier[i] for the
+ * keypoints that have an edge, the other slots are left as they are;
+ * info->n_inliers = the return value (nInitialCorrespondences - nBad),
+ * n_edges = nInitialCorrespondences, lm_iterations = solve() calls,
+ * rejected_trials = the trials pop() undid.  Fewer than 3 edges: n_inliers = 0,
+ * pose_out = pose_in (the edges' flags are cleared).  An edge whose octave is
+ * outside [0, n_levels): n_edges = -1, n_inliers = 0, pose_out = pose_in,
+ * outlier untouched.  pose_out may be pose_in.
+ * Pinned arithmetic (double unless the reference says float; the numpy
+ * restatement tests/poseopt_ref.py states the same list): sin / cos of
+ * SE3Quat::exp by the double form of DESIGN.md App. A.6; pow(x, 3) = (x*x)*x;
+ * IEEE sqrt and division; every Eigen operation by its documented closed form
+ * with sums left to right (Quaterniond(Matrix3d), normalize, quaternion
+ * products, toRotationMatrix, 3x3 products, (A^T Omega) A and
+ * ((rho1 A^T) Omega) e with the zero terms of the diagonal Omega dropped,
+ * LDLT on the lower triangle with symmetric pivoting on the first largest
+ * |diagonal|); sums over edges in ascending keypoint order.  Unpinned against
+ * Eigen / g2o binaries.  Host buffers. */
+typedef struct orb_pose_opt_info {
+  int32_t n_inliers, n_edges, lm_iterations, rejected_trials;
+} orb_pose_opt_info_t;
+orb_status_t orb_pose_optimization(orb_matcher_t* m, int n, const orb_keypoint_t* keys_un,
+                                   const float* u_right, const int32_t* point_index,
+                                   const void* points, int point_stride_bytes,
+                                   const float* inv_level_sigma2, int n_levels,
+                                   const orb_camera_t* cam, const orb_pose_t* pose_in,
+                                   orb_pose_t* pose_out, uint8_t* outlier,
+                                   orb_pose_opt_info_t* info);
+/* Device-batched form: problem p reads d_nkeys[p] keypoints, u_right (NULL:
+ * monocular), point_index and outlier at p * kp_stride, its points at
+ * d_points + p * pt_stride * point_stride_bytes (pt_stride 0: the problems
+ * share one array), d_pose_in[p], and writes d_pose_out[p], d_info[p].
+ * orb_match_projection_local_batch[_stereo]'s d_kp_match, with the
+ * orb_map_point_t array orb_frustum_batch read for it (point_stride_bytes =
+ * sizeof(orb_map_point_t), pt_stride = mp_stride), feeds it unchanged.  inv_level_sigma2 and cam are host pointers.  kp_stride < 2^19;
+ * above orb_pose_optimization_lds_edges() slots the edge records live in the
+ * handle's device scratch.  Asynchronous on `stream`. */
+orb_status_t orb_pose_optimization_batch(orb_matcher_t* m, int n_problems,
+                                         const int32_t* d_nkeys,
+                                         const orb_keypoint_t* d_keys_un,
+                                         const float* d_u_right, int kp_stride,
+                                         const int32_t* d_point_index, const void* d_points,
+                                         int point_stride_bytes, long long pt_stride,
+                                         const float* inv_level_sigma2, int n_levels,
+                                         const orb_camera_t* cam, const orb_pose_t* d_pose_in,
+                                         orb_pose_t* d_pose_out, uint8_t* d_outlier,
+                                         orb_pose_opt_info_t* d_info, void* stream);
+/* Largest keypoint-slot count (n, kp_stride) whose edge records stay in LDS. */
+int orb_pose_optimization_lds_edges(void);
+
 /* ------------------------------------------------------ DBoW2 vocabulary */
 
 typedef struct orb_vocabulary orb_vocabulary_t;

@@ -48,6 +48,8 @@ MAP_POINT_DTYPE = np.dtype([("pos", "<f4", (3,)), ("normal", "<f4", (3,)), ("min
 POSE_DTYPE = np.dtype([("rcw", "<f4", (9,)), ("tcw", "<f4", (3,)), ("ow", "<f4", (3,))])
 CLOSE_COUNTS_DTYPE = np.dtype([("n_sorted", "<i4"), ("n_visit", "<i4"),
                                ("n_tracked_close", "<i4"), ("n_non_tracked_close", "<i4")])
+POSE_OPT_INFO_DTYPE = np.dtype([("n_inliers", "<i4"), ("n_edges", "<i4"),
+                                ("lm_iterations", "<i4"), ("rejected_trials", "<i4")])
 ORB_DEPTH_U16, ORB_DEPTH_F32 = 0, 1
 
 
@@ -197,6 +199,10 @@ def lib() -> ctypes.CDLL:
         "orb_close_points": (i32, [vp, i32, vp, vp, vp, f32, vp, vp, vp]),
         "orb_close_points_batch": (i32, [vp, i32, vp, vp, vp, vp, i32, f32, vp, vp, vp, vp]),
         "orb_close_points_lds_keys": (i32, []),
+        "orb_pose_optimization": (i32, [vp, i32, vp, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp]),
+        "orb_pose_optimization_batch": (i32, [vp, i32, vp, vp, vp, i32, vp, vp, i32, i64, vp, i32,
+                                              vp, vp, vp, vp, vp, vp]),
+        "orb_pose_optimization_lds_edges": (i32, []),
         "orb_synth_image": (None, [ctypes.c_uint64, i32, i32, i32, i32, vp, sz]),
         "orb_synth_local_map": (None, [ctypes.c_uint64, vp, vp, i32, i32, i32, i32, vp, vp, vp]),
     }
@@ -1057,6 +1063,64 @@ class ORBmatcher:
     def close_points_lds_keys() -> int:
         """Largest keypoint-slot count whose keys k_close_points sorts in LDS."""
         return lib().orb_close_points_lds_keys()
+
+    # ------------------------------------------------- Optimizer::PoseOptimization
+    def PoseOptimization(self, mvKeysUn, mvuRight, point_index, points, mvInvLevelSigma2, cam,
+                         pose, mvbOutlier=None):
+        """Optimizer::PoseOptimization (src/Optimizer.cc:243-477) for one frame.
+        point_index[i] >= 0 names the row of `points` ((m, 3) float32, or a
+        MAP_POINT_DTYPE array) that mvpMapPoints[i] holds; mvuRight None is
+        monocular.  Returns (n_inliers, pose POSE_DTYPE record, mvbOutlier
+        uint8, info POSE_OPT_INFO_DTYPE record); mvbOutlier slots without an
+        edge keep the value passed in (0 when none is)."""
+        un = np.ascontiguousarray(mvKeysUn, KEYPOINT_DTYPE)
+        n = len(un)
+        ur = None if mvuRight is None else np.ascontiguousarray(mvuRight, np.float32)
+        idx = np.ascontiguousarray(point_index, np.int32)
+        if len(idx) != n or (ur is not None and len(ur) != n):
+            raise OrbError(ORB_EINVAL, "mvKeysUn, mvuRight and point_index differ in length")
+        pts = np.ascontiguousarray(points)
+        if pts.dtype.fields is None:
+            pts = np.ascontiguousarray(pts, np.float32).reshape(-1, 3)
+            stride = 12
+        else:
+            stride = pts.dtype.itemsize
+        if n and idx.max(initial=-1) >= len(pts):
+            raise OrbError(ORB_EINVAL, "point_index names a point past the array")
+        lv = np.ascontiguousarray(mvInvLevelSigma2, np.float32)
+        pin = np.ascontiguousarray(pose, POSE_DTYPE).reshape(1)
+        pout = np.zeros(1, POSE_DTYPE)
+        ol = (np.zeros(n, np.uint8) if mvbOutlier is None
+              else np.array(mvbOutlier, np.uint8, copy=True))
+        if len(ol) != n:
+            raise OrbError(ORB_EINVAL, "mvbOutlier differs in length from mvKeysUn")
+        info = np.zeros(1, POSE_OPT_INFO_DTYPE)
+        c = self._camera(cam)
+        _check(lib().orb_pose_optimization(
+            self._h, n, _ptr(un) if n else None, _ptr(ur) if ur is not None and n else None,
+            _ptr(idx) if n else None, _ptr(pts) if len(pts) else None, stride, _ptr(lv), len(lv),
+            ctypes.addressof(c), _ptr(pin), _ptr(pout), _ptr(ol) if n else None, _ptr(info)),
+            "PoseOptimization")
+        return int(info[0]["n_inliers"]), pout[0], ol, info[0]
+
+    def pose_optimization_batch(self, n_problems, d_nkeys, d_keys_un, d_u_right, kp_stride,
+                                d_point_index, d_points, point_stride_bytes, pt_stride,
+                                inv_level_sigma2, cam, d_pose_in, d_pose_out, d_outlier, d_info,
+                                stream: int = 0):
+        """Device-batched PoseOptimization (orb_pose_optimization_batch); d_info
+        holds n_problems POSE_OPT_INFO_DTYPE records.  inv_level_sigma2 and cam
+        are host values."""
+        lv = np.ascontiguousarray(inv_level_sigma2, np.float32)
+        c = self._camera(cam)
+        _check(lib().orb_pose_optimization_batch(
+            self._h, n_problems, d_nkeys, d_keys_un, d_u_right or None, kp_stride, d_point_index,
+            d_points, point_stride_bytes, pt_stride, _ptr(lv), len(lv), ctypes.addressof(c),
+            d_pose_in, d_pose_out, d_outlier, d_info, stream or None), "pose_optimization_batch")
+
+    @staticmethod
+    def pose_optimization_lds_edges() -> int:
+        """Largest keypoint-slot count whose edge records k_pose_optimization keeps in LDS."""
+        return lib().orb_pose_optimization_lds_edges()
 
     # ------------------------------------------ MapPoint::ComputeDistinctiveDescriptors
     def ComputeDistinctiveDescriptors(self, obs_offs, obs_desc, descriptors=None):

@@ -70,6 +70,35 @@ __device__ __forceinline__ void pinned_sincos(float angle, float* s_out, float* 
   *c_out = __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, odd ? fs : fc) ^ sgnC);
 }
 
+// The double variant (SE3Quat::exp's sin(theta), cos(theta)):
+// the same reduction and kernels, returning the doubles before any narrowing.
+// (int)k saturates; a non-finite x gives NaN for both.
+__device__ __forceinline__ void pinned_sincos_d(double x, double* s_out, double* c_out) {
+  const double invpio2 = 6.36619772367581382433e-01;
+  const double pio2_1 = 1.57079632673412561417e+00, pio2_1t = 6.07710050650619224932e-11;
+  const double k = __builtin_rint(x * invpio2);
+  const double r = (x - k * pio2_1) - k * pio2_1t;
+  const double z = r * r;
+  const double S1 = -1.66666666666666324348e-01, S2 = 8.33333333332248946124e-03,
+               S3 = -1.98412698298579493134e-04, S4 = 2.75573137070700676789e-06,
+               S5 = -2.50507602534068634195e-08, S6 = 1.58969099521155010221e-10;
+  const double C1 = 4.16666666666666019037e-02, C2 = -1.38888888888741095749e-03,
+               C3 = 2.48015872894767294178e-05, C4 = -2.75573143513906633035e-07,
+               C5 = 2.08757232129817482790e-09, C6 = -1.13596475577881948265e-11;
+  const double ps = S2 + z * (S3 + z * (S4 + z * (S5 + z * S6)));
+  const double sn = r + (z * r) * (S1 + z * ps);
+  const double pc = z * (C1 + z * (C2 + z * (C3 + z * (C4 + z * (C5 + z * C6)))));
+  const double hz = 0.5 * z, w = 1.0 - hz;
+  const double cs = w + (((1.0 - w) - hz) + z * pc);
+  const double kc = k < -2147483648.0 ? -2147483648.0 : (k > 2147483647.0 ? 2147483647.0 : k);
+  const int q = (kc == kc ? (int)kc : 0) & 3;
+  // quadrant q: (s, c) = (sn, cs), (cs, -sn), (-sn, -cs), (-cs, sn)
+  const bool odd = q & 1;
+  const double a = odd ? cs : sn, b = odd ? sn : cs;
+  *s_out = (q & 2) ? -a : a;
+  *c_out = ((q + 1) & 2) ? -b : b;
+}
+
 // ------------------------------------------------ A.7 pinned log (double)
 // Natural log by the classic fdlibm scheme: x = 2^k (1+f) with 1+f in
 // [sqrt(2)/2, sqrt(2)), s = f/(2+f), log(1+f) = f - (hf - s (hf + R(s^2)))

@@ -177,3 +177,21 @@ struct PrQueryArgs {
   long long* out;
   int stage;  // -1: the whole query; 0..4: that kernel alone (isolated timing)
 };
+
+// --------------------------------------------------------- pose_kernels.hip
+// k_pose_optimization keeps up to this many 32-byte edge records in LDS (32 KiB
+// beside the 7.2 KiB term tile and 256 B for the sums: four workgroups per CU
+// at 1,000 slots); frames with more keypoint slots keep them in the handle's
+// device scratch
+#define PO_LDS_EDGES 1024
+
+// Optimizer::PoseOptimization over nProblems x stride keypoint slots (by value)
+struct PoseOptParams {
+  int nProblems, stride;
+  int nSingle;             // the keypoint count when there is no count array
+  int pointStrideBytes;    // bytes between two points (three floats each)
+  long long ptStride;      // points between two problems' point arrays
+  int nLevels;
+  float invLevelSigma2[ORB_MAX_LEVELS];  // mvInvLevelSigma2
+  float fx, fy, cx, cy, bf;
+};

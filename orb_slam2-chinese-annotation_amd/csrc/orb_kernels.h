@@ -194,4 +194,13 @@ hipError_t orb_k_close_points(int nFrames, const int32_t* counts, int nSingle, i
                               const float* depth, const uint8_t* mpState, const uint8_t* outlier,
                               float thDepth, int32_t* order, uint8_t* create,
                               orb_close_counts_t* out, void* scratch, hipStream_t s);
+// --------------------------------------------------------- pose_kernels.hip
+// bytes of global edge-record scratch a call needs (0: the records stay in LDS)
+size_t orb_k_pose_optimization_scratch(int nProblems, int stride);
+hipError_t orb_k_pose_optimization(const PoseOptParams* params, const int32_t* counts,
+                                   const orb_keypoint_t* keysUn, const float* uRight,
+                                   const int32_t* pointIndex, const void* points,
+                                   const orb_pose_t* poseIn, orb_pose_t* poseOut,
+                                   uint8_t* outlier, orb_pose_opt_info_t* info, void* scratch,
+                                   hipStream_t s);
 }

@@ -1399,6 +1399,8 @@ struct orb_matcher {
       dNcand, dKpMatch, dNMatch, dA, dB, dOut;
   DevBuf dJac;  // Jacobi-resolve scratch (ORB_RESOLVE_JACOBI)
   DevBuf dCpKeys;  // k_close_points' key scratch for frames above CP_LDS_KEYS slots
+  DevBuf dPoKeys, dPoUr, dPoIdx, dPoPts, dPoOut;  // orb_pose_optimization's staged frame
+  DevBuf dPoRecs;  // k_pose_optimization's edge records for frames above PO_LDS_EDGES slots
   DevBuf dOvf, dOvfCtr;  // candidate lists of SearchByProjection(F, localMap) (ProjParams.ovf)
   uint32_t ovfGen = 0;
   int stagedN = -1, stagedM = -1;  // orb_match_projection_local_stage's layout
@@ -3911,6 +3913,125 @@ orb_status_t orb_close_points_batch(orb_matcher_t* m, int n_frames, const int32_
   if (st) return st;
   HIP_TRY(orb_k_close_points(n_frames, d_n, 0, kp_stride, d_depth, d_mp_state, d_outlier,
                              th_depth, d_order, d_create, d_counts, m->dCpKeys.p, s));
+  return ORB_OK;
+}
+
+// Optimizer::PoseOptimization (src/Optimizer.cc:243-477); k_pose_optimization.
+int orb_pose_optimization_lds_edges(void) { return PO_LDS_EDGES; }
+
+static bool pose_opt_params(PoseOptParams& P, int nProblems, int stride, int nSingle,
+                            int pointStrideBytes, long long ptStride, const float* invLevelSigma2,
+                            int nLevels, const orb_camera_t* cam) {
+  if (!invLevelSigma2 || !cam || nLevels < 1 || nLevels > ORB_MAX_LEVELS ||
+      pointStrideBytes < 12 || (pointStrideBytes & 3) || ptStride < 0)
+    return false;
+  memset(&P, 0, sizeof(P));
+  P.nProblems = nProblems;
+  P.stride = stride;
+  P.nSingle = nSingle;
+  P.pointStrideBytes = pointStrideBytes;
+  P.ptStride = ptStride;
+  P.nLevels = nLevels;
+  for (int l = 0; l < nLevels; ++l) P.invLevelSigma2[l] = invLevelSigma2[l];
+  P.fx = cam->fx;
+  P.fy = cam->fy;
+  P.cx = cam->cx;
+  P.cy = cam->cy;
+  P.bf = cam->bf;
+  return true;
+}
+
+orb_status_t orb_pose_optimization(orb_matcher_t* m, int n, const orb_keypoint_t* keys_un,
+                                   const float* u_right, const int32_t* point_index,
+                                   const void* points, int point_stride_bytes,
+                                   const float* inv_level_sigma2, int n_levels,
+                                   const orb_camera_t* cam, const orb_pose_t* pose_in,
+                                   orb_pose_t* pose_out, uint8_t* outlier,
+                                   orb_pose_opt_info_t* info) {
+  PoseOptParams P;
+  if (!m || n < 0 || n >= (1 << 19) || !pose_in || !pose_out || !info ||
+      (n > 0 && (!keys_un || !point_index || !points || !outlier)) ||
+      point_stride_bytes < 12 || (point_stride_bytes & 3) ||
+      !pose_opt_params(P, 1, std::max(n, 1), n, 12, 0, inv_level_sigma2, n_levels, cam))
+    return ORB_EINVAL;
+  memset(info, 0, sizeof(*info));
+  if (n == 0) {
+    if (pose_out != pose_in) *pose_out = *pose_in;
+    return ORB_OK;
+  }
+  // the points the frame's edges name, packed in keypoint order
+  std::vector<float> pts((size_t)n * 3, 0.0f);
+  std::vector<int32_t> idx((size_t)n, -1);
+  for (int i = 0; i < n; ++i)
+    if (point_index[i] >= 0) {
+      memcpy(&pts[(size_t)i * 3],
+             (const uint8_t*)points + (size_t)point_index[i] * point_stride_bytes, 12);
+      idx[i] = i;
+    }
+  std::lock_guard<std::mutex> g(m->mu);
+  hipSetDevice(m->device);
+  hipStream_t s = m->stream;
+  CallOrder co(m->evLast, &m->lastStream, s);
+  if (co.status) return co.status;
+  orb_status_t st;
+  // dPoOut: pose in (64), pose out (64), info (16), outlier (n)
+  if ((st = upload(m->dPoKeys, keys_un, (size_t)n * sizeof(orb_keypoint_t), s)) ||
+      (u_right && (st = upload(m->dPoUr, u_right, (size_t)n * 4, s))) ||
+      (st = upload(m->dPoIdx, idx.data(), (size_t)n * 4, s)) ||
+      (st = upload(m->dPoPts, pts.data(), (size_t)n * 12, s)) ||
+      (st = m->dPoOut.ensure((size_t)n + 144)))
+    return st;
+  const size_t sb = orb_k_pose_optimization_scratch(1, n);
+  if (sb && (st = m->dPoRecs.ensure(sb))) return st;
+  uint8_t* d = m->dPoOut.as<uint8_t>();
+  orb_pose_t* dIn = (orb_pose_t*)d;
+  orb_pose_t* dOutPose = (orb_pose_t*)(d + 64);
+  orb_pose_opt_info_t* dInfo = (orb_pose_opt_info_t*)(d + 128);
+  uint8_t* dOutlier = d + 144;
+  HIP_TRY(hipMemcpyAsync(dIn, pose_in, sizeof(orb_pose_t), hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(dOutlier, outlier, (size_t)n, hipMemcpyHostToDevice, s));
+  HIP_TRY(orb_k_pose_optimization(&P, nullptr, m->dPoKeys.as<orb_keypoint_t>(),
+                                  u_right ? m->dPoUr.as<float>() : nullptr,
+                                  m->dPoIdx.as<int32_t>(), m->dPoPts.p, dIn, dOutPose, dOutlier,
+                                  dInfo, sb ? m->dPoRecs.p : nullptr, s));
+  HIP_TRY(hipMemcpyAsync(pose_out, dOutPose, sizeof(orb_pose_t), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(outlier, dOutlier, (size_t)n, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(info, dInfo, sizeof(*info), hipMemcpyDeviceToHost, s));
+  HIP_TRY(stream_wait(s));
+  co.settled();
+  return ORB_OK;
+}
+
+orb_status_t orb_pose_optimization_batch(orb_matcher_t* m, int n_problems,
+                                         const int32_t* d_nkeys,
+                                         const orb_keypoint_t* d_keys_un,
+                                         const float* d_u_right, int kp_stride,
+                                         const int32_t* d_point_index, const void* d_points,
+                                         int point_stride_bytes, long long pt_stride,
+                                         const float* inv_level_sigma2, int n_levels,
+                                         const orb_camera_t* cam, const orb_pose_t* d_pose_in,
+                                         orb_pose_t* d_pose_out, uint8_t* d_outlier,
+                                         orb_pose_opt_info_t* d_info, void* stream) {
+  PoseOptParams P;
+  if (!m || n_problems < 0 || kp_stride <= 0 || kp_stride >= (1 << 19) ||
+      !pose_opt_params(P, n_problems, kp_stride, 0, point_stride_bytes, pt_stride,
+                       inv_level_sigma2, n_levels, cam))
+    return ORB_EINVAL;
+  if (n_problems == 0) return ORB_OK;
+  if (!d_nkeys || !d_keys_un || !d_point_index || !d_points || !d_pose_in || !d_pose_out ||
+      !d_outlier || !d_info)
+    return ORB_EINVAL;
+  std::lock_guard<std::mutex> g(m->mu);
+  hipSetDevice(m->device);
+  hipStream_t s = stream ? (hipStream_t)stream : m->stream;
+  CallOrder co(m->evLast, &m->lastStream, s);
+  if (co.status) return co.status;
+  const size_t sb = orb_k_pose_optimization_scratch(n_problems, kp_stride);
+  orb_status_t st;
+  if (sb && (st = m->dPoRecs.ensure(sb))) return st;
+  HIP_TRY(orb_k_pose_optimization(&P, d_nkeys, d_keys_un, d_u_right, d_point_index, d_points,
+                                  d_pose_in, d_pose_out, d_outlier, d_info,
+                                  sb ? m->dPoRecs.p : nullptr, s));
   return ORB_OK;
 }
 

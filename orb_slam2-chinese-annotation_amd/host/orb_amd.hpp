@@ -766,6 +766,24 @@ class ORBmatcher {
           "search_by_projection_batch_stereo");
   }
 
+  // Device-batched Optimizer::PoseOptimization (orb_pose_optimization_batch):
+  // d_point_index / d_points as orb_match_projection_local_batch's d_kp_match
+  // and the orb_map_point_t array (or packed float3 at stride 12).
+  void pose_optimization_batch(int n_problems, const int32_t* d_nkeys, const KeyPoint* d_keys_un,
+                               const float* d_u_right, int kp_stride,
+                               const int32_t* d_point_index, const void* d_points,
+                               int point_stride_bytes, long long pt_stride,
+                               const std::vector<float>& mvInvLevelSigma2,
+                               const orb_camera_t& cam, const orb_pose_t* d_pose_in,
+                               orb_pose_t* d_pose_out, uint8_t* d_outlier,
+                               orb_pose_opt_info_t* d_info, void* stream = nullptr) {
+    check(orb_pose_optimization_batch(h_, n_problems, d_nkeys, d_keys_un, d_u_right, kp_stride,
+                                      d_point_index, d_points, point_stride_bytes, pt_stride,
+                                      mvInvLevelSigma2.data(), (int)mvInvLevelSigma2.size(), &cam,
+                                      d_pose_in, d_pose_out, d_outlier, d_info, stream),
+          "pose_optimization_batch");
+  }
+
   float mfNNratio;
   bool mbCheckOrientation;
   orb_matcher_t* handle() { return h_; }
@@ -777,6 +795,46 @@ class ORBmatcher {
     return a;
   }
   orb_matcher_t* h_ = nullptr;
+};
+
+// The Frame members Optimizer::PoseOptimization reads and writes
+// (src/Optimizer.cc:243-477).  mvpMapPoints[i] >= 0 names the MapPoint of
+// keypoint i: its GetWorldPos() is the three floats at
+// points + mvpMapPoints[i] * pointStrideBytes (12 for packed float3,
+// sizeof(orb_map_point_t) for map-point records); -1 is a null pointer.
+struct PoseFrame {
+  const std::vector<KeyPoint>* mvKeysUn = nullptr;
+  const std::vector<float>* mvuRight = nullptr;  // null: monocular
+  const std::vector<int32_t>* mvpMapPoints = nullptr;
+  const void* points = nullptr;
+  int pointStrideBytes = 12;
+  const std::vector<float>* mvInvLevelSigma2 = nullptr;
+  orb_camera_t cam{};
+  orb_pose_t mTcw{};                // in: the start pose; out: what SetPose receives
+  std::vector<uint8_t> mvbOutlier;  // written for the keypoints that have a MapPoint
+  orb_pose_opt_info_t info{};       // n_edges, lm_iterations, rejected_trials of the last call
+};
+
+class Optimizer {
+ public:
+  // int Optimizer::PoseOptimization(Frame* pFrame): returns nInitialCorrespondences - nBad
+  // (0 with fewer than 3 correspondences, pose untouched) and writes mTcw and
+  // mvbOutlier.  An octave outside mvInvLevelSigma2 leaves info.n_edges = -1.
+  static int PoseOptimization(ORBmatcher& matcher, PoseFrame* pFrame) {
+    PoseFrame& F = *pFrame;
+    const size_t n = F.mvKeysUn->size();
+    assert(F.mvpMapPoints->size() == n && (!F.mvuRight || F.mvuRight->size() == n));
+    F.mvbOutlier.resize(n, 0);
+    orb_pose_t out{};
+    check(orb_pose_optimization(
+              matcher.handle(), (int)n, F.mvKeysUn->data(),
+              F.mvuRight ? F.mvuRight->data() : nullptr, F.mvpMapPoints->data(), F.points,
+              F.pointStrideBytes, F.mvInvLevelSigma2->data(), (int)F.mvInvLevelSigma2->size(),
+              &F.cam, &F.mTcw, &out, F.mvbOutlier.data(), &F.info),
+          "PoseOptimization");
+    F.mTcw = out;
+    return F.info.n_inliers;
+  }
 };
 
 }  // namespace orb_amd

@@ -28,6 +28,11 @@ results table:
       4,096 keyframes of about 1,000 words each on an ORBvoc-shaped synthetic
       vocabulary (k 10, L 6), one query per call (queries/s), each kernel's
       isolated time, bytes/s against 12 B per database entry + exact check
+  T1  Optimizer::PoseOptimization: 1,024 problems of the C4 shape per launch
+      (1,000 keypoints, about 800 edges, mono and stereo mixed, 1 px noise,
+      20 % gross outliers), device-resident (problems/s by device events), the
+      one-problem latency through the host-buffer call, the batch's share of
+      the headline step + exact check against tests/poseopt_ref.py
   R1  RGB-D: 640x480 (TUM1 intrinsics and distortion, DepthMapFactor 5000),
       1000 features, 256 frames per launch, device-resident: extract ->
       undistort -> ComputeStereoFromRGBD -> closest points + UnprojectStereo ->
@@ -35,7 +40,7 @@ results table:
       same pipeline without the RGB-D stages (monocular matcher), each new
       kernel alone by HIP events with its algorithmic bytes + exact check
 
-Usage: python tools/bench_configs.py [--configs C1,C2,C3,C5,F1,F3,P1,R1] [--steps K]
+Usage: python tools/bench_configs.py [--configs C1,C2,C3,C5,F1,F3,P1,R1,T1] [--steps K]
 The oracle (CPU restatement) is used only for the CPU rows and parity checks.
 """
 import argparse
@@ -552,6 +557,101 @@ def r1(args, orb, oracle, torch):
             "bit_exact_frame_0": bool(exact), **means}
 
 
+def t1(args, orb, oracle, torch):
+    import poseopt_cases as pc
+    B, NKP, NE, DISTINCT = 1024, 1000, 800, 128
+    cases = [pc.make_case(9000 + i, NKP, NE + (i * 7) % 41 - 20, "mixed", 1.0, 0.2)
+             for i in range(DISTINCT)]
+    keys = np.zeros((B, NKP), orb.KEYPOINT_DTYPE)
+    ur = np.full((B, NKP), -1, np.float32)
+    idx = np.full((B, NKP), -1, np.int32)
+    poses = np.zeros(B, orb.POSE_DTYPE)
+    npts = max(len(c["points"]) for c in cases)
+    pts = np.zeros((B, npts, 3), np.float32)
+    for p in range(B):  # (the distinct problems repeat 8 times across the batch)
+        c = cases[p % DISTINCT]
+        keys[p], ur[p], idx[p], poses[p] = c["keys"], c["u_right"], c["point_index"], c["pose"][0]
+        pts[p, :len(c["points"])] = c["points"]
+
+    def dev(a):
+        return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).cuda()
+    d_keys, d_ur, d_idx, d_pin, d_pts = (dev(a) for a in (keys, ur, idx, poses, pts))
+    d_nk = torch.full((B,), NKP, dtype=torch.int32, device="cuda")
+    d_pout = torch.zeros(B * orb.POSE_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
+    d_outl = torch.zeros(B * NKP, dtype=torch.uint8, device="cuda")
+    d_info = torch.zeros(B * 4, dtype=torch.int32, device="cuda")
+    m = orb.ORBmatcher()
+    stream = torch.cuda.Stream()  # the launch and its events on one stream
+
+    def run(nprob=B):
+        m.pose_optimization_batch(nprob, d_nk.data_ptr(), d_keys.data_ptr(), d_ur.data_ptr(), NKP,
+                                  d_idx.data_ptr(), d_pts.data_ptr(), 12, npts,
+                                  pc.INV_LEVEL_SIGMA2, pc.CAM, d_pin.data_ptr(), d_pout.data_ptr(),
+                                  d_outl.data_ptr(), d_info.data_ptr(), stream=stream.cuda_stream)
+    for _ in range(2):
+        run()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(max(args.steps, 5)):  # device events around each launch
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(stream)
+        run()
+        e1.record(stream)
+        torch.cuda.synchronize()
+        ms.append(e0.elapsed_time(e1))
+    ms.sort()
+    batch_ms = ms[len(ms) // 2]
+    wall_ms = timed(run, max(args.steps, 5), 1, torch) * 1e3  # host clock, back-to-back launches
+    by_size = {}
+    for nprob in (1, 64, 256, 768):  # how the launch scales with the problems in flight
+        t = []
+        for _ in range(5):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            run(nprob)
+            e1.record(stream)
+            torch.cuda.synchronize()
+            t.append(e0.elapsed_time(e1))
+        by_size[str(nprob)] = sorted(t)[2]
+    run()
+    torch.cuda.synchronize()
+    info = d_info.cpu().numpy().view(orb.POSE_OPT_INFO_DTYPE)
+    pout = d_pout.cpu().numpy().view(orb.POSE_DTYPE)
+    outl = d_outl.cpu().numpy().reshape(B, NKP)
+    exact = True
+    for p in (0, 1, DISTINCT + 1, B - 1):
+        r = pc.run_ref(cases[p % DISTINCT])
+        want = np.where(cases[p % DISTINCT]["point_index"] >= 0, r["outlier"], 0)
+        exact &= (tuple(int(v) for v in info[p]) ==
+                  (r["n_inliers"], r["n_edges"], r["lm_iterations"], r["rejected_trials"]))
+        exact &= all(pout[p][k].tobytes() == r[k].tobytes() for k in ("rcw", "tcw", "ow"))
+        exact &= bool(np.array_equal(outl[p], want))
+    # one problem through the host-buffer call (upload, launch, download, wait)
+    c = cases[0]
+    one = lambda: m.PoseOptimization(c["keys"], c["u_right"], c["point_index"], c["points"],
+                                     pc.INV_LEVEL_SIGMA2, pc.CAM, c["pose"])
+    for _ in range(5):
+        one()
+    lat = []
+    for _ in range(50):
+        t0 = time.perf_counter()
+        one()
+        lat.append((time.perf_counter() - t0) * 1e3)
+    lat.sort()
+    headline_ms = 2.9  # the headline step per 1,024 frames
+    return {"config": "T1", "workload": f"PoseOptimization, {B} problems x {NKP} keypoints, "
+            f"{int(info['n_edges'].mean())} edges on average, mixed mono / stereo, 1 px noise, "
+            f"20% outliers ({DISTINCT} distinct problems)",
+            "batch_ms_median": batch_ms, "batch_ms_min": ms[0], "batch_ms_max": ms[-1],
+            "batch_ms_host_clock": wall_ms, "launch_ms_by_problems": by_size, "problems_per_s": B / (batch_ms * 1e-3),
+            "one_problem_latency_ms_median": lat[len(lat) // 2], "one_problem_latency_ms_min": lat[0],
+            "lm_iterations_mean": float(info["lm_iterations"].mean()),
+            "rejected_trials_mean": float(info["rejected_trials"].mean()),
+            "inliers_mean": float(info["n_inliers"].mean()),
+            "share_of_headline_step": batch_ms / headline_ms, "headline_step_ms": headline_ms,
+            "lds_edges": m.pose_optimization_lds_edges(), "bit_exact_4_problems": bool(exact)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--configs", default="C1,C2,C3,C5")
@@ -584,6 +684,8 @@ def main():
             r = p1(args, orb, oracle, torch)
         elif c == "R1":
             r = r1(args, orb, oracle, torch)
+        elif c == "T1":
+            r = t1(args, orb, oracle, torch)
         else:
             raise SystemExit(f"unknown config {c}")
         print(json.dumps(r), flush=True)
