@@ -491,7 +491,13 @@ orb_status_t orb_stereo_match_extracted(orb_matcher_t* m, orb_extractor_t* left_
  * as src/ORBmatcher.cc:1500-1505).  valid[i]=0 for NULL or outlier entries.
  * kp_match[i] (out) = MapPoint id assigned to current keypoint i by this call,
  * -1 untouched, -2 reset to NULL by the rotation-consistency filter
- * (src/ORBmatcher.cc:1597-1616). */
+ * (src/ORBmatcher.cc:1597-1616).
+ * Capacity: the replay runs in one workgroup, whose LDS (160 KiB of one CU)
+ * holds, with N = current->n and W = ceil(N / 32), both rounded up to a
+ * multiple of 4,
+ *   4 * (W + 2 * N + max(n_last, 1)) + 128 bytes <= 163840,
+ * else ORB_ECAPACITY, returned before anything is launched (outputs: all -1,
+ * *nmatches 0).  E.g. N = 12000 admits n_last <= 16552. */
 typedef struct orb_last_mp {
   float xc, yc, invzc;          /* Rcw*x3Dw + tcw, 1/z */
   int32_t last_octave;          /* LastFrame.mvKeys[i].octave */
@@ -569,7 +575,15 @@ orb_status_t orb_distinctive_descriptors_batch(orb_matcher_t* m, int n_mp,
  * orb_map_point_t; its `seen` flag marks the variant's "already found" set
  * (documented per call).  Host buffers; log_scale_factor = mfLogScaleFactor;
  * KeyFrame bounds come from the orb_frame_t (KeyFrame::IsInImage is
- * half-open, Frame bounds closed, as in the reference). */
+ * half-open, Frame bounds closed, as in the reference).
+ * Capacity of the two variants that claim keypoints
+ * (orb_search_by_projection_reloc, orb_search_by_projection_sim3): their
+ * first-come replay runs in one workgroup, whose LDS (160 KiB of one CU)
+ * holds, with N = the frame's keypoints and W = ceil(N / 32), both rounded up
+ * to a multiple of 4,
+ *   4 * (W + N + max(n_mp, 1)) + 128 bytes <= 163840,
+ * else ORB_ECAPACITY, returned before anything is launched (kp_match all -1,
+ * kp_matched as on entry, *nmatches 0).  E.g. N = 20000 admits n_mp <= 20300. */
 
 /* SearchByProjection(Frame& F, KeyFrame* pKF, sAlreadyFound, th, ORBdist),
  * src/ORBmatcher.cc:1622-1759 (Tracking::Relocalization).  Point i = the

@@ -678,7 +678,10 @@ class ORBmatcher:
     def SearchByProjectionFrame(self, current: Frame, last, last_desc, cam, tlc_z: float,
                                 th: float, bMono: bool, kp_locked=None):
         """SearchByProjection(CurrentFrame, LastFrame, th, bMono): (nmatches, kp_match).
-        kp_match: MapPoint id assigned, -1 untouched, -2 reset by the rotation filter."""
+        kp_match: MapPoint id assigned, -1 untouched, -2 reset by the rotation filter.
+        Limit: 4 * (W + 2 * N + max(len(last), 1)) + 128 bytes must fit 160 KiB
+        (N = current.N, W = ceil(N / 32), both rounded up to 4), else OrbError
+        with ORB_ECAPACITY and nothing is launched."""
         last = np.ascontiguousarray(last, LAST_MP_DTYPE)
         last_desc = np.ascontiguousarray(last_desc, np.uint8).reshape(-1, 32)
         locked = None if kp_locked is None else np.ascontiguousarray(kp_locked, np.uint8)
@@ -749,7 +752,10 @@ class ORBmatcher:
     def SearchByProjectionKF(self, F: Frame, pose, cam, logScaleFactor: float, mps, mp_desc,
                              kf_angle, th: float, ORBdist: int, kp_locked=None):
         """SearchByProjection(F, pKF, sAlreadyFound, th, ORBdist) (src/ORBmatcher.cc:1622-1759):
-        (nmatches, kp_match) -- point index per frame keypoint, -1 none, -2 reset."""
+        (nmatches, kp_match) -- point index per frame keypoint, -1 none, -2 reset.
+        Limit (also of SearchByProjectionSim3): 4 * (W + N + max(len(mps), 1)) + 128
+        bytes must fit 160 KiB (N = F.N, W = ceil(N / 32), both rounded up to 4),
+        else OrbError with ORB_ECAPACITY and nothing is launched."""
         mps = self._mps(mps)
         md = np.ascontiguousarray(mp_desc, np.uint8).reshape(-1, 32)
         ka = np.ascontiguousarray(kf_angle, np.float32)

@@ -2072,6 +2072,7 @@ __global__ __launch_bounds__(64) void k_frame_resolve(
   // point assigned to each keypoint, the accepted keypoint of each point
   extern __shared__ __attribute__((aligned(16))) uint32_t dyn[];
   __shared__ int hist[32];
+  static_assert(sizeof(hist) == ORB_RESOLVE_STATIC_LDS, "capacity rule counts hist[]");
   const int lane = threadIdx.x;
   const int words = (nkeys + 31) >> 5;
   const int wpad = (words + 3) & ~3, npad = (nkeys + 3) & ~3;
@@ -2205,6 +2206,14 @@ __global__ __launch_bounds__(64) void k_frame_resolve(
   if (lane == 0) *nmatches = acc - rem;
 }
 
+// LDS of one k_frame_resolve block: lock bits, claimBy and lastWriter per
+// keypoint, accIdx per point, plus the kernel's static hist[32].
+extern "C" size_t orb_k_frame_resolve_lds(int nkeys, int nlast) {
+  const size_t words = (size_t)((nkeys + 31) / 32);
+  return (((words + 3) & ~(size_t)3) + 2 * (((size_t)nkeys + 3) & ~(size_t)3) +
+          (size_t)std::max(nlast, 1)) * 4 + ORB_RESOLVE_STATIC_LDS;
+}
+
 extern "C" hipError_t orb_k_frame_proj(const orb_keypoint_t* keys, const uint8_t* desc,
                                        const float* uright, const uint8_t* locked, int nkeys,
                                        const orb_last_mp_t* last, const uint8_t* lastDesc,
@@ -2213,6 +2222,8 @@ extern "C" hipError_t orb_k_frame_proj(const orb_keypoint_t* keys, const uint8_t
                                        uint32_t* topk, int32_t* ncand, int32_t* kpMatch,
                                        int32_t* nmatches, hipStream_t s) {
   const FrameProjParams F = *params;
+  const size_t total = orb_k_frame_resolve_lds(nkeys, nlast);
+  if (total > ORB_LDS_PER_CU) return hipErrorInvalidValue;  // nothing is launched
   if (nlast > 0) {
     hipLaunchKernelGGL(k_frame_candidates, dim3((nlast + 255) / 256), dim3(256), 0, s, keys,
                        desc, uright, locked, last, lastDesc, nlast, cellStart, cellIdx, F, topk,
@@ -2220,10 +2231,7 @@ extern "C" hipError_t orb_k_frame_proj(const orb_keypoint_t* keys, const uint8_t
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
   }
-  const size_t words = (size_t)((nkeys + 31) / 32);
-  const size_t lds = (((words + 3) & ~(size_t)3) + 2 * (((size_t)nkeys + 3) & ~(size_t)3) +
-                      (size_t)std::max(nlast, 1)) * 4;
-  if (lds > 160 * 1024) return hipErrorInvalidValue;
+  const size_t lds = total - ORB_RESOLVE_STATIC_LDS;  // dynamic part
   if (lds > 65536) {
     hipError_t e = hipFuncSetAttribute((const void*)k_frame_resolve,
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);

@@ -96,6 +96,12 @@ hipError_t orb_k_stereo(const orb_keypoint_t* lkeys, const uint8_t* ldesc, const
                         int kpStride, int maxLeft, const StereoPairLevels* pyr,
                         const StereoParams* params, float* uRight, float* depth, int32_t* sad,
                         int npairs, int32_t* rowStart, int32_t* rowIdx, hipStream_t s);
+// Capacity rule of the one-block resolve kernels (k_frame_resolve,
+// k_pp_resolve): dynamic LDS + the kernel's static hist[32] must fit one CU.
+// orb_k_*_resolve_lds return that total; a call fits iff it is <= ORB_LDS_PER_CU.
+#define ORB_LDS_PER_CU ((size_t)160 * 1024)
+#define ORB_RESOLVE_STATIC_LDS ((size_t)128)
+size_t orb_k_frame_resolve_lds(int nkeys, int nlast);
 hipError_t orb_k_frame_proj(const orb_keypoint_t* keys, const uint8_t* desc, const float* uright,
                             const uint8_t* locked, int nkeys, const orb_last_mp_t* last,
                             const uint8_t* lastDesc, int nlast, const int32_t* cellStart,

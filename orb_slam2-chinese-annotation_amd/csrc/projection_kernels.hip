@@ -190,6 +190,7 @@ __global__ __launch_bounds__(64) void k_pp_resolve(
     int32_t* __restrict__ kpMatch, int32_t* __restrict__ nmatches) {
   extern __shared__ __attribute__((aligned(16))) uint32_t dyn[];
   __shared__ int hist[32];
+  static_assert(sizeof(hist) == ORB_RESOLVE_STATIC_LDS, "capacity rule counts hist[]");
   const int lane = threadIdx.x;
   const int words = (nkeys + 31) >> 5;
   const int wpad = (words + 3) & ~3;
@@ -456,10 +457,13 @@ extern "C" hipError_t orb_k_pp_match(int mode, const orb_map_point_t* mps, const
   return hipGetLastError();
 }
 
+// LDS of one k_pp_resolve block: the dynamic arrays (lock bits, claimBy per
+// keypoint, accIdx per point) plus the kernel's static hist[32]
+// (ORB_RESOLVE_STATIC_LDS).  The call fits iff this is <= ORB_LDS_PER_CU.
 extern "C" size_t orb_k_pp_resolve_lds(int nkeys, int n) {
   const size_t words = (size_t)((nkeys + 31) / 32);
   return (((words + 3) & ~(size_t)3) + (((size_t)nkeys + 3) & ~(size_t)3) +
-          (size_t)std::max(n, 1)) * 4;
+          (size_t)std::max(n, 1)) * 4 + ORB_RESOLVE_STATIC_LDS;
 }
 
 extern "C" hipError_t orb_k_pp_resolve(const orb_keypoint_t* keys, const uint8_t* desc,
@@ -470,8 +474,9 @@ extern "C" hipError_t orb_k_pp_resolve(const orb_keypoint_t* keys, const uint8_t
                                        const int32_t* ncand, int32_t* kpMatch,
                                        int32_t* nmatches, hipStream_t s) {
   const PPParams P = *params;
-  const size_t lds = orb_k_pp_resolve_lds(nkeys, n);
-  if (lds > 160 * 1024) return hipErrorInvalidValue;
+  const size_t total = orb_k_pp_resolve_lds(nkeys, n);
+  if (total > ORB_LDS_PER_CU) return hipErrorInvalidValue;
+  const size_t lds = total - ORB_RESOLVE_STATIC_LDS;  // dynamic part
   if (lds > 65536) {
     hipError_t e = hipFuncSetAttribute((const void*)k_pp_resolve,
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);

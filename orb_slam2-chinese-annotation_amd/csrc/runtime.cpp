@@ -2213,6 +2213,8 @@ orb_status_t orb_match_projection_frame(orb_matcher_t* m, const orb_frame_t* C,
   *nmatches = 0;
   for (int i = 0; i < C->n; ++i) kp_match[i] = -1;
   if (C->n == 0) return ORB_OK;
+  // k_frame_resolve is one block: its LDS must fit one CU (checked before any launch)
+  if (orb_k_frame_resolve_lds(C->n, n_last) > ORB_LDS_PER_CU) return ORB_ECAPACITY;
   std::lock_guard<std::mutex> g(m->mu);
   hipSetDevice(m->device);
   hipStream_t s = m->stream;
@@ -2571,8 +2573,6 @@ static orb_status_t pp_run(orb_matcher_t* m, int mode, const PPParams& P, int sl
                          f.cellidx(), &P, b[PP_RECS].as<PPRec>(), best, b[PP_TOPK].as<uint32_t>(),
                          b[PP_NCAND].as<int32_t>(), s));
   if (claims) {
-    const size_t lds = orb_k_pp_resolve_lds(K->n, n_mp);
-    if (lds > 160 * 1024) return ORB_ECAPACITY;
     if (kpLocked && (st = upload(b[PP_LOCKED], kpLocked, (size_t)K->n, s))) return st;
     if ((st = upload(b[PP_KPMATCH], kp_match_host, (size_t)K->n * 4, s))) return st;
     if ((st = b[PP_COUNT].ensure(16))) return st;
@@ -2617,6 +2617,8 @@ orb_status_t orb_search_by_projection_reloc(orb_matcher_t* m, const orb_frame_t*
   *nmatches = 0;
   for (int j = 0; j < frame->n; ++j) kp_match[j] = -1;
   if (frame->n == 0 || n_mp == 0) return ORB_OK;
+  // k_pp_resolve is one block: its LDS must fit one CU (checked before any launch)
+  if (orb_k_pp_resolve_lds(frame->n, n_mp) > ORB_LDS_PER_CU) return ORB_ECAPACITY;
   std::lock_guard<std::mutex> g(m->mu);
   hipSetDevice(m->device);
   hipStream_t s = m->stream;
@@ -2640,6 +2642,7 @@ orb_status_t orb_search_by_projection_sim3(orb_matcher_t* m, const orb_frame_t* 
   sim3_normalise(scw, P.R, P.t, P.Ow);
   *nmatches = 0;
   if (kf->n == 0 || n_mp == 0) return ORB_OK;
+  if (orb_k_pp_resolve_lds(kf->n, n_mp) > ORB_LDS_PER_CU) return ORB_ECAPACITY;
   std::lock_guard<std::mutex> g(m->mu);
   hipSetDevice(m->device);
   hipStream_t s = m->stream;

@@ -373,6 +373,9 @@ class ORBmatcher {
   }
 
   // SearchByProjection(CurrentFrame, LastFrame, th, bMono) -- src/ORBmatcher.cc:1460-1619.
+  // Limit (ORB_ECAPACITY, nothing launched): with N = current.N() and
+  // W = ceil(N / 32), both rounded up to 4,
+  // 4 * (W + 2 * N + max(last.size(), 1)) + 128 bytes must fit 160 KiB.
   int SearchByProjection(const FrameView& current, const std::vector<orb_last_mp_t>& last,
                          const std::vector<uint8_t>& lastDescriptors, const orb_camera_t& cam,
                          float tlc_z, float th, bool bMono, std::vector<int32_t>& mvpMapPoints,
@@ -547,6 +550,9 @@ class ORBmatcher {
 
   // SearchByProjection(Frame& F, KeyFrame* pKF, sAlreadyFound, th, ORBdist),
   // src/ORBmatcher.cc:1622-1759: kpMatch[j] = point assigned, -1 none, -2 reset.
+  // Limit of this overload and the Scw one below (ORB_ECAPACITY, nothing
+  // launched): with N = F.N() and W = ceil(N / 32), both rounded up to 4,
+  // 4 * (W + N + max(mps.size(), 1)) + 128 bytes must fit 160 KiB.
   int SearchByProjection(const FrameView& F, const std::vector<uint8_t>& locked,
                          const orb_pose_t& pose, const orb_camera_t& cam, float logScaleFactor,
                          const std::vector<orb_map_point_t>& mps,

@@ -373,15 +373,18 @@ def _rot_bin(a1, a2):
     return 0 if b == 30 else b
 
 
-def _three_maxima(counts):
+def _three_maxima(counts, ge=False):
+    """ComputeThreeMaxima (src/ORBmatcher.cc:1761-1807).  `ge` switches the scan's
+    strict `s > max` to the wrong neighbour `s >= max` (sensitivity tests only)."""
     m1 = m2 = m3 = 0
     i1 = i2 = i3 = -1
+    over = (lambda s, m: s >= m) if ge else (lambda s, m: s > m)
     for i, s in enumerate(counts):
-        if s > m1:
+        if over(s, m1):
             m3, m2, m1, i3, i2, i1 = m2, m1, s, i2, i1, i
-        elif s > m2:
+        elif over(s, m2):
             m3, m2, i3, i2 = m2, s, i2, i
-        elif s > m3:
+        elif over(s, m3):
             m3, i3 = s, i
     if m2 < f32(0.1) * f32(m1):
         i2 = i3 = -1
@@ -486,33 +489,59 @@ def _sim3_pose(S):
     return R, t, ow
 
 
-def _in_kf(x, y, w, h):
+# Rule switches (sensitivity tests only).  Every restatement below takes
+# `rules`, a collection of names of WRONG neighbours of a reference rule; the
+# default, no names, is the reference.
+#   th_strict  the distance threshold's <= becomes < (or < becomes <=)
+#   tie_flip   first minimum becomes last minimum on ties (or last becomes first)
+#   top4       a point whose TOPK nearest candidates are all locked gets no match
+#   stereo_flip  u_right >= 0 becomes > 0 (or > 0 becomes >= 0)
+#   bounds_flip  half-open image bounds become closed (or closed become half-open)
+#   hist_ge    ComputeThreeMaxima scans with s >= max
+#   no_claims  claims inside a vocabulary node are ignored
+TOPK = 4  # matcher_common.h TOPK: candidates the device keeps per point
+
+
+def _in_kf(x, y, w, h, closed=False):
+    if closed:
+        return 0 <= x <= w and 0 <= y <= h
     return 0 <= x < w and 0 <= y < h
 
 
+def _out_frame(u, v, w, h, half_open=False):
+    if half_open:
+        return u < 0 or u >= w or v < 0 or v >= h
+    return u < 0 or u > w or v < 0 or v > h
+
+
 def _best(keys, desc, cells, invW, invH, dq, u, v, r, lo, hi, skip=None, gate=None,
-          check_levels=False, init=256):
+          check_levels=False, init=256, rules=()):
     """GetFeaturesInArea + first-minimum scan; the level filter is either the
     function's (check_levels) or the loop's (kpLevel < lo || > hi)."""
     idx = features_in_area(keys, cells, invW, invH, u, v, r, lo if check_levels else -1,
                            hi if check_levels else -1)
     bd, bi = init, -1
+    cands = []
     for j in idx:
-        if skip is not None and skip(j):
-            continue
         o = int(keys[j]["octave"])
         if not check_levels and (o < lo or o > hi):
             continue
         if gate is not None and not gate(j):
             continue
         d = hamming(dq, desc[j])
-        if d < bd:
+        cands.append((d, len(cands), j))
+        if skip is not None and skip(j):
+            continue
+        if d < bd or ("tie_flip" in rules and d == bd and bi >= 0):
             bd, bi = d, j
+    if "top4" in rules and skip is not None and len(cands) > TOPK and \
+            all(skip(j) for _, _, j in sorted(cands)[:TOPK]):
+        return init, -1
     return bd, bi
 
 
 def search_by_projection_sim3(keys, desc, scale, width, height, S, cam, mps, mp_desc, th,
-                              kp_matched, log_scale, n_levels=8):
+                              kp_matched, log_scale, n_levels=8, rules=()):
     fx, fy, cx, cy = (f32(c) for c in cam[:4])
     cells, invW, invH = grid_cells(keys, width, height)
     R, t, ow = _sim3_pose(S)
@@ -527,7 +556,7 @@ def search_by_projection_sim3(keys, desc, scale, width, height, S, cam, mps, mp_
         invz = f32(f32(1) / Pc[2])
         u = f32(f32(fx * f32(Pc[0] * invz)) + cx)
         v = f32(f32(fy * f32(Pc[1] * invz)) + cy)
-        if not _in_kf(u, v, width, height):
+        if not _in_kf(u, v, width, height, "bounds_flip" in rules):
             continue
         PO = [f32(f32(mp["pos"][k]) - ow[k]) for k in range(3)]
         dist = _norm(PO)
@@ -537,15 +566,16 @@ def search_by_projection_sim3(keys, desc, scale, width, height, S, cam, mps, mp_
             continue
         lvl = _level(mp["max_distance"], dist, log_scale, n_levels)
         bd, bi = _best(keys, desc, cells, invW, invH, mp_desc[i], u, v,
-                       f32(f32(th) * f32(scale[lvl])), lvl - 1, lvl, skip=lambda j: km[j] >= 0)
-        if bd <= 50:
+                       f32(f32(th) * f32(scale[lvl])), lvl - 1, lvl, skip=lambda j: km[j] >= 0,
+                       rules=rules)
+        if bd < 50 or (bd == 50 and "th_strict" not in rules):
             km[bi] = i
             n += 1
     return n, km
 
 
 def fuse(keys, desc, scale, inv_sigma2, width, height, u_right, R, t, ow, cam, mps, mp_desc, th,
-         log_scale, n_levels=8):
+         log_scale, n_levels=8, rules=()):
     fx, fy, cx, cy, bf = (f32(c) for c in cam[:5])
     cells, invW, invH = grid_cells(keys, width, height)
     best = np.full(len(mps), -1, np.int32)
@@ -559,7 +589,7 @@ def fuse(keys, desc, scale, inv_sigma2, width, height, u_right, R, t, ow, cam, m
         invz = f32(f32(1) / Pc[2])
         u = f32(f32(fx * f32(Pc[0] * invz)) + cx)
         v = f32(f32(fy * f32(Pc[1] * invz)) + cy)
-        if not _in_kf(u, v, width, height):
+        if not _in_kf(u, v, width, height, "bounds_flip" in rules):
             continue
         ur = f32(u - f32(bf * invz))
         PO = [f32(f32(mp["pos"][k]) - f32(ow[k])) for k in range(3)]
@@ -574,20 +604,20 @@ def fuse(keys, desc, scale, inv_sigma2, width, height, u_right, R, t, ow, cam, m
             k = keys[j]
             ex, ey = f32(u - f32(k["x"])), f32(v - f32(k["y"]))
             e2 = f32(f32(ex * ex) + f32(ey * ey))
-            if u_right[j] >= 0:
+            if u_right[j] > 0 or (u_right[j] == 0 and "stereo_flip" not in rules):
                 er = f32(ur - f32(u_right[j]))
                 return float(f32(f32(e2 + f32(er * er)) * f32(inv_sigma2[k["octave"]]))) <= 7.8
             return float(f32(e2 * f32(inv_sigma2[k["octave"]]))) <= 5.99
 
         bd, bi = _best(keys, desc, cells, invW, invH, mp_desc[i], u, v,
-                       f32(f32(th) * f32(scale[lvl])), lvl - 1, lvl, gate=gate)
-        if bd <= 50:
+                       f32(f32(th) * f32(scale[lvl])), lvl - 1, lvl, gate=gate, rules=rules)
+        if bd < 50 or (bd == 50 and "th_strict" not in rules):
             best[i] = bi
             n += 1
     return n, best
 
 
-def search_by_sim3(kf1, kf2, cam, s12, R12, t12, th, log_scale, n_levels=8):
+def search_by_sim3(kf1, kf2, cam, s12, R12, t12, th, log_scale, n_levels=8, rules=()):
     fx, fy, cx, cy = (f32(c) for c in cam[:4])
     R12 = np.asarray(R12, np.float32).reshape(3, 3)
     sR12 = np.array([[f32(float(s12) * float(R12[r, c])) for c in range(3)] for r in range(3)])
@@ -608,15 +638,16 @@ def search_by_sim3(kf1, kf2, cam, s12, R12, t12, th, log_scale, n_levels=8):
             invz = f32(1.0 / float(Pb[2]))
             u = f32(f32(fx * f32(Pb[0] * invz)) + cx)
             v = f32(f32(fy * f32(Pb[1] * invz)) + cy)
-            if not _in_kf(u, v, B["width"], B["height"]):
+            if not _in_kf(u, v, B["width"], B["height"], "bounds_flip" in rules):
                 continue
             dist = _norm(Pb)
             if dist < f32(f32(0.8) * mp["min_distance"]) or dist > f32(f32(1.2) * mp["max_distance"]):
                 continue
             lvl = _level(mp["max_distance"], dist, log_scale, n_levels)
             bd, bi = _best(B["keys"], B["desc"], cells, invW, invH, A["mp_desc"][i], u, v,
-                           f32(f32(th) * f32(B["scale"][lvl])), lvl - 1, lvl, init=1 << 31)
-            if bd <= 100:
+                           f32(f32(th) * f32(B["scale"][lvl])), lvl - 1, lvl, init=1 << 31,
+                           rules=rules)
+            if bd < 100 or (bd == 100 and "th_strict" not in rules):
                 out[i] = bi
         return out
 
@@ -626,7 +657,8 @@ def search_by_sim3(kf1, kf2, cam, s12, R12, t12, th, log_scale, n_levels=8):
     return int((m12 >= 0).sum()), m12
 
 
-def search_by_bow_kf(d1, a1, mp1, bad1, fv1, d2, a2, mp2, bad2, fv2, nnratio, check_ori):
+def search_by_bow_kf(d1, a1, mp1, bad1, fv1, d2, a2, mp2, bad2, fv2, nnratio, check_ori,
+                     rules=()):
     m12 = np.full(len(d1), -1, np.int32)
     matched2 = np.zeros(len(d2), bool)
     hist = [[] for _ in range(30)]
@@ -640,20 +672,23 @@ def search_by_bow_kf(d1, a1, mp1, bad1, fv1, d2, a2, mp2, bad2, fv2, nnratio, ch
                 continue
             b1, b2, bi = 256, 256, -1
             for i2 in f2:
-                if matched2[i2] or mp2[i2] < 0 or bad2[i2]:
+                if (matched2[i2] and "no_claims" not in rules) or mp2[i2] < 0 or bad2[i2]:
                     continue
                 d = hamming(d1[i1], d2[i2])
                 if d < b1:
                     b2, b1, bi = b1, d, i2
+                elif "tie_flip" in rules and d == b1:
+                    b2, bi = d, i2
                 elif d < b2:
                     b2 = d
-            if b1 < 50 and f32(b1) < f32(f32(nnratio) * f32(b2)):
+            if (b1 < 50 or (b1 == 50 and "th_strict" in rules)) and \
+                    f32(b1) < f32(f32(nnratio) * f32(b2)):
                 m12[i1] = mp2[bi]
                 matched2[bi] = True
                 if check_ori:
                     hist[_rot_bin(a1[i1], a2[bi])].append(i1)
     if check_ori:
-        keep = _three_maxima([len(h) for h in hist])
+        keep = _three_maxima([len(h) for h in hist], "hist_ge" in rules)
         for b in range(30):
             if b not in keep:
                 for i1 in hist[b]:
@@ -663,7 +698,7 @@ def search_by_bow_kf(d1, a1, mp1, bad1, fv1, d2, a2, mp2, bad2, fv2, nnratio, ch
 
 def search_by_projection_reloc(keys, desc, scale, width, height, R, t, ow, cam, mps, mp_desc,
                                kf_angle, th, orb_dist, check_ori, kp_locked, log_scale,
-                               n_levels=8):
+                               n_levels=8, rules=()):
     fx, fy, cx, cy = (f32(c) for c in cam[:4])
     cells, invW, invH = grid_cells(keys, width, height)
     lock = np.asarray(kp_locked, bool).copy()
@@ -676,7 +711,7 @@ def search_by_projection_reloc(keys, desc, scale, width, height, R, t, ow, cam, 
         invz = f32(1.0 / float(Pc[2]))
         u = f32(f32(f32(fx * Pc[0]) * invz) + cx)
         v = f32(f32(f32(fy * Pc[1]) * invz) + cy)
-        if u < 0 or u > width or v < 0 or v > height:
+        if _out_frame(u, v, width, height, "bounds_flip" in rules):
             continue
         PO = [f32(f32(mp["pos"][k]) - f32(ow[k])) for k in range(3)]
         dist = _norm(PO)
@@ -685,14 +720,14 @@ def search_by_projection_reloc(keys, desc, scale, width, height, R, t, ow, cam, 
         lvl = _level(mp["max_distance"], dist, log_scale, n_levels)
         bd, bi = _best(keys, desc, cells, invW, invH, mp_desc[i], u, v,
                        f32(f32(th) * f32(scale[lvl])), lvl - 1, lvl + 1, skip=lambda j: lock[j],
-                       check_levels=True)
-        if bd <= orb_dist:
+                       check_levels=True, rules=rules)
+        if bd < orb_dist or (bd == orb_dist and "th_strict" not in rules):
             lock[bi] = True
             km[bi] = i
             if check_ori:
                 hist[_rot_bin(kf_angle[i], keys[bi]["angle"])].append(bi)
     if check_ori:
-        keep = _three_maxima([len(h) for h in hist])
+        keep = _three_maxima([len(h) for h in hist], "hist_ge" in rules)
         for b in range(30):
             if b not in keep:
                 for j in hist[b]:
@@ -701,8 +736,9 @@ def search_by_projection_reloc(keys, desc, scale, width, height, R, t, ow, cam, 
 
 
 def search_for_triangulation(kf1, kf2, level_sigma2, F12, cam, Cw, R2w, t2w, fv1, fv2,
-                             only_stereo, check_ori):
+                             only_stereo, check_ori, rules=()):
     fx, fy, cx, cy = (f32(c) for c in cam[:4])
+    stereo = (lambda ur: ur > 0) if "stereo_flip" in rules else (lambda ur: ur >= 0)
     F = np.asarray(F12, np.float32).reshape(3, 3)
     C2 = _xf(R2w, t2w, Cw)
     invz = f32(f32(1) / C2[2])
@@ -719,7 +755,7 @@ def search_for_triangulation(kf1, kf2, level_sigma2, F12, cam, Cw, R2w, t2w, fv1
         for i1 in fv1[2][fv1[1][k]:fv1[1][k + 1]]:
             if kf1["has_mp"][i1]:
                 continue
-            st1 = kf1["u_right"][i1] >= 0
+            st1 = stereo(kf1["u_right"][i1])
             if only_stereo and not st1:
                 continue
             kp1 = k1s[i1]
@@ -730,11 +766,15 @@ def search_for_triangulation(kf1, kf2, level_sigma2, F12, cam, Cw, R2w, t2w, fv1
             for i2 in f2:
                 if kf2["has_mp"][i2]:
                     continue
-                st2 = kf2["u_right"][i2] >= 0
+                st2 = stereo(kf2["u_right"][i2])
                 if only_stereo and not st2:
                     continue
                 d = hamming(kf1["desc"][i1], kf2["desc"][i2])
                 if d > 50 or d > bd:
+                    continue
+                if d == 50 and "th_strict" in rules:
+                    continue
+                if d == bd and bi >= 0 and "tie_flip" in rules:
                     continue
                 kp2 = k2s[i2]
                 if not st1 and not st2:
@@ -752,12 +792,129 @@ def search_for_triangulation(kf1, kf2, level_sigma2, F12, cam, Cw, R2w, t2w, fv1
                 if check_ori:
                     hist[_rot_bin(kp1["angle"], k2s[bi]["angle"])].append(i1)
     if check_ori:
-        keep = _three_maxima([len(h) for h in hist])
+        keep = _three_maxima([len(h) for h in hist], "hist_ge" in rules)
         for bb in range(30):
             if bb not in keep:
                 for i1 in hist[bb]:
                     m12[i1] = -1
     return int((m12 >= 0).sum()), m12
+
+
+def search_by_projection_frame(keys, desc, scale, width, height, last, last_desc, cam, tlc_z, th,
+                               mono, check_ori, kp_locked=None, u_right=None, rules=()):
+    """SearchByProjection(CurrentFrame, LastFrame, th, bMono) (src/ORBmatcher.cc:1460-1619).
+    `last` rows carry xc, yc, invzc (x3Dc and 1/z), last_octave, last_angle, valid
+    (pMP && !outlier), has_obs (Observations() > 0 of the point written into the
+    current frame) and mp_id.  A keypoint may be written several times (points
+    without observations do not lock it); every write is one nmatches++ and one
+    histogram entry, and every entry of a rejected bin is one nmatches--.
+    Returns (nmatches, kp_match): id written last, -1 untouched, -2 reset."""
+    fx, fy, cx, cy, bf, mb = (f32(c) for c in cam)
+    cells, invW, invH = grid_cells(keys, width, height)
+    lock = np.zeros(len(keys), bool) if kp_locked is None else np.asarray(kp_locked, bool).copy()
+    entry = lock.copy()
+    held = [None] * len(keys)  # None untouched, id, or "null" after the filter
+    fwd = f32(tlc_z) > mb and not mono
+    bwd = -f32(tlc_z) > mb and not mono
+    hist = [[] for _ in range(30)]
+    n = 0
+    for i, L in enumerate(last):
+        if not L["valid"]:
+            continue
+        invzc = f32(L["invzc"])
+        if invzc < 0:
+            continue
+        u = f32(f32(f32(fx * f32(L["xc"])) * invzc) + cx)
+        v = f32(f32(f32(fy * f32(L["yc"])) * invzc) + cy)
+        if _out_frame(u, v, width, height, "bounds_flip" in rules):
+            continue
+        o = int(L["last_octave"])
+        r = f32(f32(th) * f32(scale[o]))
+        if fwd:
+            idx = features_in_area(keys, cells, invW, invH, u, v, r, o, -1)
+        elif bwd:
+            idx = features_in_area(keys, cells, invW, invH, u, v, r, 0, o)
+        else:
+            idx = features_in_area(keys, cells, invW, invH, u, v, r, o - 1, o + 1)
+        bd, bi = 256, -1
+        cands = []  # what a TOPK candidate list would hold: entry locks filtered out
+        for j in idx:
+            if entry[j]:
+                continue
+            if u_right is not None and (u_right[j] > 0 or
+                                        (u_right[j] == 0 and "stereo_flip" in rules)):
+                er = abs(f32(f32(u - f32(bf * invzc)) - f32(u_right[j])))
+                if er > r:
+                    continue
+            d = hamming(last_desc[i], desc[j])
+            cands.append((d, len(cands), j))
+            if lock[j]:
+                continue
+            if d < bd or ("tie_flip" in rules and d == bd and bi >= 0):
+                bd, bi = d, j
+        if "top4" in rules and len(cands) > TOPK and all(lock[j] for _, _, j in
+                                                          sorted(cands)[:TOPK]):
+            continue
+        if bd < 100 or (bd == 100 and "th_strict" not in rules):
+            held[bi] = int(L["mp_id"])
+            lock[bi] = bool(L["has_obs"])
+            n += 1
+            if check_ori:
+                hist[_rot_bin(L["last_angle"], keys[bi]["angle"])].append(bi)
+    if check_ori:
+        keep = _three_maxima([len(h) for h in hist], "hist_ge" in rules)
+        for b in range(30):
+            if b not in keep:
+                for j in hist[b]:
+                    held[j] = "null"
+                    n -= 1
+    km = np.array([-1 if h is None else (-2 if h == "null" else h) for h in held], np.int32)
+    return n, km.reshape(len(keys))
+
+
+def search_by_bow(kf_desc, kf_angle, kf_mp, kf_bad, kf_fv, f_desc, f_angle, f_fv, nnratio,
+                  check_ori, rules=()):
+    """SearchByBoW(pKF, F, vpMapPointMatches) (src/ORBmatcher.cc:164-306): TH_LOW is
+    `<=` here (`<` between KeyFrames), a Frame feature with a match is skipped by
+    later KeyFrame features, the first minimum wins.  Returns (nmatches, f_match)."""
+    fm = np.full(len(f_desc), -1, np.int32)
+    taken = np.zeros(len(f_desc), bool)
+    hist = [[] for _ in range(30)]
+    n = 0
+    nodes_f = {int(f_fv[0][k]): f_fv[2][f_fv[1][k]:f_fv[1][k + 1]] for k in range(len(f_fv[0]))}
+    for k in range(len(kf_fv[0])):
+        ff = nodes_f.get(int(kf_fv[0][k]))
+        if ff is None:
+            continue
+        for ik in kf_fv[2][kf_fv[1][k]:kf_fv[1][k + 1]]:
+            if kf_mp[ik] < 0 or (kf_bad is not None and kf_bad[ik]):
+                continue
+            b1, b2, bi = 256, 256, -1
+            for jf in ff:
+                if taken[jf] and "no_claims" not in rules:
+                    continue
+                d = hamming(kf_desc[ik], f_desc[jf])
+                if d < b1:
+                    b2, b1, bi = b1, d, jf
+                elif "tie_flip" in rules and d == b1:
+                    b2, bi = d, jf
+                elif d < b2:
+                    b2 = d
+            if (b1 < 50 or (b1 == 50 and "th_strict" not in rules)) and \
+                    f32(b1) < f32(f32(nnratio) * f32(b2)):
+                fm[bi] = kf_mp[ik]
+                taken[bi] = True
+                n += 1
+                if check_ori:
+                    hist[_rot_bin(kf_angle[ik], f_angle[bi])].append(bi)
+    if check_ori:
+        keep = _three_maxima([len(h) for h in hist], "hist_ge" in rules)
+        for b in range(30):
+            if b not in keep:
+                for j in hist[b]:
+                    fm[j] = -1
+                    n -= 1
+    return n, fm
 
 
 _POP8 = np.array([bin(i).count("1") for i in range(256)], np.int64)
