@@ -1685,6 +1685,10 @@ __device__ __forceinline__ void oct_rank_by_count(unsigned long long* sortBuf, i
 
 #define OCT_MAX_PASSES 512
 #define OCT_REG_KEYS 8  // keys per thread held in registers (n <= 8 x 512), small batches
+#define OCT_KB 4        // keys a thread has in flight in a key walk
+#ifndef OCT_GB
+#define OCT_GB 8        // keys a thread has in flight in the gather
+#endif
 #ifndef OCT_BATCH_THREADS
 #define OCT_BATCH_THREADS 256  // workgroup of the batch octree (A/B: 128)
 #endif
@@ -1720,13 +1724,13 @@ __global__ __launch_bounds__(512) void k_octree(
   // level ranges of one batch could run concurrently)
   unsigned char* p = GNODES ? gNodes + ((long long)img * plan.nlevels + l) * nodeStride : smem;
   unsigned long long* sortBuf = (unsigned long long*)p; p += (size_t)n2 * 8;
-  OctNode* A = (OctNode*)p; p += (size_t)NC * sizeof(OctNode);
-  OctNode* B = (OctNode*)p; p += (size_t)NC * sizeof(OctNode);
-  int* q4 = (int*)p; p += (size_t)NC * 16;       // quadrant counts, then child indices
-  int* g0 = (int*)p; p += (size_t)NC * 4;
-  int* g1 = (int*)p; p += (size_t)NC * 4;
-  int* g2 = (int*)p; p += (size_t)NC * 4;
-  int* rk = (int*)p; p += (size_t)NC * 4;
+  OctNode* nodeA = (OctNode*)p; p += (size_t)NC * sizeof(OctNode);
+  OctNode* nodeB = (OctNode*)p; p += (size_t)NC * sizeof(OctNode);
+  // two tables of 4 x NC ints that swap roles every pass: one holds the pass's
+  // quadrant counts (then the child indices), the other its per-node scratch
+  // (g0, g1, g2, rk: NC ints each) and then the next pass's quadrant counts
+  int* tabQ = (int*)p; p += (size_t)NC * 16;
+  int* tabG = (int*)p; p += (size_t)NC * 16;
   int* cellBase = (int*)p; p += (size_t)((maxCellsPerLevel + 3) & ~3) * 4;
   if (GNODES) p = smem;
   uint32_t* Klds = (uint32_t*)p; p += (size_t)ldsKeyCap * 4;
@@ -1737,22 +1741,54 @@ __global__ __launch_bounds__(512) void k_octree(
   for (int i = t; i < nc; i += T) cellBase[i] = cellCount[cellSlot0 + i];
   __syncthreads();
   const int n = block_scan_array(cellBase, nc, tmp);
-  uint32_t* K;
-  uint16_t* NID;
-  if (n <= ldsKeyCap) {
-    K = Klds;
-    NID = Nlds;
-  } else {
-    K = gKeys + cellSlot0 * plan.keyCap;  // this level's slot range, reused compacted
-    NID = gNid + cellSlot0 * plan.keyCap;
-  }
   // n < 2^24 (x, y < 4096): node labels NID are node indices (< nodeCap <= 65535),
   // the final-phase sort key packs (size: 24 bits, creation order: 24 bits, node: 16 bits)
   errFlag += img;  // per-image status (read back through the image's count)
-  for (int c = t; c < nc; c += T) {
-    const int cnt = cellCount[cellSlot0 + c], base = cellBase[c];
-    const uint32_t* src = cellKeys + (cellSlot0 + c) * plan.keyCap;
-    for (int i = 0; i < cnt; ++i) K[base + i] = src[i];
+  // The distribution, instantiated once for keys in LDS and once for keys in
+  // the level's global scratch (the branch below is uniform per workgroup): a
+  // pointer that may be either would make every key access a flat_* one, the
+  // same reason GNODES is a template parameter.
+  auto distribute = [&](uint32_t* __restrict__ K, uint16_t* __restrict__ NID,
+                        auto keysInLds) __attribute__((always_inline)) {
+  constexpr bool KLDS = decltype(keysInLds)::value;
+  static_assert(OCT_KB == 4 && OCT_REG_KEYS % OCT_KB == 0, "key blocks are four keys");
+  OctNode* A = nodeA;
+  OctNode* B = nodeB;
+  int* Q = tabQ;
+  int* G = tabG;
+  // ---- gather the cells' key lists (cell order, then list order).  Key k's
+  // cell is the last one whose prefix is <= k (a binary search in cellBase,
+  // OCT_GB keys per thread interleaved), so the global loads of a block are
+  // independent of each other and of every other block's: a wave makes
+  // ceil(n / (OCT_GB * T)) round trips however full its cells are.
+  {
+    int ncp = 1;
+    while (ncp < nc) ncp <<= 1;
+    const int keyCap = plan.keyCap;
+    for (int k0 = t; k0 < n; k0 += OCT_GB * T) {
+      int kk[OCT_GB], c[OCT_GB];
+#pragma unroll
+      for (int u = 0; u < OCT_GB; ++u) {
+        kk[u] = min(k0 + u * T, n - 1);
+        c[u] = 0;
+      }
+      for (int s = ncp >> 1; s > 0; s >>= 1) {
+#pragma unroll
+        for (int u = 0; u < OCT_GB; ++u) {
+          const int m = c[u] + s;
+          if (cellBase[min(m, nc - 1)] <= kk[u] && m < nc) c[u] = m;
+        }
+      }
+      uint32_t v[OCT_GB];
+#pragma unroll
+      for (int u = 0; u < OCT_GB; ++u) {
+        const int i = min(kk[u] - cellBase[c[u]], keyCap - 1);  // < the cell's count <= keyCap
+        v[u] = cellKeys[(cellSlot0 + c[u]) * keyCap + i];
+      }
+#pragma unroll
+      for (int u = 0; u < OCT_GB; ++u)
+        if (k0 + u * T < n) K[k0 + u * T] = v[u];
+    }
   }
   // REG (a frame or two per call, one workgroup per level): each thread's keys
   // k = t, t + T, ... live in registers (key and node id) for the whole
@@ -1764,21 +1800,90 @@ __global__ __launch_bounds__(512) void k_octree(
   const bool inReg = REG && n <= OCT_REG_KEYS * T;
   uint32_t kr[OCT_REG_KEYS];
   int nr[OCT_REG_KEYS];
-  auto each_key = [&](auto&& f) {
+  // A key walk hands f blocks of OCT_KB keys: key[u], nid[u] belong to key
+  // k0 + u * ks (valid while < n; invalid ones read as key 0 in node 0 so that
+  // their table lookups stay in range).  f issues the lookups of all its keys
+  // before it uses the first, so a key's dependent round trips overlap the
+  // other keys'.  Memory-resident keys go four consecutive keys per thread
+  // (one ds_read_b128 + ds_read_b64 when they are in LDS).
+  auto each_block = [&](bool loadN, bool storeN, auto&& f) __attribute__((always_inline)) {
     if (inReg) {
 #pragma unroll
-      for (int i = 0; i < OCT_REG_KEYS; ++i) {
-        const int k = t + i * T;
-        if (k < n) f(kr[i], nr[i], k);
+      for (int b = 0; b < OCT_REG_KEYS / OCT_KB; ++b) {
+        const int k0 = t + b * OCT_KB * T;
+        if (k0 < n) f(&kr[b * OCT_KB], &nr[b * OCT_KB], k0, T);
       }
     } else {
-      for (int k = t; k < n; k += T) {
-        const uint32_t key = K[k];
-        int nid = NID[k];
-        f(key, nid, k);
-        NID[k] = (uint16_t)nid;
+      for (int k0 = t * OCT_KB; k0 < n; k0 += T * OCT_KB) {
+        uint32_t key[OCT_KB];
+        int nid[OCT_KB];
+        if constexpr (KLDS) {
+          // k0 + 3 < ldsKeyCap (a multiple of 8 >= n): the tail reads stay in the arrays
+          const uint4 kv = *(const uint4*)(K + k0);
+          key[0] = kv.x; key[1] = kv.y; key[2] = kv.z; key[3] = kv.w;
+          uint2 nv = make_uint2(0u, 0u);
+          if (loadN) nv = *(const uint2*)(NID + k0);
+          nid[0] = (int)(nv.x & 0xFFFFu); nid[1] = (int)(nv.x >> 16);
+          nid[2] = (int)(nv.y & 0xFFFFu); nid[3] = (int)(nv.y >> 16);
+#pragma unroll
+          for (int u = 0; u < OCT_KB; ++u)
+            if (k0 + u >= n) {
+              key[u] = 0u;
+              nid[u] = 0;
+            }
+        } else {
+#pragma unroll
+          for (int u = 0; u < OCT_KB; ++u) {
+            const bool ok = k0 + u < n;
+            key[u] = ok ? K[k0 + u] : 0u;
+            nid[u] = ok && loadN ? (int)NID[k0 + u] : 0;
+          }
+        }
+        f(key, nid, k0, 1);
+        if (storeN) {
+          if constexpr (KLDS) {
+            *(uint2*)(NID + k0) = make_uint2((uint32_t)nid[0] | ((uint32_t)nid[1] << 16),
+                                             (uint32_t)nid[2] | ((uint32_t)nid[3] << 16));
+          } else {
+#pragma unroll
+            for (int u = 0; u < OCT_KB; ++u)
+              if (k0 + u < n) NID[k0 + u] = (uint16_t)nid[u];
+          }
+        }
       }
     }
+  };
+  // Re-label every key with its node's child (Q holds the child index of every
+  // quadrant; undivided nodes carry their new index in all four) and, when
+  // another pass follows (cont), add the key to that child's quadrant count
+  // for it (table G, zeroed by the caller): one walk over the keys per pass.
+  auto relabel_and_count = [&](bool cont) __attribute__((always_inline)) {
+    each_block(true, true, [&](const uint32_t* key, int* nid, int k0, int ks) __attribute__((always_inline)) {
+      OctNode nd[OCT_KB];
+      int ci[OCT_KB];
+#pragma unroll
+      for (int u = 0; u < OCT_KB; ++u) nd[u] = A[nid[u]];
+#pragma unroll
+      for (int u = 0; u < OCT_KB; ++u) {
+        const int v = Q[nid[u] * 4 + oct_quad(key[u], nd[u])];
+        ci[u] = k0 + u * ks < n ? v : 0;
+      }
+      if (cont) {
+        OctNode cn[OCT_KB];
+#pragma unroll
+        for (int u = 0; u < OCT_KB; ++u) cn[u] = B[ci[u]];
+#pragma unroll
+        for (int u = 0; u < OCT_KB; ++u)
+          if (k0 + u * ks < n) {
+            nid[u] = ci[u];
+            if (cn[u].cnt > 1) atomicAdd(&G[ci[u] * 4 + oct_quad(key[u], cn[u])], 1);
+          }
+      } else {
+#pragma unroll
+        for (int u = 0; u < OCT_KB; ++u)
+          if (k0 + u * ks < n) nid[u] = ci[u];
+      }
+    });
   };
   __syncthreads();  // K complete
   if (inReg) {
@@ -1792,58 +1897,186 @@ __global__ __launch_bounds__(512) void k_octree(
   // ---- roots (src/ORBextractor.cc:562-604)
   const int nIni = L.nIni;
   const float hX = L.hX;
-  for (int i = t; i < nIni; i += T) g0[i] = 0;
-  __syncthreads();
-  each_key([&](uint32_t key, int& nid, int) {
-    const float xr = (float)(key_x(key) - 16);
-    const int r = min((int)__fdiv_rn(xr, hX), nIni - 1);  // vpIniNodes[kp.pt.x/hX]
-    nid = r;
-    atomicAdd(&g0[r], 1);
-  });
-  __syncthreads();
-  if (t == 0) {
-    int a = 0;
-    for (int i = 0; i < nIni; ++i) {
-      g1[i] = a;
-      if (g0[i] > 0) {
-        OctNode nd;
-        nd.x0 = (int16_t)(int)(hX * (float)i);
-        nd.x1 = (int16_t)(int)(hX * (float)(i + 1));
-        nd.y0 = 0;
-        nd.y1 = (int16_t)L.Hr;
-        nd.cnt = g0[i];
-        nd.seq = i;
-        A[a++] = nd;
-      }
+  {
+    int* const g0 = G;
+    int* const g1 = G + NC;
+    for (int i = t; i < nIni; i += T) {
+      g0[i] = 0;
+      *(int4*)&Q[i * 4] = make_int4(0, 0, 0, 0);
     }
-    sh[0] = a;
+    __syncthreads();
+    each_block(false, true, [&](const uint32_t* key, int* nid, int k0, int ks) __attribute__((always_inline)) {
+#pragma unroll
+      for (int u = 0; u < OCT_KB; ++u)
+        if (k0 + u * ks < n) {
+          const float xr = (float)(key_x(key[u]) - 16);
+          const int r = min((int)__fdiv_rn(xr, hX), nIni - 1);  // vpIniNodes[kp.pt.x/hX]
+          nid[u] = r;
+          atomicAdd(&g0[r], 1);
+        }
+    });
+    __syncthreads();
+    if (t == 0) {
+      int a = 0;
+      for (int i = 0; i < nIni; ++i) {
+        g1[i] = a;
+        if (g0[i] > 0) {
+          OctNode nd;
+          nd.x0 = (int16_t)(int)(hX * (float)i);
+          nd.x1 = (int16_t)(int)(hX * (float)(i + 1));
+          nd.y0 = 0;
+          nd.y1 = (int16_t)L.Hr;
+          nd.cnt = g0[i];
+          nd.seq = i;
+          A[a++] = nd;
+        }
+      }
+      sh[0] = a;
+    }
+    __syncthreads();
+    // root index -> node index, and the first pass's quadrant counts
+    each_block(true, true, [&](const uint32_t* key, int* nid, int k0, int ks) __attribute__((always_inline)) {
+      int v[OCT_KB];
+      OctNode nd[OCT_KB];
+#pragma unroll
+      for (int u = 0; u < OCT_KB; ++u) v[u] = k0 + u * ks < n ? g1[nid[u]] : 0;
+#pragma unroll
+      for (int u = 0; u < OCT_KB; ++u) nd[u] = A[v[u]];
+#pragma unroll
+      for (int u = 0; u < OCT_KB; ++u)
+        if (k0 + u * ks < n) {
+          nid[u] = v[u];
+          if (nd[u].cnt > 1) atomicAdd(&Q[v[u] * 4 + oct_quad(key[u], nd[u])], 1);
+        }
+    });
   }
-  __syncthreads();
-  each_key([&](uint32_t, int& nid, int) { nid = g1[nid]; });
   int alive = sh[0];
   const int N = L.quota;
   int seqNext = nIni;
   bool finalPhase = false;
   int pass = 0;
   __syncthreads();
+  // Every pass starts with its quadrant counts in Q (nodes with > 1 key; the
+  // previous pass's re-labelling walk, or the roots', counted them) and ends
+  // with the tables swapped.
   for (; pass < maxPasses; ++pass) {
     const int prev = alive;
-    if (!finalPhase) {
+    int* const g0 = G;
+    int* const g1 = G + NC;
+    int* const g2 = G + 2 * NC;
+    int* const rk = G + 3 * NC;
+    int S, next;
+    const bool small = alive <= 64;
+    if (small) {
+      // ================= up to 64 nodes (the first passes of every level, and
+      // all of them at 1000 features): wave 0 takes one node per lane and does
+      // the pass's node steps of either kind below in registers -- wave scans
+      // for the prefix sums, lane permutes for the final phase's sorted order
+      // -- with no scratch table and one barrier instead of six to fifteen.
+      if (finalPhase && seqNext >= (1 << 24)) {
+        if (t == 0) atomicOr(errFlag, 8);
+        break;
+      }
+      if (t < 64) {
+        const int a = t;
+        const bool valid = a < alive;
+        const OctNode nd = A[valid ? a : 0];
+        const bool multi = valid && nd.cnt > 1;
+        const int4 cv = *(const int4*)&Q[(valid ? a : 0) * 4];
+        const int c[4] = {multi ? cv.x : 0, multi ? cv.y : 0, multi ? cv.z : 0, multi ? cv.w : 0};
+        int nce = 0, nte = 0;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          nce += c[q] > 0;
+          nte += c[q] > 1;
+        }
+        bool divide, stop = false;
+        int pos, Sw, nExp = 0;
+        if (!finalPhase) {  // (:625-684)
+          divide = multi;
+          const int ia = wave_incl_scan(nce);
+          Sw = __builtin_amdgcn_readlane(ia, 63);
+          pos = ia - nce;
+          nExp = wave_sum(nte);
+        } else {  // (:695-756)
+          const int ncand = __popcll(__ballot(multi));
+          stop = ncand == 0;  // nothing to divide: size == prevSize
+          // rank by (size, creation order) descending; the other lanes follow in lane order
+          const unsigned long long key =
+              multi ? ((unsigned long long)nd.cnt << 40) | ((unsigned long long)(uint32_t)nd.seq << 16) |
+                          (unsigned)a
+                    : 0ull;
+          const int klo = (int)(uint32_t)key, khi = (int)(uint32_t)(key >> 32);
+          int rank = 0;
+          for (int i = 0; i < 64; ++i) {
+            const unsigned long long ki =
+                ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane(khi, i) << 32) |
+                (uint32_t)__builtin_amdgcn_readlane(klo, i);
+            rank += (ki > key || (ki == key && i < a)) ? 1 : 0;
+          }
+          // lane j of the sorted order: the candidate of rank j
+          const int nceS = __builtin_amdgcn_ds_permute(rank * 4, nce);
+          const bool candS = a < ncand;
+          // node j adds (non-empty children - 1) nodes; stop after the first
+          // division that brings the list to >= N (:749-750)
+          const int d = candS ? nceS - 1 : 0;
+          const int g2x = wave_incl_scan(d) - d;
+          const unsigned long long hit = __ballot(candS && alive + g2x + nceS - 1 >= N);
+          const int jstop = hit ? __ffsll((long long)hit) - 1 : ncand - 1;
+          const int e = candS && a <= jstop ? nceS : 0;
+          const int ie = wave_incl_scan(e);
+          Sw = __builtin_amdgcn_readlane(ie, 63);
+          pos = __builtin_amdgcn_ds_bpermute(rank * 4, ie - e);
+          divide = multi && rank <= jstop;
+        }
+        const int keepf = valid && !divide ? 1 : 0;
+        const int ik = wave_incl_scan(keepf);
+        const int keepW = __builtin_amdgcn_readlane(ik, 63);
+        const int nextW = Sw + keepW;
+        if (!stop && nextW <= NC) {
+          const bool contW = nextW < N && nextW != prev && pass + 1 < maxPasses;
+          if (divide) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+              if (c[q] > 0) {
+                const int ni = Sw - 1 - pos;
+                B[ni] = oct_child(nd, q, c[q], seqNext + pos);
+                Q[a * 4 + q] = ni;
+                if (contW) *(int4*)&G[ni * 4] = make_int4(0, 0, 0, 0);
+                ++pos;
+              }
+          } else if (valid) {
+            const int ni = Sw + ik - keepf;
+            B[ni] = nd;
+            *(int4*)&Q[a * 4] = make_int4(ni, ni, ni, ni);
+            if (contW) *(int4*)&G[ni * 4] = make_int4(0, 0, 0, 0);
+          }
+        }
+        if (t == 0) {
+          sh[2] = Sw;
+          sh[3] = nextW;
+          sh[4] = nExp;
+          sh[5] = stop ? 1 : 0;
+        }
+      }
+      __syncthreads();
+      if (sh[5]) break;
+      S = sh[2];
+      next = sh[3];
+      if (next > NC) {
+        if (t == 0) atomicOr(errFlag, 2);
+        break;
+      }
+      if (!finalPhase && next + sh[4] * 3 > N) finalPhase = true;  // :692 (when the loop goes on)
+    } else if (!finalPhase) {
       // ================= regular pass: divide every node with > 1 key (:625-684)
-      for (int i = t; i < alive * 4; i += T) q4[i] = 0;
-      __syncthreads();
-      each_key([&](uint32_t key, int& nid, int) {
-        const OctNode nd = A[nid];
-        if (nd.cnt > 1) atomicAdd(&q4[nid * 4 + oct_quad(key, nd)], 1);
-      });
-      __syncthreads();
       int nteLocal = 0;
       for (int a = t; a < alive; a += T) {
         int nce = 0;
         if (A[a].cnt > 1) {
 #pragma unroll
           for (int q = 0; q < 4; ++q) {
-            const int c = q4[a * 4 + q];
+            const int c = Q[a * 4 + q];
             nce += c > 0;
             nteLocal += c > 1;
           }
@@ -1851,7 +2084,7 @@ __global__ __launch_bounds__(512) void k_octree(
         g0[a] = nce;
         g1[a] = A[a].cnt > 1 ? 0 : 1;
       }
-      int nToExpand, S, NM;
+      int nToExpand, NM;
       block_scan2(g0, alive, g1, alive, nteLocal, tmp, &S, &NM, &nToExpand);
       if (S + NM > NC) {
         if (t == 0) atomicOr(errFlag, 2);
@@ -1863,31 +2096,22 @@ __global__ __launch_bounds__(512) void k_octree(
           int pos = g0[a];
 #pragma unroll
           for (int q = 0; q < 4; ++q) {
-            const int c = q4[a * 4 + q];
+            const int c = Q[a * 4 + q];
             if (c > 0) {
               const int ni = S - 1 - pos;
               B[ni] = oct_child(nd, q, c, seqNext + pos);
-              q4[a * 4 + q] = ni;
+              Q[a * 4 + q] = ni;
               ++pos;
             }
           }
         } else {
           const int ni = S + g1[a];
           B[ni] = nd;
-          q4[a * 4] = ni;
+          *(int4*)&Q[a * 4] = make_int4(ni, ni, ni, ni);
         }
       }
-      __syncthreads();
-      each_key([&](uint32_t key, int& nid, int) {
-        const OctNode nd = A[nid];
-        nid = q4[nid * 4 + (nd.cnt > 1 ? oct_quad(key, nd) : 0)];
-      });
-      __syncthreads();
-      OctNode* sw = A; A = B; B = sw;
-      alive = S + NM;
-      seqNext += S;
-      if (alive >= N || alive == prev) break;                 // :688-691
-      if (alive + nToExpand * 3 > N) finalPhase = true;      // :692
+      next = S + NM;
+      if (next + nToExpand * 3 > N) finalPhase = true;      // :692 (when the loop goes on)
     } else {
       // ================= final phase pass (:695-756)
       if (seqNext >= (1 << 24)) {  // creation order no longer fits the sort key (24 bits)
@@ -1907,7 +2131,6 @@ __global__ __launch_bounds__(512) void k_octree(
         if (nd.cnt > 1)  // sort key (size, creation order); node index rides in the low bits
           sortBuf[g0[a]] = ((unsigned long long)nd.cnt << 40) |
                            ((unsigned long long)(uint32_t)nd.seq << 16) | (unsigned)a;
-        q4[a * 4 + 0] = q4[a * 4 + 1] = q4[a * 4 + 2] = q4[a * 4 + 3] = 0;
         rk[a] = 0x7fffffff;
       }
       __syncthreads();
@@ -1927,10 +2150,6 @@ __global__ __launch_bounds__(512) void k_octree(
         block_bitonic_desc(sortBuf, m2);
       }
       for (int j = t; j < ncand; j += T) rk[(int)(sortBuf[j] & 0xFFFF)] = j;
-      each_key([&](uint32_t key, int& nid, int) {
-        const OctNode nd = A[nid];
-        if (nd.cnt > 1) atomicAdd(&q4[nid * 4 + oct_quad(key, nd)], 1);
-      });
       if (t == 0) sh[1] = ncand - 1;
       __syncthreads();
       // node j in sorted order adds (non-empty children - 1) nodes; stop after
@@ -1939,7 +2158,7 @@ __global__ __launch_bounds__(512) void k_octree(
         const int a = (int)(sortBuf[j] & 0xFFFF);
         int nce = 0;
 #pragma unroll
-        for (int q = 0; q < 4; ++q) nce += q4[a * 4 + q] > 0;
+        for (int q = 0; q < 4; ++q) nce += Q[a * 4 + q] > 0;
         g1[j] = nce;
         g2[j] = nce - 1;
       }
@@ -1953,7 +2172,7 @@ __global__ __launch_bounds__(512) void k_octree(
         if (j > jstop) g1[j] = 0;
       for (int a = t; a < alive; a += T) g2[a] = (rk[a] <= jstop) ? 0 : 1;
       // child base per divided node, position of each kept node
-      int S, keep, unused;
+      int keep, unused;
       block_scan2(g1, ncand, g2, alive, 0, tmp, &S, &keep, &unused);
       if (S + keep > NC) {
         if (t == 0) atomicOr(errFlag, 2);
@@ -1966,44 +2185,61 @@ __global__ __launch_bounds__(512) void k_octree(
           int pos = g1[j];
 #pragma unroll
           for (int q = 0; q < 4; ++q) {
-            const int c = q4[a * 4 + q];
+            const int c = Q[a * 4 + q];
             if (c > 0) {
               const int ni = S - 1 - pos;
               B[ni] = oct_child(nd, q, c, seqNext + pos);
-              q4[a * 4 + q] = ni;
+              Q[a * 4 + q] = ni;
               ++pos;
             }
           }
         } else {
           const int ni = S + g2[a];
           B[ni] = nd;
-          q4[a * 4] = ni;
+          *(int4*)&Q[a * 4] = make_int4(ni, ni, ni, ni);
         }
       }
-      __syncthreads();
-      each_key([&](uint32_t key, int& nid, int) {
-        const OctNode nd = A[nid];
-        nid = q4[nid * 4 + (rk[nid] <= jstop ? oct_quad(key, nd) : 0)];
-      });
-      __syncthreads();
-      OctNode* sw = A; A = B; B = sw;
-      alive = S + keep;
-      seqNext += S;
-      if (alive >= N || alive == prev) break;  // :753-754
+      next = S + keep;
     }
+    // the loop goes on unless the list is full or did not grow (:688-691, :753-754)
+    const bool cont = next < N && next != prev && pass + 1 < maxPasses;
+    if (!small) {
+      __syncthreads();  // B and Q complete; g0 .. rk (G) read for the last time
+      if (cont) {
+        for (int i = t; i < next; i += T) *(int4*)&G[i * 4] = make_int4(0, 0, 0, 0);
+        __syncthreads();
+      }
+    }
+    relabel_and_count(cont);
+    __syncthreads();
+    OctNode* sw = A; A = B; B = sw;
+    int* st = Q; Q = G; G = st;
+    alive = next;
+    seqNext += S;
+    if (alive >= N || alive == prev) break;
   }
   if (pass >= maxPasses && t == 0) atomicOr(errFlag, 4);
   // ---- retain the best key of each node (:760-779)
-  uint32_t* best = (uint32_t*)g0;
+  uint32_t* best = (uint32_t*)G;
   for (int a = t; a < alive; a += T) best[a] = 0u;
   __syncthreads();
-  each_key([&](uint32_t key, int& nid, int k) {
-    atomicMax(&best[nid], ((uint32_t)key_s(key) << 24) | (uint32_t)(0xFFFFFF - k));
+  each_block(true, false, [&](const uint32_t* key, int* nid, int k0, int ks) __attribute__((always_inline)) {
+#pragma unroll
+    for (int u = 0; u < OCT_KB; ++u) {
+      const int k = k0 + u * ks;
+      if (k < n)
+        atomicMax(&best[nid[u]], ((uint32_t)key_s(key[u]) << 24) | (uint32_t)(0xFFFFFF - k));
+    }
   });
   __syncthreads();
   uint32_t* out = outKeys + (long long)img * plan.slotsPerImage + L.outOff;
   for (int a = t; a < alive; a += T) out[a] = K[0xFFFFFF - (int)(best[a] & 0xFFFFFF)];
   if (t == 0) outCount[img * plan.nlevels + l] = alive;
+  };  // distribute
+  if (n <= ldsKeyCap)
+    distribute(Klds, Nlds, std::true_type{});
+  else  // this level's slot range of the global scratch, reused compacted
+    distribute(gKeys + cellSlot0 * plan.keyCap, gNid + cellSlot0 * plan.keyCap, std::false_type{});
 }
 
 // ============================================================ k_blur_levels

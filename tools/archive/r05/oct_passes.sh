@@ -1,4 +1,6 @@
 # k_octree time against its pass bound (ORB_OCTREE_MAX_PASSES test hook: the distribution stops after k passes; results flagged, timing only)
+# OBSOLETE: the ORB_OCTREE_MAX_PASSES getenv hook was removed; nothing reads the variable.
+# The pass bound is lowered only at compile time (make testhook, -DORB_OCTREE_TEST_PASSES=k).
 set -u
 cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/octp; mkdir -p $O

@@ -20,6 +20,9 @@
 # input pipeline (round 8, measured and not kept):
 # -DRESOLVE_AHEAD=1|2 (blocks in flight in registers), -DRESOLVE_KM_GLOBAL=1
 # (kpMatch by global atomics) and -DRESOLVE_SLOW_CALL=1 (the exact re-scan as a call).
+# PATCHES=octree_stamps.patch adds k_octree's per-phase s_memtime sums per level
+# (-DOCT_STAMPS, read by tools/probe/oct_stamps.py; the stamps themselves cost
+# about a third of the stamped kernel's time, so read them as shares).
 # Select the build with ORB_AMD_LIB=<path>.  variants.patch is the diff from
 # the product file to the round-5 source that held these blocks inline
 # (regenerate: tools/unifdef.py resolves them, see its docstring).
