@@ -67,6 +67,12 @@
  *   orb_close_points(_batch)       the closest-point selection of Tracking::UpdateLastFrame
  *                                  src/Tracking.cc:969-1021 and CreateNewKeyFrame :1263-1318,
  *                                  the counts of NeedNewKeyFrame :1181-1197
+ *   orb_match_projection_frame_batch  device-batched SearchByProjection(CurrentFrame, LastFrame)
+ *                                  src/ORBmatcher.cc:1460-1619 with TrackWithMotionModel's
+ *                                  2 * th retry src/Tracking.cc:1044-1052; pins: twc as mOw,
+ *                                  3x3 * vector as ((r0 x + r1 y) + r2 z) + t, invzc = 1.0f / z
+ *   orb_track_discard_outliers_batch  "Discard outliers" src/Tracking.cc:1060-1083 and the
+ *                                  already-matched marking of SearchLocalPoints :1333-1354
  *   orb_vocabulary_create / _load_text / _destroy
  *                                  DBoW2 TemplatedVocabulary ctor + loadFromTextFile
  *                                  Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:1362-1448
@@ -862,6 +868,83 @@ orb_status_t orb_pose_optimization_batch(orb_matcher_t* m, int n_problems,
                                          orb_pose_opt_info_t* d_info, void* stream);
 /* Largest keypoint-slot count (n, kp_stride) whose edge records stay in LDS. */
 int orb_pose_optimization_lds_edges(void);
+
+/* Device-batched SearchByProjection(CurrentFrame, LastFrame, th, bMono)
+ * (src/ORBmatcher.cc:1460-1619) as Tracking::TrackWithMotionModel calls it
+ * (src/Tracking.cc:1044-1052): n_problems independent problems, every input a
+ * device pointer, asynchronous on `stream`, no host synchronisation.
+ * Problem p reads
+ *   the current frame: d_keys, d_desc (x 32), d_u_right (NULL: monocular, every
+ *     mvuRight = -1) and d_locked (NULL: none; != 0 <=> mvpMapPoints[i] &&
+ *     Observations() > 0 on entry) at p * kp_stride, d_nkeys[p] keypoints;
+ *   d_pose_cur[p] (the predicted mVelocity * mLastFrame.mTcw) and
+ *     d_pose_last[p]: rcw and tcw only, ow is not read;
+ *   the last frame: d_last_keys at p * kp_stride (octave and angle),
+ *     d_last_nkeys[p], d_last_point_index at p * kp_stride (>= 0: the index of
+ *     mvpMapPoints[i]; any negative value, this family's -2 included, = NULL),
+ *     d_last_outlier (NULL: none);
+ *   the map points d_points + p * mp_stride (mp_stride 0: one array shared by
+ *     all problems; pos and has_obs are read; the caller keeps every index
+ *     inside the array), their descriptors d_mp_desc + (p * mp_stride + index) * 32.
+ * cam, scale_factors (n_levels floats) and the rest are host values.
+ * Pinned arithmetic: twc[i] = -((R[i] t0 + R[3+i] t1) + R[6+i] t2) with R, t of
+ * the current pose; every other float 3x3 * vector product, tlc = Rlw twc + tlw
+ * and x3Dc = Rcw x3Dw + tcw, is ((r0 x + r1 y) + r2 z) + t without contraction;
+ * invzc = 1.0f / z (the reference's double division narrowed is the same float).
+ * bForward = tlc.z > cam->mb && !mono, bBackward = -tlc.z > cam->mb && !mono.
+ * Retry: with retry_below > 0 a problem whose first pass returns fewer than
+ * retry_below matches is run again from cleared outputs with 2.0f * th, on the
+ * device, that problem alone (Tracking: retry_below = 20).
+ * Out: d_kp_match + p * kp_stride (the first d_nkeys[p] entries): the map-point
+ * index assigned to the keypoint, -1 untouched, -2 reset by the rotation
+ * filter: orb_pose_optimization_batch's d_point_index (with d_points,
+ * sizeof(orb_map_point_t), mp_stride); d_info[p].
+ * A last-frame keypoint that holds a non-outlier map point and whose octave is
+ * outside [0, n_levels) is found on the device: that problem's n_matches and
+ * n_matches_first_pass are -1, its kp_match all -1, nothing is read out of
+ * bounds.  kp_stride above orb_match_projection_frame_batch_max_stride() (the
+ * replay state of one problem lives in the LDS of one CU): ORB_ECAPACITY
+ * before anything is launched. */
+typedef struct orb_frame_match_info {
+  int32_t n_matches;            /* the return value (of the second pass when retried) */
+  int32_t n_matches_first_pass; /* the first pass's return value */
+  int32_t retried;              /* 1 when the 2 * th pass ran */
+  int32_t forward, backward;    /* bForward, bBackward */
+} orb_frame_match_info_t;
+orb_status_t orb_match_projection_frame_batch(
+    orb_matcher_t* m, int n_problems, const orb_keypoint_t* d_keys, const uint8_t* d_desc,
+    const float* d_u_right, const uint8_t* d_locked, const int32_t* d_nkeys, int kp_stride,
+    const orb_pose_t* d_pose_cur, const orb_pose_t* d_pose_last,
+    const orb_keypoint_t* d_last_keys, const int32_t* d_last_nkeys,
+    const int32_t* d_last_point_index, const uint8_t* d_last_outlier,
+    const orb_map_point_t* d_points, const uint8_t* d_mp_desc, int mp_stride,
+    const orb_camera_t* cam, float min_x, float max_x, float min_y, float max_y, int n_levels,
+    const float* scale_factors, float th, int mono, int check_orientation, int retry_below,
+    int32_t* d_kp_match, orb_frame_match_info_t* d_info, void* stream);
+int orb_match_projection_frame_batch_max_stride(void);
+
+/* TrackWithMotionModel's "Discard outliers" loop (src/Tracking.cc:1060-1083)
+ * after orb_pose_optimization_batch, per problem, in place on d_kp_match and
+ * d_outlier (both at p * kp_stride, d_nkeys[p] entries): a matched keypoint
+ * flagged outlier gets kp_match = -1 and outlier = 0.  d_out[p]: n_discarded,
+ * n_matches_map = the kept matches whose point has has_obs (nmatchesMap),
+ * n_matches = d_info[p].n_matches - n_discarded.
+ * mark_seen != 0 (needs mp_stride > 0, else ORB_EINVAL) also marks, in the
+ * problem's own records d_points + p * mp_stride, what orb_frustum_batch must
+ * skip: a kept match whose point is bad becomes -1 (SearchLocalPoints' first
+ * loop, src/Tracking.cc:1333-1354), every other kept point and every discarded
+ * point (:1076) gets seen = 1.  IncreaseVisible and the other MapPoint side
+ * effects stay with the caller.  mp_stride as above.  Asynchronous on `stream`. */
+typedef struct orb_track_discard_info {
+  int32_t n_matches, n_matches_map, n_discarded;
+} orb_track_discard_info_t;
+orb_status_t orb_track_discard_outliers_batch(orb_matcher_t* m, int n_problems,
+                                              const int32_t* d_nkeys, int kp_stride,
+                                              int32_t* d_kp_match, uint8_t* d_outlier,
+                                              orb_map_point_t* d_points, int mp_stride,
+                                              int mark_seen,
+                                              const orb_frame_match_info_t* d_info,
+                                              orb_track_discard_info_t* d_out, void* stream);
 
 /* ------------------------------------------------------ DBoW2 vocabulary */
 

@@ -50,6 +50,10 @@ CLOSE_COUNTS_DTYPE = np.dtype([("n_sorted", "<i4"), ("n_visit", "<i4"),
                                ("n_tracked_close", "<i4"), ("n_non_tracked_close", "<i4")])
 POSE_OPT_INFO_DTYPE = np.dtype([("n_inliers", "<i4"), ("n_edges", "<i4"),
                                 ("lm_iterations", "<i4"), ("rejected_trials", "<i4")])
+FRAME_MATCH_INFO_DTYPE = np.dtype([("n_matches", "<i4"), ("n_matches_first_pass", "<i4"),
+                                   ("retried", "<i4"), ("forward", "<i4"), ("backward", "<i4")])
+TRACK_DISCARD_INFO_DTYPE = np.dtype([("n_matches", "<i4"), ("n_matches_map", "<i4"),
+                                     ("n_discarded", "<i4")])
 ORB_DEPTH_U16, ORB_DEPTH_F32 = 0, 1
 
 
@@ -203,10 +207,22 @@ def lib() -> ctypes.CDLL:
         "orb_pose_optimization_batch": (i32, [vp, i32, vp, vp, vp, i32, vp, vp, i32, i64, vp, i32,
                                               vp, vp, vp, vp, vp, vp]),
         "orb_pose_optimization_lds_edges": (i32, []),
+        "orb_match_projection_frame_batch": (
+            i32, [vp, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, f32,
+                  f32, f32, f32, i32, vp, f32, i32, i32, i32, vp, vp, vp]),
+        "orb_match_projection_frame_batch_max_stride": (i32, []),
+        "orb_track_discard_outliers_batch": (i32, [vp, i32, vp, i32, vp, vp, vp, i32, i32, vp, vp,
+                                                   vp]),
         "orb_synth_image": (None, [ctypes.c_uint64, i32, i32, i32, i32, vp, sz]),
         "orb_synth_local_map": (None, [ctypes.c_uint64, vp, vp, i32, i32, i32, i32, vp, vp, vp]),
     }
+    # entries an older build named by ORB_AMD_LIB (a baseline for an A/B
+    # measurement) does not have; calling one there is an AttributeError
+    newer = ("orb_match_projection_frame_batch", "orb_match_projection_frame_batch_max_stride",
+             "orb_track_discard_outliers_batch")
     for name, (res, args) in sig.items():
+        if name in newer and "ORB_AMD_LIB" in os.environ and not hasattr(L, name):
+            continue
         fn = getattr(L, name)
         fn.restype = res
         fn.argtypes = args
@@ -1127,6 +1143,44 @@ class ORBmatcher:
     def pose_optimization_lds_edges() -> int:
         """Largest keypoint-slot count whose edge records k_pose_optimization keeps in LDS."""
         return lib().orb_pose_optimization_lds_edges()
+
+    # ------------------------- TrackWithMotionModel's matcher stage, device batch
+    def search_by_projection_frame_batch(self, n_problems, d_keys, d_desc, d_u_right, d_locked,
+                                         d_nkeys, kp_stride, d_pose_cur, d_pose_last,
+                                         d_last_keys, d_last_nkeys, d_last_point_index,
+                                         d_last_outlier, d_points, d_mp_desc, mp_stride, cam,
+                                         min_x, max_x, min_y, max_y, scale_factors, th, bMono,
+                                         retry_below, d_kp_match, d_info, stream: int = 0):
+        """Device-batched SearchByProjection(CurrentFrame, LastFrame, th, bMono)
+        with TrackWithMotionModel's 2 * th retry (orb_match_projection_frame_batch).
+        d_* are device addresses; d_u_right, d_locked and d_last_outlier may be 0
+        (monocular / none); d_info holds n_problems FRAME_MATCH_INFO_DTYPE
+        records; cam = (fx, fy, cx, cy, bf, mb) and scale_factors are host
+        values.  Asynchronous on `stream`."""
+        sf = np.ascontiguousarray(scale_factors, np.float32)
+        c = self._camera(cam)
+        _check(lib().orb_match_projection_frame_batch(
+            self._h, n_problems, d_keys, d_desc, d_u_right or None, d_locked or None, d_nkeys,
+            kp_stride, d_pose_cur, d_pose_last, d_last_keys, d_last_nkeys, d_last_point_index,
+            d_last_outlier or None, d_points, d_mp_desc, mp_stride, ctypes.addressof(c), min_x,
+            max_x, min_y, max_y, len(sf), _ptr(sf), th, int(bMono),
+            int(self.mbCheckOrientation), retry_below, d_kp_match, d_info, stream or None),
+            "search_by_projection_frame_batch")
+
+    @staticmethod
+    def search_by_projection_frame_batch_max_stride() -> int:
+        """Largest kp_stride search_by_projection_frame_batch accepts."""
+        return lib().orb_match_projection_frame_batch_max_stride()
+
+    def track_discard_outliers_batch(self, n_problems, d_nkeys, kp_stride, d_kp_match, d_outlier,
+                                     d_points, mp_stride, mark_seen, d_info, d_out,
+                                     stream: int = 0):
+        """TrackWithMotionModel's "Discard outliers" loop and, with mark_seen,
+        SearchLocalPoints' already-matched marking (orb_track_discard_outliers_batch);
+        d_out holds n_problems TRACK_DISCARD_INFO_DTYPE records."""
+        _check(lib().orb_track_discard_outliers_batch(
+            self._h, n_problems, d_nkeys, kp_stride, d_kp_match, d_outlier, d_points, mp_stride,
+            int(bool(mark_seen)), d_info, d_out, stream or None), "track_discard_outliers_batch")
 
     # ------------------------------------------ MapPoint::ComputeDistinctiveDescriptors
     def ComputeDistinctiveDescriptors(self, obs_offs, obs_desc, descriptors=None):

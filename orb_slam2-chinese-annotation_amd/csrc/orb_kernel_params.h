@@ -195,3 +195,16 @@ struct PoseOptParams {
   float invLevelSigma2[ORB_MAX_LEVELS];  // mvInvLevelSigma2
   float fx, fy, cx, cy, bf;
 };
+
+// -------------------------------------------------------- track_kernels.hip
+// SearchByProjection(CurrentFrame, LastFrame) over nProblems x stride keypoint
+// slots, poses and map points read on the device (by value)
+struct FrameBatchParams {
+  int nProblems, stride;
+  long long mpStride;  // map points between two problems' arrays (0: one shared array)
+  float minX, maxX, minY, maxY, invW, invH;
+  float fx, fy, cx, cy, bf, mb;
+  float th;
+  int nLevels, mono, checkOri, retryBelow;
+  float scale[ORB_MAX_LEVELS];
+};

@@ -209,4 +209,20 @@ hipError_t orb_k_pose_optimization(const PoseOptParams* params, const int32_t* c
                                    const orb_pose_t* poseIn, orb_pose_t* poseOut,
                                    uint8_t* outlier, orb_pose_opt_info_t* info, void* scratch,
                                    hipStream_t s);
+// -------------------------------------------------------- track_kernels.hip
+// largest keypoint-slot count (kp_stride) whose replay state fits one CU's LDS
+int orb_k_frame_batch_max_stride(void);
+hipError_t orb_k_frame_batch(const FrameBatchParams* params, const orb_keypoint_t* keys,
+                             const uint8_t* desc, const float* uright, const uint8_t* locked,
+                             const int32_t* nkeys, const orb_pose_t* poseCur,
+                             const orb_pose_t* poseLast, const orb_keypoint_t* lastKeys,
+                             const int32_t* lastNkeys, const int32_t* lastPointIndex,
+                             const uint8_t* lastOutlier, const orb_map_point_t* points,
+                             const uint8_t* mpDesc, const int32_t* cellStart,
+                             const int32_t* cellIdx, int32_t* kpMatch,
+                             orb_frame_match_info_t* info, hipStream_t s);
+hipError_t orb_k_track_discard(int nProblems, int stride, long long mpStride, int markSeen,
+                               const int32_t* nkeys, int32_t* kpMatch, uint8_t* outlier,
+                               orb_map_point_t* points, const orb_frame_match_info_t* info,
+                               orb_track_discard_info_t* out, hipStream_t s);
 }

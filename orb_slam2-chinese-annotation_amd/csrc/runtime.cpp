@@ -4038,6 +4038,84 @@ orb_status_t orb_pose_optimization_batch(orb_matcher_t* m, int n_problems,
   return ORB_OK;
 }
 
+// --------------------------- SearchByProjection(F, LastF) as a device batch
+// (src/ORBmatcher.cc:1460-1619, src/Tracking.cc:1044-1083; track_kernels.hip)
+int orb_match_projection_frame_batch_max_stride(void) { return orb_k_frame_batch_max_stride(); }
+
+orb_status_t orb_match_projection_frame_batch(
+    orb_matcher_t* m, int n_problems, const orb_keypoint_t* d_keys, const uint8_t* d_desc,
+    const float* d_u_right, const uint8_t* d_locked, const int32_t* d_nkeys, int kp_stride,
+    const orb_pose_t* d_pose_cur, const orb_pose_t* d_pose_last,
+    const orb_keypoint_t* d_last_keys, const int32_t* d_last_nkeys,
+    const int32_t* d_last_point_index, const uint8_t* d_last_outlier,
+    const orb_map_point_t* d_points, const uint8_t* d_mp_desc, int mp_stride,
+    const orb_camera_t* cam, float min_x, float max_x, float min_y, float max_y, int n_levels,
+    const float* scale_factors, float th, int mono, int check_orientation, int retry_below,
+    int32_t* d_kp_match, orb_frame_match_info_t* d_info, void* stream) {
+  if (!m || n_problems < 0 || kp_stride <= 0 || mp_stride < 0 || !cam || !scale_factors ||
+      n_levels <= 0 || n_levels > ORB_MAX_LEVELS || !(max_x > min_x) || !(max_y > min_y) ||
+      !(th >= 0.0f) || retry_below < 0)
+    return ORB_EINVAL;
+  if (kp_stride > orb_k_frame_batch_max_stride()) return ORB_ECAPACITY;  // nothing is launched
+  if (n_problems == 0) return ORB_OK;
+  if (!d_keys || !d_desc || !d_nkeys || !d_pose_cur || !d_pose_last || !d_last_keys ||
+      !d_last_nkeys || !d_last_point_index || !d_points || !d_mp_desc || !d_kp_match || !d_info ||
+      n_problems > 65535)
+    return ORB_EINVAL;
+  std::lock_guard<std::mutex> g(m->mu);
+  hipSetDevice(m->device);
+  hipStream_t s = stream ? (hipStream_t)stream : m->stream;
+  CallOrder order(m->evLast, &m->lastStream, s);
+  if (order.status) return order.status;
+  orb_status_t st;
+  if ((st = m->dCellStart.ensure((size_t)n_problems * (ORB_GRID_COLS * ORB_GRID_ROWS + 1) * 4)))
+    return st;
+  if ((st = m->dCellIdx.ensure((size_t)n_problems * kp_stride * 4))) return st;
+  FrameBatchParams P;
+  memset(&P, 0, sizeof(P));
+  P.nProblems = n_problems;
+  P.stride = kp_stride;
+  P.mpStride = mp_stride;
+  P.minX = min_x; P.maxX = max_x; P.minY = min_y; P.maxY = max_y;
+  P.invW = (float)ORB_GRID_COLS / (max_x - min_x);
+  P.invH = (float)ORB_GRID_ROWS / (max_y - min_y);
+  P.fx = cam->fx; P.fy = cam->fy; P.cx = cam->cx; P.cy = cam->cy; P.bf = cam->bf; P.mb = cam->mb;
+  P.th = th;
+  P.nLevels = n_levels;
+  P.mono = mono ? 1 : 0;
+  P.checkOri = check_orientation ? 1 : 0;
+  P.retryBelow = retry_below;
+  for (int i = 0; i < n_levels; ++i) P.scale[i] = scale_factors[i];
+  HIP_TRY(orb_k_grid_build(d_keys, d_nkeys, kp_stride, P.minX, P.minY, P.invW, P.invH,
+                           m->dCellStart.as<int32_t>(), m->dCellIdx.as<int32_t>(), n_problems, s));
+  HIP_TRY(orb_k_frame_batch(&P, d_keys, d_desc, d_u_right, d_locked, d_nkeys, d_pose_cur,
+                            d_pose_last, d_last_keys, d_last_nkeys, d_last_point_index,
+                            d_last_outlier, d_points, d_mp_desc, m->dCellStart.as<int32_t>(),
+                            m->dCellIdx.as<int32_t>(), d_kp_match, d_info, s));
+  return ORB_OK;
+}
+
+orb_status_t orb_track_discard_outliers_batch(orb_matcher_t* m, int n_problems,
+                                              const int32_t* d_nkeys, int kp_stride,
+                                              int32_t* d_kp_match, uint8_t* d_outlier,
+                                              orb_map_point_t* d_points, int mp_stride,
+                                              int mark_seen,
+                                              const orb_frame_match_info_t* d_info,
+                                              orb_track_discard_info_t* d_out, void* stream) {
+  if (!m || n_problems < 0 || kp_stride <= 0 || mp_stride < 0 || (mark_seen && mp_stride == 0))
+    return ORB_EINVAL;
+  if (n_problems == 0) return ORB_OK;
+  if (!d_nkeys || !d_kp_match || !d_outlier || !d_points || !d_info || !d_out ||
+      n_problems > 65535)
+    return ORB_EINVAL;
+  std::lock_guard<std::mutex> g(m->mu);
+  hipSetDevice(m->device);
+  hipStream_t s = stream ? (hipStream_t)stream : m->stream;
+  HIP_TRY(orb_k_track_discard(n_problems, kp_stride, mp_stride, mark_seen ? 1 : 0, d_nkeys,
+                              d_kp_match, d_outlier, d_points, d_info, d_out, s));
+  return ORB_OK;
+}
+
 // ------------------------------------------------------------ synthetic input
 void orb_synth_image(uint64_t seed, int frame, int view, int width, int height, uint8_t* out,
                      size_t stride) {

@@ -1,0 +1,433 @@
+// track_kernels.hip -- gfx950 kernels of Tracking::TrackWithMotionModel's
+// matcher stage as a device-resident batch: SearchByProjection(CurrentFrame,
+// LastFrame, th, bMono) (src/ORBmatcher.cc:1460-1619) with the 2 * th retry
+// (src/Tracking.cc:1044-1052), and the "Discard outliers" loop (:1060-1083)
+// with SearchLocalPoints' already-matched marking (:1333-1354).
+//
+// k_frame_batch: one workgroup of four waves per problem, the problem's grid
+// built before it by k_grid_build.  Per pass: every wave projects last-frame
+// points with the poses read on the device and scans their windows, leaving
+// per point the first TOPK candidates in (distance, scan order), the count and
+// has_obs in LDS; wave 0 then replays the sequential loop over speculative
+// 64-point windows exactly as k_frame_resolve does (matcher_kernels.hip), with
+// every value on its serial chain in LDS: the candidate entries carry the
+// keypoint, the distance and the rotation bin, so the replay loads nothing from
+// global memory except in the exact re-scan of a point whose top-K ran dry;
+// all waves apply the rotation filter and count.  The workgroup itself decides
+// whether the problem runs again with 2 * th.
+#include <algorithm>
+
+#include "matcher_common.h"
+#include "orb_kernels.h"
+
+#define FB_T 256
+#define FB_STATIC_LDS ((size_t)512)  // budget for hist[32], ctl[4] and the block vote
+
+// Candidate entry: keypoint index (14b) | rotation bin (5b) << 14 | distance
+// (9b) << 19; the distance sits where Top4 reads it (cand_dist), an empty slot
+// is 0xFFFFFFFF (distance 511).
+__device__ __forceinline__ uint32_t fb_pack(int idx, int bin, int dist) {
+  return (uint32_t)idx | ((uint32_t)bin << 14) | ((uint32_t)dist << 19);
+}
+__device__ __forceinline__ int fb_idx(uint32_t e) { return (int)(e & 0x3FFFu); }
+__device__ __forceinline__ int fb_bin(uint32_t e) { return (int)((e >> 14) & 31u); }
+
+__device__ __forceinline__ bool fb_locked(const uint32_t* bm, int idx) {
+  return (bm[idx >> 5] >> (idx & 31)) & 1u;
+}
+
+// ((r0 x + r1 y) + r2 z) + t: cv::Mat's float product row by row, then the sum
+__device__ __forceinline__ float fb_row(const float* R, int r, float x, float y, float z, float t) {
+  return ((R[3 * r] * x + R[3 * r + 1] * y) + R[3 * r + 2] * z) + t;
+}
+
+struct FbWindow {
+  float u, v, invzc, radius;
+  int minL, maxL;
+};
+
+// src/ORBmatcher.cc:1489-1535 for last-frame keypoint m: false when the
+// reference skips the point before its window scan.  The octave is in range
+// (checked for the whole problem first).
+__device__ __forceinline__ bool fb_window(const FrameBatchParams& P, const float* Rcw,
+                                          const float* tcw, const orb_keypoint_t* lastKeys,
+                                          const int32_t* lastIdx, const uint8_t* lastOut,
+                                          const orb_map_point_t* pts, int m, float th, bool fwd,
+                                          bool bwd, FbWindow& w, int& pointIdx) {
+  const int pi = lastIdx[m];
+  pointIdx = pi;
+  if (pi < 0) return false;
+  if (lastOut && lastOut[m]) return false;
+  const float x = pts[pi].pos[0], y = pts[pi].pos[1], z = pts[pi].pos[2];
+  const float xc = fb_row(Rcw, 0, x, y, z, tcw[0]);
+  const float yc = fb_row(Rcw, 1, x, y, z, tcw[1]);
+  const float zc = fb_row(Rcw, 2, x, y, z, tcw[2]);
+  w.invzc = __fdiv_rn(1.0f, zc);
+  if (w.invzc < 0) return false;
+  w.u = P.fx * xc * w.invzc + P.cx;
+  w.v = P.fy * yc * w.invzc + P.cy;
+  if (w.u < P.minX || w.u > P.maxX) return false;
+  if (w.v < P.minY || w.v > P.maxY) return false;
+  const int o = lastKeys[m].octave;
+  w.radius = th * P.scale[o];
+  if (fwd) { w.minL = o; w.maxL = -1; }
+  else if (bwd) { w.minL = 0; w.maxL = o; }
+  else { w.minL = o - 1; w.maxL = o + 1; }
+  return true;
+}
+
+__global__ __launch_bounds__(FB_T) void k_frame_batch(
+    FrameBatchParams P, const orb_keypoint_t* __restrict__ keys, const uint8_t* __restrict__ desc,
+    const float* __restrict__ uright, const uint8_t* __restrict__ locked,
+    const int32_t* __restrict__ nkeys, const orb_pose_t* __restrict__ poseCur,
+    const orb_pose_t* __restrict__ poseLast, const orb_keypoint_t* __restrict__ lastKeys,
+    const int32_t* __restrict__ lastNkeys, const int32_t* __restrict__ lastPointIndex,
+    const uint8_t* __restrict__ lastOutlier, const orb_map_point_t* __restrict__ points,
+    const uint8_t* __restrict__ mpDesc, const int32_t* __restrict__ cellStart,
+    const int32_t* __restrict__ cellIdx, int32_t* __restrict__ kpMatch,
+    orb_frame_match_info_t* __restrict__ info) {
+  // LDS per keypoint slot: four candidate entries, the point's count | has_obs,
+  // its accepted keypoint | bin, the window's earliest claiming lane and the
+  // last point assigned per keypoint; then the lock bits
+  extern __shared__ __attribute__((aligned(16))) uint32_t dyn[];
+  __shared__ int hist[32];
+  __shared__ int ctl[4];  // accepted, removed
+  static_assert(sizeof(hist) + sizeof(ctl) + 256 <= FB_STATIC_LDS, "capacity rule counts these");
+  const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int S = (P.stride + 3) & ~3;
+  uint32_t* top = dyn;
+  int* meta = (int*)(dyn + 4 * (size_t)S);
+  int* acc = meta + S;
+  int* claimBy = acc + S;
+  int* lastWriter = claimBy + S;
+  uint32_t* bm = (uint32_t*)(lastWriter + S);
+
+  const int n = min(max(nkeys[p], 0), P.stride);
+  const int nlast = min(max(lastNkeys[p], 0), P.stride);
+  const int words = (n + 31) >> 5;
+  const size_t kb = (size_t)p * P.stride;
+  const orb_keypoint_t* K = keys + kb;
+  const uint8_t* D = desc + kb * 32;
+  const float* UR = uright ? uright + kb : nullptr;
+  const uint8_t* LK = locked ? locked + kb : nullptr;
+  const orb_keypoint_t* LKEYS = lastKeys + kb;
+  const int32_t* LIDX = lastPointIndex + kb;
+  const uint8_t* LOUT = lastOutlier ? lastOutlier + kb : nullptr;
+  const size_t mb = (size_t)p * (size_t)P.mpStride;
+  const orb_map_point_t* PTS = points + mb;
+  const uint8_t* MD = mpDesc + mb * 32;
+  const int32_t* cs = cellStart + (size_t)p * (GRID_CELLS + 1);
+  const int32_t* ci = cellIdx + kb;
+  int32_t* KM = kpMatch + kb;
+
+  // poses: Rcw, tcw of the current frame; the last frame's third row for tlc.z
+  float Rcw[9], tcw[3];
+  for (int i = 0; i < 9; ++i) Rcw[i] = poseCur[p].rcw[i];
+  for (int i = 0; i < 3; ++i) tcw[i] = poseCur[p].tcw[i];
+  float twc[3];  // src/ORBmatcher.cc:1475, as Frame::UpdatePoseMatrices' mOw
+  for (int i = 0; i < 3; ++i)
+    twc[i] = -((Rcw[i] * tcw[0] + Rcw[3 + i] * tcw[1]) + Rcw[6 + i] * tcw[2]);
+  const float tlcz = fb_row(poseLast[p].rcw, 2, twc[0], twc[1], twc[2], poseLast[p].tcw[2]);
+  const bool fwd = tlcz > P.mb && !P.mono;   // :1482
+  const bool bwd = -tlcz > P.mb && !P.mono;  // :1484
+
+  // an octave the scale table does not have: the problem is reported, not run
+  {
+    int bad = 0;
+    for (int m = tid; m < nlast; m += FB_T) {
+      if (LIDX[m] < 0 || (LOUT && LOUT[m])) continue;
+      const int o = LKEYS[m].octave;
+      bad |= (o < 0 || o >= P.nLevels);
+    }
+    if (__syncthreads_or(bad)) {
+      for (int i = tid; i < n; i += FB_T) KM[i] = -1;
+      if (tid == 0) {
+        info[p].n_matches = -1;
+        info[p].n_matches_first_pass = -1;
+        info[p].retried = 0;
+        info[p].forward = fwd;
+        info[p].backward = bwd;
+      }
+      return;
+    }
+  }
+
+  ProjParams G;  // the grid geometry for_features_in_area reads
+  G.minX = P.minX; G.minY = P.minY; G.invW = P.invW; G.invH = P.invH;
+
+  float th = P.th;
+  int first = 0, retried = 0, nm = 0;
+  for (int pass = 0;; ++pass) {
+    for (int i = tid; i < words; i += FB_T) bm[i] = 0u;
+    for (int i = tid; i < n; i += FB_T) { claimBy[i] = 64; lastWriter[i] = -1; }
+    if (tid < 32) hist[tid] = 0;
+    if (tid < 4) ctl[tid] = 0;
+
+    // ---- projection and candidate scan, a point per thread
+    for (int m = tid; m < nlast; m += FB_T) {
+      FbWindow w;
+      int pi;
+      Top4 t4;
+      int count = -1, hasObs = 0;
+      if (fb_window(P, Rcw, tcw, LKEYS, LIDX, LOUT, PTS, m, th, fwd, bwd, w, pi)) {
+        hasObs = PTS[pi].has_obs != 0;
+        const ulonglong4 q = load_desc(MD + (size_t)pi * 32);
+        const float la = LKEYS[m].angle;
+        count = 0;
+        for_features_in_area(K, cs, ci, G, w.u, w.v, w.radius, w.minL, w.maxL,
+                             [&](int idx, const orb_keypoint_t& kp) {
+                               if (idx >= n) return;
+                               if (LK && LK[idx]) return;
+                               if (UR && UR[idx] > 0) {
+                                 const float ur = w.u - P.bf * w.invzc;
+                                 const float er = fabsf(ur - UR[idx]);
+                                 if (er > w.radius) return;
+                               }
+                               const int dist = hamming256(q, load_desc(D + (size_t)idx * 32));
+                               if (dist >= 256) return;
+                               ++count;
+                               const int bin = P.checkOri ? rot_bin(la - kp.angle) : 0;
+                               t4.insert(fb_pack(idx, bin, dist), dist);
+                             });
+      }
+      t4.store(top + (size_t)m * TOPK);
+      meta[m] = count < 0 ? -1 : (count | (hasObs << 24));
+      acc[m] = -1;
+    }
+    __syncthreads();
+
+    // ---- the ordered replay, wave 0 (k_frame_resolve's windows)
+    if (wave == 0) {
+      int start = 0;
+      while (start < nlast) {
+        const int m = start + lane;
+        const bool active = m < nlast;
+        int nc = -1;
+        uint32_t e[TOPK] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
+        bool hasObs = false;
+        if (active) {
+          const int mt = meta[m];
+          nc = mt < 0 ? -1 : (mt & 0xFFFFFF);
+          hasObs = mt >= 0 && (mt >> 24) != 0;
+          const uint4 t = *reinterpret_cast<const uint4*>(top + (size_t)m * TOPK);
+          e[0] = t.x; e[1] = t.y; e[2] = t.z; e[3] = t.w;
+        }
+        int best = -1, bestDist = 256, bestBin = 0, consumed = 0;
+        const int avail = nc < TOPK ? nc : TOPK;  // <= 0: no candidate
+#pragma unroll
+        for (int j = 0; j < TOPK; ++j) {
+          if (j < avail && best < 0) {
+            ++consumed;
+            if (!fb_locked(bm, fb_idx(e[j]))) {
+              best = fb_idx(e[j]);
+              bestDist = cand_dist(e[j]);
+              bestBin = fb_bin(e[j]);
+            }
+          }
+        }
+        const bool slow = nc > TOPK && best < 0;
+        const bool accept = !slow && best >= 0 && bestDist <= 100;  // TH_HIGH
+        const bool locks = accept && hasObs;
+        if (locks) atomicMin(&claimBy[best], lane);
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        bool conflict = false;
+#pragma unroll
+        for (int q = 0; q < TOPK; ++q)
+          if (q < consumed) conflict |= claimBy[fb_idx(e[q])] < lane;
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        if (locks) claimBy[best] = 64;
+        const unsigned long long bad = __ballot(active && (conflict || (slow && lane > 0)));
+        const unsigned long long slowFirst = __ballot(lane == 0 && active && slow);
+        int commit = bad ? (int)__builtin_ctzll(bad) : 64;
+        if (slowFirst) {
+          if (lane == 0) {  // exact re-scan against the current locks
+            FbWindow w;
+            int pi;
+            fb_window(P, Rcw, tcw, LKEYS, LIDX, LOUT, PTS, m, th, fwd, bwd, w, pi);
+            const ulonglong4 q = load_desc(MD + (size_t)pi * 32);
+            int bd = 256, bi = -1;
+            for_features_in_area(K, cs, ci, G, w.u, w.v, w.radius, w.minL, w.maxL,
+                                 [&](int idx, const orb_keypoint_t& kp) {
+                                   if (idx >= n) return;
+                                   if ((LK && LK[idx]) || fb_locked(bm, idx)) return;
+                                   if (UR && UR[idx] > 0) {
+                                     const float ur = w.u - P.bf * w.invzc;
+                                     if (fabsf(ur - UR[idx]) > w.radius) return;
+                                   }
+                                   const int dist =
+                                       hamming256(q, load_desc(D + (size_t)idx * 32));
+                                   if (dist < bd) { bd = dist; bi = idx; }
+                                 });
+            if (bd <= 100) {
+              const int bin = P.checkOri ? rot_bin(LKEYS[m].angle - K[bi].angle) : 0;
+              acc[m] = bi | (bin << 16);
+              atomicMax(&lastWriter[bi], m);
+              if (hasObs) bm[bi >> 5] |= 1u << (bi & 31);
+              if (P.checkOri) atomicAdd(&hist[bin], 1);
+            }
+          }
+          commit = 1;
+        } else {
+          if (active && lane < commit && accept) {
+            acc[m] = best | (bestBin << 16);
+            atomicMax(&lastWriter[best], m);
+            if (locks) atomicOr(&bm[best >> 5], 1u << (best & 31));
+            if (P.checkOri) atomicAdd(&hist[bestBin], 1);
+          }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        start += commit;
+      }
+    }
+    __syncthreads();
+
+    // ---- rotation filter (:1597-1616): the records of the bins outside the
+    // top three are undone; bm becomes "reset to NULL by the filter"
+    int ind1 = -1, ind2 = -1, ind3 = -1;
+    if (P.checkOri) three_maxima(hist, ind1, ind2, ind3);
+    for (int i = tid; i < words; i += FB_T) bm[i] = 0u;
+    __syncthreads();
+    int removed = 0, accepted = 0;
+    for (int m = tid; m < nlast; m += FB_T) {
+      const int a = acc[m];
+      if (a < 0) continue;
+      ++accepted;
+      if (!P.checkOri) continue;
+      const int b = a >> 16, bi = a & 0xFFFF;
+      if (b != ind1 && b != ind2 && b != ind3) {
+        ++removed;
+        atomicOr(&bm[bi >> 5], 1u << (bi & 31));
+      }
+    }
+    accepted = wave_sum(accepted);
+    removed = wave_sum(removed);
+    if (lane == 0) {
+      atomicAdd(&ctl[0], accepted);
+      atomicAdd(&ctl[1], removed);
+    }
+    __syncthreads();
+    nm = ctl[0] - ctl[1];
+    if (pass == 0) first = nm;
+    if (pass == 0 && P.retryBelow > 0 && nm < P.retryBelow) {  // src/Tracking.cc:1048-1052
+      retried = 1;
+      th = 2.0f * P.th;
+      __syncthreads();  // ctl and bm are read before the next pass clears them
+      continue;
+    }
+    break;
+  }
+
+  // kp_match: the map-point index assigned by the (last) pass, -1 untouched,
+  // -2 reset to NULL by the filter
+  for (int i = tid; i < n; i += FB_T) {
+    const int wr = lastWriter[i];
+    if ((bm[i >> 5] >> (i & 31)) & 1u) KM[i] = -2;
+    else KM[i] = wr >= 0 ? LIDX[wr] : -1;
+  }
+  if (tid == 0) {
+    info[p].n_matches = nm;
+    info[p].n_matches_first_pass = first;
+    info[p].retried = retried;
+    info[p].forward = fwd;
+    info[p].backward = bwd;
+  }
+}
+
+// dynamic LDS of one k_frame_batch workgroup at `stride` keypoint slots
+static size_t frame_batch_lds(int stride) {
+  const size_t S = ((size_t)stride + 3) & ~(size_t)3;
+  const size_t W = ((S + 31) / 32 + 3) & ~(size_t)3;
+  return (8 * S + W) * 4;
+}
+
+extern "C" int orb_k_frame_batch_max_stride(void) {
+  // 32 B and one bit per slot, plus the static part, within 160 KiB; the
+  // candidate entries hold 14 index bits
+  int s = (int)((ORB_LDS_PER_CU - FB_STATIC_LDS) / 32) & ~3;
+  while (frame_batch_lds(s) + FB_STATIC_LDS > ORB_LDS_PER_CU) s -= 4;
+  return std::min(s, (1 << 14) - 4);
+}
+
+extern "C" hipError_t orb_k_frame_batch(
+    const FrameBatchParams* params, const orb_keypoint_t* keys, const uint8_t* desc,
+    const float* uright, const uint8_t* locked, const int32_t* nkeys, const orb_pose_t* poseCur,
+    const orb_pose_t* poseLast, const orb_keypoint_t* lastKeys, const int32_t* lastNkeys,
+    const int32_t* lastPointIndex, const uint8_t* lastOutlier, const orb_map_point_t* points,
+    const uint8_t* mpDesc, const int32_t* cellStart, const int32_t* cellIdx, int32_t* kpMatch,
+    orb_frame_match_info_t* info, hipStream_t s) {
+  const FrameBatchParams P = *params;
+  if (P.stride <= 0 || P.stride > orb_k_frame_batch_max_stride()) return hipErrorInvalidValue;
+  const size_t lds = frame_batch_lds(P.stride);
+  if (lds > 65536 - FB_STATIC_LDS) {
+    hipError_t e = hipFuncSetAttribute((const void*)k_frame_batch,
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(k_frame_batch, dim3(P.nProblems), dim3(FB_T), lds, s, P, keys, desc, uright,
+                     locked, nkeys, poseCur, poseLast, lastKeys, lastNkeys, lastPointIndex,
+                     lastOutlier, points, mpDesc, cellStart, cellIdx, kpMatch, info);
+  return hipGetLastError();
+}
+
+// ------------------------------------------------ discard outliers and mark
+// src/Tracking.cc:1060-1083 over one problem's keypoints, then (markSeen) the
+// first loop of SearchLocalPoints (:1333-1354) on what is kept.  Several
+// keypoints may hold one point: their `seen` stores write the same byte value.
+__global__ __launch_bounds__(256) void k_track_discard(
+    int stride, long long mpStride, int markSeen, const int32_t* __restrict__ nkeys,
+    int32_t* __restrict__ kpMatch, uint8_t* __restrict__ outlier, orb_map_point_t* points,
+    const orb_frame_match_info_t* __restrict__ info, orb_track_discard_info_t* __restrict__ out) {
+  __shared__ int cnt[2];
+  const int p = blockIdx.x, tid = threadIdx.x;
+  const int n = min(max(nkeys[p], 0), stride);
+  int32_t* KM = kpMatch + (size_t)p * stride;
+  uint8_t* OL = outlier + (size_t)p * stride;
+  orb_map_point_t* PTS = points + (size_t)p * (size_t)mpStride;
+  if (tid < 2) cnt[tid] = 0;
+  __syncthreads();
+  int discarded = 0, inMap = 0;
+  for (int i = tid; i < n; i += 256) {
+    const int pi = KM[i];
+    if (pi < 0) continue;
+    if (OL[i]) {
+      KM[i] = -1;
+      OL[i] = 0;
+      if (markSeen) PTS[pi].seen = 1;  // mnLastFrameSeen = mCurrentFrame.mnId (:1076)
+      ++discarded;
+    } else {
+      if (PTS[pi].has_obs) ++inMap;
+      if (markSeen) {
+        if (PTS[pi].bad) KM[i] = -1;  // :1340-1343
+        else PTS[pi].seen = 1;        // :1350
+      }
+    }
+  }
+  discarded = wave_sum(discarded);
+  inMap = wave_sum(inMap);
+  if ((tid & 63) == 0) {
+    atomicAdd(&cnt[0], discarded);
+    atomicAdd(&cnt[1], inMap);
+  }
+  __syncthreads();
+  if (tid == 0) {
+    out[p].n_discarded = cnt[0];
+    out[p].n_matches_map = cnt[1];
+    out[p].n_matches = info[p].n_matches - cnt[0];
+  }
+}
+
+extern "C" hipError_t orb_k_track_discard(int nProblems, int stride, long long mpStride,
+                                          int markSeen, const int32_t* nkeys, int32_t* kpMatch,
+                                          uint8_t* outlier, orb_map_point_t* points,
+                                          const orb_frame_match_info_t* info,
+                                          orb_track_discard_info_t* out, hipStream_t s) {
+  hipLaunchKernelGGL(k_track_discard, dim3(nProblems), dim3(256), 0, s, stride, mpStride,
+                     markSeen, nkeys, kpMatch, outlier, points, info, out);
+  return hipGetLastError();
+}

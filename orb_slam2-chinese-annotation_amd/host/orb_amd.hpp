@@ -790,6 +790,47 @@ class ORBmatcher {
           "pose_optimization_batch");
   }
 
+  // Device-batched SearchByProjection(CurrentFrame, LastFrame, th, bMono) with
+  // TrackWithMotionModel's 2 * th retry below retry_below matches
+  // (orb_match_projection_frame_batch; src/ORBmatcher.cc:1460-1619,
+  // src/Tracking.cc:1044-1052).  d_kp_match is pose_optimization_batch's
+  // d_point_index (d_points, sizeof(orb_map_point_t), mp_stride).
+  void search_by_projection_frame_batch(
+      int n_problems, const KeyPoint* d_keys, const uint8_t* d_desc, const float* d_u_right,
+      const uint8_t* d_locked, const int32_t* d_nkeys, int kp_stride, const orb_pose_t* d_pose_cur,
+      const orb_pose_t* d_pose_last, const KeyPoint* d_last_keys, const int32_t* d_last_nkeys,
+      const int32_t* d_last_point_index, const uint8_t* d_last_outlier,
+      const orb_map_point_t* d_points, const uint8_t* d_mp_desc, int mp_stride,
+      const orb_camera_t& cam, float min_x, float max_x, float min_y, float max_y,
+      const std::vector<float>& mvScaleFactors, float th, bool bMono, int retry_below,
+      int32_t* d_kp_match, orb_frame_match_info_t* d_info, void* stream = nullptr) {
+    check(orb_match_projection_frame_batch(
+              h_, n_problems, d_keys, d_desc, d_u_right, d_locked, d_nkeys, kp_stride, d_pose_cur,
+              d_pose_last, d_last_keys, d_last_nkeys, d_last_point_index, d_last_outlier, d_points,
+              d_mp_desc, mp_stride, &cam, min_x, max_x, min_y, max_y, (int)mvScaleFactors.size(),
+              mvScaleFactors.data(), th, bMono ? 1 : 0, mbCheckOrientation ? 1 : 0, retry_below,
+              d_kp_match, d_info, stream),
+          "search_by_projection_frame_batch");
+  }
+  static int search_by_projection_frame_batch_max_stride() {
+    return orb_match_projection_frame_batch_max_stride();
+  }
+
+  // TrackWithMotionModel's "Discard outliers" loop (src/Tracking.cc:1060-1083)
+  // and, with mark_seen, SearchLocalPoints' already-matched marking
+  // (:1333-1354) in the problems' own map-point records
+  // (orb_track_discard_outliers_batch).
+  void track_discard_outliers_batch(int n_problems, const int32_t* d_nkeys, int kp_stride,
+                                    int32_t* d_kp_match, uint8_t* d_outlier,
+                                    orb_map_point_t* d_points, int mp_stride, bool mark_seen,
+                                    const orb_frame_match_info_t* d_info,
+                                    orb_track_discard_info_t* d_out, void* stream = nullptr) {
+    check(orb_track_discard_outliers_batch(h_, n_problems, d_nkeys, kp_stride, d_kp_match,
+                                           d_outlier, d_points, mp_stride, mark_seen ? 1 : 0,
+                                           d_info, d_out, stream),
+          "track_discard_outliers_batch");
+  }
+
   float mfNNratio;
   bool mbCheckOrientation;
   orb_matcher_t* handle() { return h_; }

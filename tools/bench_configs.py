@@ -33,6 +33,13 @@ results table:
       20 % gross outliers), device-resident (problems/s by device events), the
       one-problem latency through the host-buffer call, the batch's share of
       the headline step + exact check against tests/poseopt_ref.py
+  M1  TrackWithMotionModel's SearchByProjection(CurrentFrame, LastFrame): 1,024
+      problems of the C4 shape per launch (1241x376, 1,000 keypoints, map
+      points on about 80 % of the last frame's keypoints, a rotated predicted
+      pose, th 15, retry below 20), device-resident, by device events (median
+      of 20), also 1, 64 and 256 problems; against orb_match_projection_frame
+      over the same problems one call at a time (host clock; run once more
+      with ORB_AMD_LIB naming the parent build for the baseline) + exact check
   R1  RGB-D: 640x480 (TUM1 intrinsics and distortion, DepthMapFactor 5000),
       1000 features, 256 frames per launch, device-resident: extract ->
       undistort -> ComputeStereoFromRGBD -> closest points + UnprojectStereo ->
@@ -40,7 +47,7 @@ results table:
       same pipeline without the RGB-D stages (monocular matcher), each new
       kernel alone by HIP events with its algorithmic bytes + exact check
 
-Usage: python tools/bench_configs.py [--configs C1,C2,C3,C5,F1,F3,P1,R1,T1] [--steps K]
+Usage: python tools/bench_configs.py [--configs C1,C2,C3,C5,F1,F3,P1,R1,T1,M1] [--steps K]
 The oracle (CPU restatement) is used only for the CPU rows and parity checks.
 """
 import argparse
@@ -652,6 +659,128 @@ def t1(args, orb, oracle, torch):
             "lds_edges": m.pose_optimization_lds_edges(), "bit_exact_4_problems": bool(exact)}
 
 
+def m1(args, orb, oracle, torch):
+    import scenarios as S
+    import track_motion_ref as R
+    B, DISTINCT, TH, RETRY = 1024, 32, 15.0, 20
+    W, H = 1241, 376
+    rng = np.random.default_rng(SEED)
+    probs, scale = [], None
+    for i in range(DISTINCT):  # frame_pair scenes: frames 0 and 1 of sequence 40 + i
+        fp = S.frame_pair(oracle, 40 + i, rng_seed=i)
+        last = fp["last"].copy()
+        last["valid"] = rng.random(len(last)) < 0.8
+        scale = fp["scale"]
+        pr = R.problem_from_records(fp["kb"], fp["db"], last, fp["last_desc"], 0.0)
+        Rm, t, _ = S.pose(rng)
+        pts = pr["points"].copy()
+        pts["pos"] = ((pts["pos"].astype(np.float64) - t.astype(np.float64))
+                      @ Rm.astype(np.float64)).astype(np.float32)
+        pr["points"], pr["pose_cur"] = pts, R.pose(Rm, t)
+        pr["pose_last"] = R.pose(Rm, t + np.array([0, 0, 0.3], np.float32))
+        probs.append(pr)
+    stride = max(max(len(p["keys"]), len(p["last_keys"])) for p in probs)
+    keys = np.zeros((B, stride), orb.KEYPOINT_DTYPE)
+    desc = np.zeros((B, stride, 32), np.uint8)
+    lkeys = np.zeros((B, stride), orb.KEYPOINT_DTYPE)
+    lidx = np.full((B, stride), -1, np.int32)
+    pts = np.zeros((B, stride), orb.MAP_POINT_DTYPE)
+    md = np.zeros((B, stride, 32), np.uint8)
+    nk, ln = np.zeros(B, np.int32), np.zeros(B, np.int32)
+    pc, pl = np.zeros(B, orb.POSE_DTYPE), np.zeros(B, orb.POSE_DTYPE)
+    for p in range(B):
+        pr = probs[p % DISTINCT]
+        n, m = len(pr["keys"]), len(pr["last_keys"])
+        keys[p, :n], desc[p, :n], nk[p] = pr["keys"], pr["desc"], n
+        lkeys[p, :m], lidx[p, :m], ln[p] = pr["last_keys"], pr["last_point_index"], m
+        pts[p, :m], md[p, :m] = pr["points"][:m], pr["mp_desc"][:m]
+        pc[p], pl[p] = pr["pose_cur"][0], pr["pose_last"][0]
+    cam = S.camera()
+    m = orb.ORBmatcher(0.9, True)
+    # one call at a time through the one-problem entry, host-projected records
+    recs = []
+    for pr in probs:
+        last, ld = R.last_records(pr["pose_cur"], pr["last_keys"], pr["last_point_index"], None,
+                                  pr["points"], pr["mp_desc"])
+        recs.append((orb.Frame(pr["keys"], pr["desc"], scale, W, H), last, ld,
+                     float(R.tlc(pr["pose_cur"], pr["pose_last"])[2])))
+
+    def one(i, th=TH):
+        F, last, ld, tz = recs[i]
+        return m.SearchByProjectionFrame(F, last, ld, cam, tz, th, True)
+    for i in range(DISTINCT):
+        one(i)
+    lat = []
+    for rep in range(4):
+        for i in range(DISTINCT):
+            t0 = time.perf_counter()
+            one(i)
+            lat.append((time.perf_counter() - t0) * 1e3)
+    lat.sort()
+    out = {"config": "M1", "library": str(orb.LIB_PATH),
+           "workload": f"SearchByProjection(F, LastF), {B} problems x {stride} keypoint slots, "
+                       f"{int(np.mean([(p['last_point_index'] >= 0).sum() for p in probs]))} "
+                       f"last-frame map points on average, th {TH}, retry below {RETRY} "
+                       f"({DISTINCT} distinct problems)",
+           "one_call_ms_median": lat[len(lat) // 2], "one_call_ms_min": lat[0],
+           "one_call_ms_max": lat[-1], "one_call_samples": len(lat)}
+    if not hasattr(orb.lib(), "orb_match_projection_frame_batch"):
+        return out  # a build from before the batch entry: the baseline row only
+
+    def dev(a):
+        return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).cuda()
+    d = {k: dev(a) for k, a in dict(keys=keys, desc=desc, lkeys=lkeys, lidx=lidx, pts=pts, md=md,
+                                    nk=nk, ln=ln, pc=pc, pl=pl).items()}
+    d_km = torch.zeros(B * stride, dtype=torch.int32, device="cuda")
+    d_info = torch.zeros(B * 5, dtype=torch.int32, device="cuda")
+    stream = torch.cuda.Stream()
+
+    def run(nprob=B):
+        m.search_by_projection_frame_batch(
+            nprob, d["keys"].data_ptr(), d["desc"].data_ptr(), 0, 0, d["nk"].data_ptr(), stride,
+            d["pc"].data_ptr(), d["pl"].data_ptr(), d["lkeys"].data_ptr(), d["ln"].data_ptr(),
+            d["lidx"].data_ptr(), 0, d["pts"].data_ptr(), d["md"].data_ptr(), stride, cam, 0.0,
+            float(W), 0.0, float(H), scale, TH, True, RETRY, d_km.data_ptr(), d_info.data_ptr(),
+            stream=stream.cuda_stream)
+
+    def events(nprob, reps):
+        t = []
+        for _ in range(reps):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            run(nprob)
+            e1.record(stream)
+            torch.cuda.synchronize()
+            t.append(e0.elapsed_time(e1))
+        return sorted(t)
+    for _ in range(3):
+        run()
+    torch.cuda.synchronize()
+    ms = events(B, 20)
+    by_size = {str(n): events(n, 20)[10] for n in (1, 64, 256)}
+    run()
+    torch.cuda.synchronize()
+    km = d_km.cpu().numpy().reshape(B, stride)
+    info = d_info.cpu().numpy().view(orb.FRAME_MATCH_INFO_DTYPE)
+    exact = True
+    for p in (0, 1, DISTINCT + 1, B - 1):
+        i = p % DISTINCT
+        n1, km1 = one(i)
+        if n1 < RETRY:
+            n1, km1 = one(i, 2.0 * TH)
+        exact &= n1 == int(info[p]["n_matches"]) and bool(np.array_equal(km1, km[p, :len(km1)]))
+    batch_ms = ms[len(ms) // 2]
+    out.update({"batch_ms_median": batch_ms, "batch_ms_min": ms[0], "batch_ms_max": ms[-1],
+                "launch_ms_by_problems": by_size, "problems_per_s": B / (batch_ms * 1e-3),
+                "batch_us_per_problem": batch_ms * 1e3 / B,
+                "one_call_over_batch_per_problem": lat[len(lat) // 2] / (batch_ms / B),
+                "matches_mean": float(info["n_matches"].mean()),
+                "retried": int(info["retried"].sum()), "kp_stride": stride,
+                "max_stride": m.search_by_projection_frame_batch_max_stride(),
+                "exact_vs_one_problem_entry_4_problems": bool(exact)})
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--configs", default="C1,C2,C3,C5")
@@ -686,6 +815,8 @@ def main():
             r = r1(args, orb, oracle, torch)
         elif c == "T1":
             r = t1(args, orb, oracle, torch)
+        elif c == "M1":
+            r = m1(args, orb, oracle, torch)
         else:
             raise SystemExit(f"unknown config {c}")
         print(json.dumps(r), flush=True)
