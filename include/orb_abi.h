@@ -73,6 +73,11 @@
  *                                  3x3 * vector as ((r0 x + r1 y) + r2 z) + t, invzc = 1.0f / z
  *   orb_track_discard_outliers_batch  "Discard outliers" src/Tracking.cc:1060-1083 and the
  *                                  already-matched marking of SearchLocalPoints :1333-1354
+ *   orb_match_bow_batch            device-batched SearchByBoW(KeyFrame*, Frame&, ...)
+ *                                  src/ORBmatcher.cc:164-306 as TrackReferenceKeyFrame
+ *                                  src/Tracking.cc:904-954 and Relocalization :1592-1616 call it
+ *   orb_track_discard_outliers_batch_n  the discard loop with the match count read through a
+ *                                  strided pointer (src/Tracking.cc:928-951 after SearchByBoW)
  *   orb_vocabulary_create / _load_text / _destroy
  *                                  DBoW2 TemplatedVocabulary ctor + loadFromTextFile
  *                                  Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:1362-1448
@@ -945,6 +950,84 @@ orb_status_t orb_track_discard_outliers_batch(orb_matcher_t* m, int n_problems,
                                               int mark_seen,
                                               const orb_frame_match_info_t* d_info,
                                               orb_track_discard_info_t* d_out, void* stream);
+/* The same with the match counts read from d_n_matches[p * n_matches_stride]
+ * (int32 units, >= 1): the first field of either matcher's info array, stride
+ * 5 for orb_frame_match_info_t and orb_bow_match_info_t alike
+ * (TrackReferenceKeyFrame's loop, src/Tracking.cc:928-951, takes its count from
+ * SearchByBoW).  orb_track_discard_outliers_batch is this entry with
+ * &d_info->n_matches and 5. */
+orb_status_t orb_track_discard_outliers_batch_n(orb_matcher_t* m, int n_problems,
+                                                const int32_t* d_nkeys, int kp_stride,
+                                                int32_t* d_kp_match, uint8_t* d_outlier,
+                                                orb_map_point_t* d_points, int mp_stride,
+                                                int mark_seen, const int32_t* d_n_matches,
+                                                int n_matches_stride,
+                                                orb_track_discard_info_t* d_out, void* stream);
+
+/* Device-batched SearchByBoW(pKF, F, vpMapPointMatches) (src/ORBmatcher.cc:
+ * 164-306) as Tracking::TrackReferenceKeyFrame (src/Tracking.cc:904-954) and
+ * Relocalization's candidate loop (:1592-1616) call it: n_problems independent
+ * problems in one launch, every array a device pointer, asynchronous on
+ * `stream`, no host synchronisation, upload or download.
+ * Slots: slot k of the keyframe side (d_kf_*) and of the frame side (d_f_*) is
+ * what orb_extractor_extract_batch and orb_vocabulary_transform_batch write
+ * with stride kp_stride: keys, point_index, fv_nodes and fv_feats at
+ * k * kp_stride, descriptors at 32 * k * kp_stride, fv_offs at
+ * k * (kp_stride + 1), the counts nkeys[k] and n_fv_nodes[k].  Of the keys only
+ * `angle` is read.  The two sides may be the same allocation.
+ * Problem p matches keyframe slot d_kf_index[p] against frame slot
+ * d_f_index[p] (either NULL: slot p; a slot may serve many problems; the
+ * caller keeps the slot numbers inside the arrays).  d_kf_point_index[i] >= 0
+ * names mvpMapPoints[i] in d_points + p * mp_stride (mp_stride 0: one array
+ * shared by all problems), any negative value is NULL; isBad() is that
+ * record's `bad` byte (d_points NULL: no point is bad); the caller keeps the
+ * indices inside the array.
+ * Out: d_kp_match + p * kp_stride, the first d_f_nkeys[slot] entries (the rest
+ * is not written): the point index assigned to the frame keypoint or -1;
+ * matches removed by the rotation filter are -1, as in orb_match_bow.  With
+ * identity frame indices this is orb_pose_optimization_batch's d_point_index
+ * (with d_points, sizeof(orb_map_point_t), mp_stride).  d_info[p] as below.
+ * Per problem the result is orb_match_bow's on the same inputs.
+ * min_matches (Tracking: 15; 0: no gate): a problem with fewer matches keeps
+ * its counts, gets enough = 0 and every kp_match entry -1 (Tracking returns
+ * before it assigns mvpMapPoints).
+ * Malformed slots are found on the device: counts are clamped to
+ * [0, kp_stride] and n_fv_nodes to [0, count]; an offset that decreases (or a
+ * negative first one), an offset above the slot's count or a feature index >=
+ * the slot's count in either FeatureVector gives n_matches = -1, the other
+ * fields 0 and kp_match all -1 over the clamped count, and nothing is indexed
+ * with the bad value.  Ascending node ids are the caller's promise and are
+ * NOT checked (the merge-join is a binary search over them).
+ * Capacity: one workgroup per problem keeps 8 bytes per keypoint slot in LDS
+ * (the match word per frame keypoint and the partner node per keyframe node):
+ * 8 * ((kp_stride + 3) & ~3) + 512 bytes must fit the 160 KiB of one CU;
+ * orb_match_bow_batch_max_stride() is the largest such kp_stride (a pure
+ * function, callable without a device; every stride
+ * orb_vocabulary_transform_batch accepts is below it).  Above it:
+ * ORB_ECAPACITY before anything is launched, nothing is written.
+ * ORB_EINVAL: a null required pointer, n_problems < 0, kp_stride <= 0,
+ * mp_stride < 0, nnratio not finite.  n_problems == 0: ORB_OK, no launch.
+ * The call takes the handle's mutex; its kernel keeps all state in LDS and the
+ * caller's arrays and uses none of the handle's scratch, so it is ordered by
+ * `stream` alone. */
+typedef struct orb_bow_match_info {
+  int32_t n_matches;      /* the return value (after the rotation filter); -1: malformed slot */
+  int32_t n_accepted;     /* nmatches before the filter (src/ORBmatcher.cc:262) */
+  int32_t n_common_nodes; /* node ids present in both FeatureVectors */
+  int32_t n_tried;        /* KF keypoints of common nodes with a non-NULL, non-bad MapPoint */
+  int32_t enough;         /* n_matches >= min_matches */
+} orb_bow_match_info_t;   /* 20 bytes */
+orb_status_t orb_match_bow_batch(
+    orb_matcher_t* m, int n_problems, const int32_t* d_kf_index, const int32_t* d_f_index,
+    const orb_keypoint_t* d_kf_keys, const uint8_t* d_kf_desc, const int32_t* d_kf_nkeys,
+    const int32_t* d_kf_point_index, const uint32_t* d_kf_fv_nodes, const int32_t* d_kf_fv_offs,
+    const uint32_t* d_kf_fv_feats, const int32_t* d_kf_n_fv_nodes,
+    const orb_keypoint_t* d_f_keys, const uint8_t* d_f_desc, const int32_t* d_f_nkeys,
+    const uint32_t* d_f_fv_nodes, const int32_t* d_f_fv_offs, const uint32_t* d_f_fv_feats,
+    const int32_t* d_f_n_fv_nodes, int kp_stride, const orb_map_point_t* d_points,
+    long long mp_stride, float nnratio, int check_orientation, int min_matches,
+    int32_t* d_kp_match, orb_bow_match_info_t* d_info, void* stream);
+int orb_match_bow_batch_max_stride(void);
 
 /* ------------------------------------------------------ DBoW2 vocabulary */
 

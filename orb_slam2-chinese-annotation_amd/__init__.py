@@ -54,6 +54,8 @@ FRAME_MATCH_INFO_DTYPE = np.dtype([("n_matches", "<i4"), ("n_matches_first_pass"
                                    ("retried", "<i4"), ("forward", "<i4"), ("backward", "<i4")])
 TRACK_DISCARD_INFO_DTYPE = np.dtype([("n_matches", "<i4"), ("n_matches_map", "<i4"),
                                      ("n_discarded", "<i4")])
+BOW_MATCH_INFO_DTYPE = np.dtype([("n_matches", "<i4"), ("n_accepted", "<i4"),
+                                 ("n_common_nodes", "<i4"), ("n_tried", "<i4"), ("enough", "<i4")])
 ORB_DEPTH_U16, ORB_DEPTH_F32 = 0, 1
 
 
@@ -213,13 +215,19 @@ def lib() -> ctypes.CDLL:
         "orb_match_projection_frame_batch_max_stride": (i32, []),
         "orb_track_discard_outliers_batch": (i32, [vp, i32, vp, i32, vp, vp, vp, i32, i32, vp, vp,
                                                    vp]),
+        "orb_track_discard_outliers_batch_n": (i32, [vp, i32, vp, i32, vp, vp, vp, i32, i32, vp,
+                                                     i32, vp, vp]),
+        "orb_match_bow_batch": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                      vp, vp, vp, vp, i32, vp, i64, f32, i32, i32, vp, vp, vp]),
+        "orb_match_bow_batch_max_stride": (i32, []),
         "orb_synth_image": (None, [ctypes.c_uint64, i32, i32, i32, i32, vp, sz]),
         "orb_synth_local_map": (None, [ctypes.c_uint64, vp, vp, i32, i32, i32, i32, vp, vp, vp]),
     }
     # entries an older build named by ORB_AMD_LIB (a baseline for an A/B
     # measurement) does not have; calling one there is an AttributeError
     newer = ("orb_match_projection_frame_batch", "orb_match_projection_frame_batch_max_stride",
-             "orb_track_discard_outliers_batch")
+             "orb_track_discard_outliers_batch", "orb_track_discard_outliers_batch_n",
+             "orb_match_bow_batch", "orb_match_bow_batch_max_stride")
     for name, (res, args) in sig.items():
         if name in newer and "ORB_AMD_LIB" in os.environ and not hasattr(L, name):
             continue
@@ -252,6 +260,12 @@ def _check(status: int, what: str) -> int:
 
 def _ptr(a: np.ndarray) -> int:
     return a.ctypes.data
+
+
+def match_bow_batch_max_stride() -> int:
+    """orb_match_bow_batch_max_stride(): a pure function of k_bow_batch's LDS
+    layout, callable without a device."""
+    return lib().orb_match_bow_batch_max_stride()
 
 
 def device_count() -> int:
@@ -1181,6 +1195,44 @@ class ORBmatcher:
         _check(lib().orb_track_discard_outliers_batch(
             self._h, n_problems, d_nkeys, kp_stride, d_kp_match, d_outlier, d_points, mp_stride,
             int(bool(mark_seen)), d_info, d_out, stream or None), "track_discard_outliers_batch")
+
+    def track_discard_outliers_batch_n(self, n_problems, d_nkeys, kp_stride, d_kp_match,
+                                       d_outlier, d_points, mp_stride, mark_seen, d_n_matches,
+                                       n_matches_stride, d_out, stream: int = 0):
+        """track_discard_outliers_batch with the match counts read from
+        d_n_matches[p * n_matches_stride] (int32 units): the first field of a
+        FRAME_MATCH_INFO_DTYPE or BOW_MATCH_INFO_DTYPE array, stride 5
+        (orb_track_discard_outliers_batch_n)."""
+        _check(lib().orb_track_discard_outliers_batch_n(
+            self._h, n_problems, d_nkeys, kp_stride, d_kp_match, d_outlier, d_points, mp_stride,
+            int(bool(mark_seen)), d_n_matches, n_matches_stride, d_out, stream or None),
+            "track_discard_outliers_batch_n")
+
+    # ---------------- TrackReferenceKeyFrame / Relocalization's matcher, device batch
+    def search_by_bow_batch(self, n_problems, d_kf_index, d_f_index, d_kf_keys, d_kf_desc,
+                            d_kf_nkeys, d_kf_point_index, d_kf_fv_nodes, d_kf_fv_offs,
+                            d_kf_fv_feats, d_kf_n_fv_nodes, d_f_keys, d_f_desc, d_f_nkeys,
+                            d_f_fv_nodes, d_f_fv_offs, d_f_fv_feats, d_f_n_fv_nodes, kp_stride,
+                            d_points, mp_stride, min_matches, d_kp_match, d_info,
+                            stream: int = 0):
+        """Device-batched SearchByBoW(pKF, F, vpMapPointMatches) (orb_match_bow_batch)
+        with this matcher's mfNNratio and mbCheckOrientation.  d_* are device
+        addresses in the slot layout of ORBextractor's batch and
+        ORBVocabulary.transform_batch; d_kf_index, d_f_index (slot per problem)
+        and d_points may be 0 (identity / no bad point); d_info holds n_problems
+        BOW_MATCH_INFO_DTYPE records.  Asynchronous on `stream`."""
+        _check(lib().orb_match_bow_batch(
+            self._h, n_problems, d_kf_index or None, d_f_index or None, d_kf_keys, d_kf_desc,
+            d_kf_nkeys, d_kf_point_index, d_kf_fv_nodes, d_kf_fv_offs, d_kf_fv_feats,
+            d_kf_n_fv_nodes, d_f_keys, d_f_desc, d_f_nkeys, d_f_fv_nodes, d_f_fv_offs,
+            d_f_fv_feats, d_f_n_fv_nodes, kp_stride, d_points or None, mp_stride,
+            self.mfNNratio, int(self.mbCheckOrientation), min_matches, d_kp_match, d_info,
+            stream or None), "search_by_bow_batch")
+
+    @staticmethod
+    def search_by_bow_batch_max_stride() -> int:
+        """Largest kp_stride search_by_bow_batch accepts."""
+        return lib().orb_match_bow_batch_max_stride()
 
     # ------------------------------------------ MapPoint::ComputeDistinctiveDescriptors
     def ComputeDistinctiveDescriptors(self, obs_offs, obs_desc, descriptors=None):

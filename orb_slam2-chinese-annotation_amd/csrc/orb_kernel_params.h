@@ -208,3 +208,29 @@ struct FrameBatchParams {
   int nLevels, mono, checkOri, retryBelow;
   float scale[ORB_MAX_LEVELS];
 };
+
+// One side's slot arrays of SearchByBoW(KF, F) as a batch: what
+// orb_extractor_extract_batch and orb_vocabulary_transform_batch write, slot k
+// at k * stride (desc x 32, fvOffs at k * (stride + 1))
+struct BowSlots {
+  const orb_keypoint_t* keys;
+  const uint8_t* desc;
+  const int32_t* nkeys;
+  const uint32_t* fvNodes;
+  const int32_t* fvOffs;
+  const uint32_t* fvFeats;
+  const int32_t* nFvNodes;
+};
+
+// SearchByBoW(pKF, F, vpMapPointMatches) over nProblems (by value)
+struct BowBatchParams {
+  int nProblems, stride;
+  long long mpStride;          // map points between two problems' arrays (0: one shared array)
+  const int32_t* kfIndex;      // keyframe / frame slot of problem p (null: p)
+  const int32_t* fIndex;
+  BowSlots kf, f;
+  const int32_t* kfPointIndex; // mvpMapPoints per keyframe keypoint (< 0: NULL)
+  const orb_map_point_t* points;  // null: no point is bad
+  float nnratio;
+  int checkOri, minMatches;
+};

@@ -223,6 +223,10 @@ hipError_t orb_k_frame_batch(const FrameBatchParams* params, const orb_keypoint_
                              orb_frame_match_info_t* info, hipStream_t s);
 hipError_t orb_k_track_discard(int nProblems, int stride, long long mpStride, int markSeen,
                                const int32_t* nkeys, int32_t* kpMatch, uint8_t* outlier,
-                               orb_map_point_t* points, const orb_frame_match_info_t* info,
+                               orb_map_point_t* points, const int32_t* nMatches, int nMatchesStride,
                                orb_track_discard_info_t* out, hipStream_t s);
+// largest kp_stride whose per-problem state fits one CU's LDS
+int orb_k_bow_batch_max_stride(void);
+hipError_t orb_k_bow_batch(const BowBatchParams* params, int32_t* kpMatch,
+                           orb_bow_match_info_t* info, hipStream_t s);
 }

@@ -4102,17 +4102,80 @@ orb_status_t orb_track_discard_outliers_batch(orb_matcher_t* m, int n_problems,
                                               int mark_seen,
                                               const orb_frame_match_info_t* d_info,
                                               orb_track_discard_info_t* d_out, void* stream) {
-  if (!m || n_problems < 0 || kp_stride <= 0 || mp_stride < 0 || (mark_seen && mp_stride == 0))
+  return orb_track_discard_outliers_batch_n(
+      m, n_problems, d_nkeys, kp_stride, d_kp_match, d_outlier, d_points, mp_stride, mark_seen,
+      d_info ? &d_info->n_matches : nullptr,
+      (int)(sizeof(orb_frame_match_info_t) / sizeof(int32_t)), d_out, stream);
+}
+
+orb_status_t orb_track_discard_outliers_batch_n(orb_matcher_t* m, int n_problems,
+                                                const int32_t* d_nkeys, int kp_stride,
+                                                int32_t* d_kp_match, uint8_t* d_outlier,
+                                                orb_map_point_t* d_points, int mp_stride,
+                                                int mark_seen, const int32_t* d_n_matches,
+                                                int n_matches_stride,
+                                                orb_track_discard_info_t* d_out, void* stream) {
+  if (!m || n_problems < 0 || kp_stride <= 0 || mp_stride < 0 || (mark_seen && mp_stride == 0) ||
+      n_matches_stride < 1)
     return ORB_EINVAL;
   if (n_problems == 0) return ORB_OK;
-  if (!d_nkeys || !d_kp_match || !d_outlier || !d_points || !d_info || !d_out ||
+  if (!d_nkeys || !d_kp_match || !d_outlier || !d_points || !d_n_matches || !d_out ||
       n_problems > 65535)
     return ORB_EINVAL;
   std::lock_guard<std::mutex> g(m->mu);
   hipSetDevice(m->device);
   hipStream_t s = stream ? (hipStream_t)stream : m->stream;
   HIP_TRY(orb_k_track_discard(n_problems, kp_stride, mp_stride, mark_seen ? 1 : 0, d_nkeys,
-                              d_kp_match, d_outlier, d_points, d_info, d_out, s));
+                              d_kp_match, d_outlier, d_points, d_n_matches, n_matches_stride,
+                              d_out, s));
+  return ORB_OK;
+}
+
+// ------------------------------------ SearchByBoW(KF, F) as a device batch
+// (src/ORBmatcher.cc:164-306, src/Tracking.cc:904-954, :1592-1616;
+// track_kernels.hip).  No CallOrder: the kernel uses none of the handle's
+// scratch, its state is in LDS and the caller's arrays.
+int orb_match_bow_batch_max_stride(void) { return orb_k_bow_batch_max_stride(); }
+
+orb_status_t orb_match_bow_batch(
+    orb_matcher_t* m, int n_problems, const int32_t* d_kf_index, const int32_t* d_f_index,
+    const orb_keypoint_t* d_kf_keys, const uint8_t* d_kf_desc, const int32_t* d_kf_nkeys,
+    const int32_t* d_kf_point_index, const uint32_t* d_kf_fv_nodes, const int32_t* d_kf_fv_offs,
+    const uint32_t* d_kf_fv_feats, const int32_t* d_kf_n_fv_nodes,
+    const orb_keypoint_t* d_f_keys, const uint8_t* d_f_desc, const int32_t* d_f_nkeys,
+    const uint32_t* d_f_fv_nodes, const int32_t* d_f_fv_offs, const uint32_t* d_f_fv_feats,
+    const int32_t* d_f_n_fv_nodes, int kp_stride, const orb_map_point_t* d_points,
+    long long mp_stride, float nnratio, int check_orientation, int min_matches,
+    int32_t* d_kp_match, orb_bow_match_info_t* d_info, void* stream) {
+  if (!m || n_problems < 0 || kp_stride <= 0 || mp_stride < 0 || !std::isfinite(nnratio))
+    return ORB_EINVAL;
+  if (kp_stride > orb_k_bow_batch_max_stride()) return ORB_ECAPACITY;  // nothing is launched
+  if (n_problems == 0) return ORB_OK;
+  if (!d_kf_keys || !d_kf_desc || !d_kf_nkeys || !d_kf_point_index || !d_kf_fv_nodes ||
+      !d_kf_fv_offs || !d_kf_fv_feats || !d_kf_n_fv_nodes || !d_f_keys || !d_f_desc ||
+      !d_f_nkeys || !d_f_fv_nodes || !d_f_fv_offs || !d_f_fv_feats || !d_f_n_fv_nodes ||
+      !d_kp_match || !d_info)
+    return ORB_EINVAL;
+  std::lock_guard<std::mutex> g(m->mu);
+  hipSetDevice(m->device);
+  hipStream_t s = stream ? (hipStream_t)stream : m->stream;
+  BowBatchParams P;
+  memset(&P, 0, sizeof(P));
+  P.nProblems = n_problems;
+  P.stride = kp_stride;
+  P.mpStride = mp_stride;
+  P.kfIndex = d_kf_index;
+  P.fIndex = d_f_index;
+  P.kf = BowSlots{d_kf_keys, d_kf_desc, d_kf_nkeys, d_kf_fv_nodes, d_kf_fv_offs, d_kf_fv_feats,
+                  d_kf_n_fv_nodes};
+  P.f = BowSlots{d_f_keys, d_f_desc, d_f_nkeys, d_f_fv_nodes, d_f_fv_offs, d_f_fv_feats,
+                 d_f_n_fv_nodes};
+  P.kfPointIndex = d_kf_point_index;
+  P.points = d_points;
+  P.nnratio = nnratio;
+  P.checkOri = check_orientation ? 1 : 0;
+  P.minMatches = min_matches;
+  HIP_TRY(orb_k_bow_batch(&P, d_kp_match, d_info, s));
   return ORB_OK;
 }
 

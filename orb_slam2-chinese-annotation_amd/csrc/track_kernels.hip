@@ -2,7 +2,10 @@
 // matcher stage as a device-resident batch: SearchByProjection(CurrentFrame,
 // LastFrame, th, bMono) (src/ORBmatcher.cc:1460-1619) with the 2 * th retry
 // (src/Tracking.cc:1044-1052), and the "Discard outliers" loop (:1060-1083)
-// with SearchLocalPoints' already-matched marking (:1333-1354).
+// with SearchLocalPoints' already-matched marking (:1333-1354); and of
+// TrackReferenceKeyFrame's and Relocalization's matcher stage, SearchByBoW(pKF,
+// F, vpMapPointMatches) (src/ORBmatcher.cc:164-306), as the same kind of batch
+// (k_bow_batch, at the end of the file).
 //
 // k_frame_batch: one workgroup of four waves per problem, the problem's grid
 // built before it by k_grid_build.  Per pass: every wave projects last-frame
@@ -379,10 +382,13 @@ extern "C" hipError_t orb_k_frame_batch(
 // src/Tracking.cc:1060-1083 over one problem's keypoints, then (markSeen) the
 // first loop of SearchLocalPoints (:1333-1354) on what is kept.  Several
 // keypoints may hold one point: their `seen` stores write the same byte value.
+// The matcher's count is nMatches[p * nMatchesStride] (the first field of
+// either matcher's info records).
 __global__ __launch_bounds__(256) void k_track_discard(
     int stride, long long mpStride, int markSeen, const int32_t* __restrict__ nkeys,
     int32_t* __restrict__ kpMatch, uint8_t* __restrict__ outlier, orb_map_point_t* points,
-    const orb_frame_match_info_t* __restrict__ info, orb_track_discard_info_t* __restrict__ out) {
+    const int32_t* __restrict__ nMatches, int nMatchesStride,
+    orb_track_discard_info_t* __restrict__ out) {
   __shared__ int cnt[2];
   const int p = blockIdx.x, tid = threadIdx.x;
   const int n = min(max(nkeys[p], 0), stride);
@@ -418,16 +424,319 @@ __global__ __launch_bounds__(256) void k_track_discard(
   if (tid == 0) {
     out[p].n_discarded = cnt[0];
     out[p].n_matches_map = cnt[1];
-    out[p].n_matches = info[p].n_matches - cnt[0];
+    out[p].n_matches = nMatches[(size_t)p * nMatchesStride] - cnt[0];
   }
 }
 
 extern "C" hipError_t orb_k_track_discard(int nProblems, int stride, long long mpStride,
                                           int markSeen, const int32_t* nkeys, int32_t* kpMatch,
                                           uint8_t* outlier, orb_map_point_t* points,
-                                          const orb_frame_match_info_t* info,
+                                          const int32_t* nMatches, int nMatchesStride,
                                           orb_track_discard_info_t* out, hipStream_t s) {
   hipLaunchKernelGGL(k_track_discard, dim3(nProblems), dim3(256), 0, s, stride, mpStride,
-                     markSeen, nkeys, kpMatch, outlier, points, info, out);
+                     markSeen, nkeys, kpMatch, outlier, points, nMatches, nMatchesStride, out);
+  return hipGetLastError();
+}
+
+// ============================== SearchByBoW(KeyFrame*, Frame&, ...) as a batch
+// src/ORBmatcher.cc:164-306 for Tracking::TrackReferenceKeyFrame
+// (src/Tracking.cc:904-954) and Relocalization's candidates (:1592-1616): one
+// workgroup of eight waves per problem, one launch for validation, matching, the rotation
+// filter, the min_matches gate and the outputs.  A frame feature belongs to
+// exactly one node, so nodes are independent (k_bow_match): the waves draw
+// keyframe nodes from an LDS counter.  Per problem the LDS holds one word per
+// frame keypoint (the keyframe keypoint that claimed it | its rotation bin <<
+// 24, -1 unclaimed: claim flag and accepted list in one, with no word shared
+// between nodes and so no atomics on it), and per keyframe node the position
+// of the frame's node with the same id, found by all threads at once before
+// the matching, so that no binary search sits between two nodes of a wave.
+// A node of at most 64 frame features keeps a frame descriptor, its angle and
+// the claimed flag per lane in registers for the whole node; the keyframe
+// features are loaded a feature per lane too (64 at a time) and broadcast from
+// there by readlane, so the serial loop over them loads nothing: a step is one
+// Hamming distance and two wave-wide minima, by (distance, position) and of
+// the distance over the lanes other than the winner.  Larger frame nodes scan
+// in 64-lane trips with the claims read from LDS.
+#ifndef BB_T
+#define BB_T 512  // eight waves (128, 256 and 1024 measured beside it)
+#endif
+#define BB_STATIC_LDS ((size_t)512)  // budget for hist[32], ctl[8] and the block vote
+#define BB_TH_LOW 50
+
+// Minimum over the 64 lanes (all active), wave-uniform: the DPP steps of
+// wave_incl_scan with min; a lane whose source is outside its row keeps v.
+__device__ __forceinline__ int wave_min(int v) {
+  v = min(v, __builtin_amdgcn_update_dpp(v, v, 0x111, 0xf, 0xf, false));  // row_shr:1
+  v = min(v, __builtin_amdgcn_update_dpp(v, v, 0x112, 0xf, 0xf, false));  // row_shr:2
+  v = min(v, __builtin_amdgcn_update_dpp(v, v, 0x114, 0xf, 0xf, false));  // row_shr:4
+  v = min(v, __builtin_amdgcn_update_dpp(v, v, 0x118, 0xf, 0xf, false));  // row_shr:8
+  v = min(v, __builtin_amdgcn_update_dpp(v, v, 0x142, 0xa, 0xf, false));  // row_bcast:15
+  v = min(v, __builtin_amdgcn_update_dpp(v, v, 0x143, 0xc, 0xf, false));  // row_bcast:31
+  return __builtin_amdgcn_readlane(v, 63);
+}
+
+__device__ __forceinline__ unsigned long long lane_bcast64(unsigned long long v, int srcLane) {
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, srcLane);
+  const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), srcLane);
+  return ((unsigned long long)hi << 32) | lo;
+}
+
+// One FeatureVector's offsets: non-negative, non-decreasing, none above count.
+__device__ __forceinline__ int bb_bad_offsets(const int32_t* offs, int nNodes, int count, int tid) {
+  int bad = 0;
+  if (nNodes > 0)
+    for (int i = tid; i <= nNodes; i += BB_T) {
+      const int o = offs[i];
+      bad |= (o < 0 || o > count);
+      if (i < nNodes) bad |= (offs[i + 1] < o);
+    }
+  return bad;
+}
+// Its feature indices, once the offsets are known to be good.
+__device__ __forceinline__ int bb_bad_feats(const int32_t* offs, const uint32_t* feats, int nNodes,
+                                            int count, int tid) {
+  int bad = 0;
+  if (nNodes > 0)
+    for (int q = offs[0] + tid; q < offs[nNodes]; q += BB_T) bad |= (feats[q] >= (uint32_t)count);
+  return bad;
+}
+
+__global__ __launch_bounds__(BB_T) void k_bow_batch(BowBatchParams P, int32_t* __restrict__ kpMatch,
+                                                    orb_bow_match_info_t* __restrict__ info) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t dyn[];
+  __shared__ int hist[32];
+  __shared__ int ctl[8];  // next node, tried, common nodes, accepted, removed
+  static_assert(sizeof(hist) + sizeof(ctl) + 256 <= BB_STATIC_LDS, "capacity rule counts these");
+  const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+  const int S = (P.stride + 3) & ~3;
+  int* fmatch = (int*)dyn;    // per frame keypoint: keyframe keypoint | bin << 24, -1 unclaimed
+  int* partner = fmatch + S;  // per keyframe node: position of the frame's node, -1 none
+
+  const int ks = P.kfIndex ? P.kfIndex[p] : p;
+  const int fs = P.fIndex ? P.fIndex[p] : p;
+  const size_t kb = (size_t)ks * P.stride, fb = (size_t)fs * P.stride;
+  const int nK = min(max(P.kf.nkeys[ks], 0), P.stride);
+  const int nF = min(max(P.f.nkeys[fs], 0), P.stride);
+  const int nnK = min(max(P.kf.nFvNodes[ks], 0), nK);
+  const int nnF = min(max(P.f.nFvNodes[fs], 0), nF);
+  const orb_keypoint_t* kKeys = P.kf.keys + kb;
+  const uint8_t* kDesc = P.kf.desc + kb * 32;
+  const uint32_t* kNodes = P.kf.fvNodes + kb;
+  const int32_t* kOffs = P.kf.fvOffs + (size_t)ks * ((size_t)P.stride + 1);
+  const uint32_t* kFeats = P.kf.fvFeats + kb;
+  const int32_t* PI = P.kfPointIndex + kb;
+  const orb_keypoint_t* fKeys = P.f.keys + fb;
+  const uint8_t* fDesc = P.f.desc + fb * 32;
+  const uint32_t* fNodes = P.f.fvNodes + fb;
+  const int32_t* fOffs = P.f.fvOffs + (size_t)fs * ((size_t)P.stride + 1);
+  const uint32_t* fFeats = P.f.fvFeats + fb;
+  const orb_map_point_t* PTS = P.points ? P.points + (size_t)p * (size_t)P.mpStride : nullptr;
+  int32_t* KM = kpMatch + (size_t)p * P.stride;
+
+  // ---- malformed slots: the offsets first, then (inside good offsets) the
+  // feature indices; a bad value is reported and never used as an index
+  int bad = bb_bad_offsets(kOffs, nnK, nK, tid) | bb_bad_offsets(fOffs, nnF, nF, tid);
+  bad = __syncthreads_or(bad);
+  if (!bad) {
+    bad = bb_bad_feats(kOffs, kFeats, nnK, nK, tid) | bb_bad_feats(fOffs, fFeats, nnF, nF, tid);
+    bad = __syncthreads_or(bad);
+  }
+  if (bad) {
+    for (int i = tid; i < nF; i += BB_T) KM[i] = -1;
+    if (tid == 0) {
+      info[p].n_matches = -1;
+      info[p].n_accepted = 0;
+      info[p].n_common_nodes = 0;
+      info[p].n_tried = 0;
+      info[p].enough = 0;
+    }
+    return;
+  }
+
+  // ---- the merge-join on node id, a keyframe node per thread
+  for (int i = tid; i < nF; i += BB_T) fmatch[i] = -1;
+  if (tid < 32) hist[tid] = 0;
+  if (tid < 8) ctl[tid] = 0;
+  __syncthreads();
+  {
+    int common = 0;
+    for (int a = tid; a < nnK; a += BB_T) {
+      const uint32_t id = kNodes[a];
+      int lo = 0, hi = nnF;
+      while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (fNodes[mid] < id) lo = mid + 1; else hi = mid;
+      }
+      const bool found = lo < nnF && fNodes[lo] == id;
+      partner[a] = found ? lo : -1;
+      common += found;
+    }
+    common = wave_sum(common);
+    if (lane == 0 && common) atomicAdd(&ctl[2], common);
+  }
+  __syncthreads();
+
+  // ---- matching: a wave per keyframe node
+  int tried = 0;
+  for (;;) {
+    int a = 0;
+    if (lane == 0) a = atomicAdd(&ctl[0], 1);
+    a = __builtin_amdgcn_readfirstlane(a);
+    if (a >= nnK) break;
+    const int fp = __builtin_amdgcn_readfirstlane(partner[a]);
+    if (fp < 0) continue;
+    const int kb0 = __builtin_amdgcn_readfirstlane(kOffs[a]);
+    const int ke0 = __builtin_amdgcn_readfirstlane(kOffs[a + 1]);
+    const int fb0 = __builtin_amdgcn_readfirstlane(fOffs[fp]);
+    const int fc = __builtin_amdgcn_readfirstlane(fOffs[fp + 1]) - fb0;
+    if (fc <= 0) continue;
+    const bool fast = fc <= 64;
+    // the frame's node in registers (fast path): a feature per lane
+    int myF = 0;
+    ulonglong4 dF = make_ulonglong4(0, 0, 0, 0);
+    float aF = 0.0f;
+    bool avail = false;
+    if (fast && lane < fc) {
+      myF = (int)fFeats[fb0 + lane];
+      dF = load_desc(fDesc + (size_t)myF * 32);
+      aF = fKeys[myF].angle;
+      avail = true;
+    }
+    for (int c = kb0; c < ke0; c += 64) {
+      // 64 keyframe features of the node, a feature per lane
+      int kf = 0;
+      ulonglong4 dK = make_ulonglong4(0, 0, 0, 0);
+      float aK = 0.0f;
+      bool ok = false;
+      if (c + lane < ke0) {
+        kf = (int)kFeats[c + lane];
+        const int pi = PI[kf];
+        ok = pi >= 0 && !(PTS && PTS[pi].bad);  // :204-209
+        if (ok) {
+          dK = load_desc(kDesc + (size_t)kf * 32);
+          aK = kKeys[kf].angle;
+        }
+      }
+      unsigned long long todo = __ballot(ok);
+      tried += __popcll(todo);
+      while (todo) {  // in list order
+        const int j = (int)__builtin_ctzll(todo);
+        todo &= todo - 1;
+        ulonglong4 q;
+        q.x = lane_bcast64(dK.x, j);
+        q.y = lane_bcast64(dK.y, j);
+        q.z = lane_bcast64(dK.z, j);
+        q.w = lane_bcast64(dK.w, j);
+        int best1, best2, win, pos = 0;
+        if (fast) {
+          const int dist = avail ? hamming256(q, dF) : 256;
+          const int key = wave_min((dist << 8) | lane);
+          best1 = key >> 8;
+          win = key & 63;
+          best2 = wave_min(lane == win ? 256 : dist);
+        } else {
+          // per lane the first two of its trips in (distance, position) order
+          int d1 = 256, q1 = 0xFFFF, d2 = 256;
+          for (int t = lane; t < fc; t += 64) {
+            const int rf = (int)fFeats[fb0 + t];
+            if (fmatch[rf] >= 0) continue;  // :222-223
+            const int dist = hamming256(q, load_desc(fDesc + (size_t)rf * 32));
+            if (dist < d1) { d2 = d1; d1 = dist; q1 = t; }
+            else if (dist < d2) { d2 = dist; }
+          }
+          const int key = wave_min((d1 << 16) | q1);
+          best1 = key >> 16;
+          pos = key & 0xFFFF;
+          win = pos & 63;  // position t is scanned by lane t & 63
+          best2 = wave_min(lane == win ? d2 : d1);
+        }
+        if (best1 <= BB_TH_LOW && (float)best1 < P.nnratio * (float)best2) {  // :239-241
+          const int kfj = __builtin_amdgcn_readlane(kf, j);
+          const float akj = __builtin_bit_cast(
+              float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, aK), j));
+          if (lane == win) {
+            int rf = myF;
+            float af = aF;
+            if (!fast) {
+              rf = (int)fFeats[fb0 + pos];
+              af = fKeys[rf].angle;
+            }
+            const int bin = P.checkOri ? rot_bin(akj - af) : 0;  // :247-258
+            fmatch[rf] = kfj | (bin << 24);
+            if (P.checkOri) atomicAdd(&hist[bin], 1);
+            avail = false;
+          }
+        }
+        if (!fast) {  // the next feature's trips read this claim
+          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+          __builtin_amdgcn_wave_barrier();
+          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        }
+      }
+    }
+  }
+  if (lane == 0 && tried) atomicAdd(&ctl[1], tried);
+  __syncthreads();
+
+  // ---- rotation filter (:265-281), the gate and the outputs
+  int ind1 = -1, ind2 = -1, ind3 = -1;
+  if (P.checkOri) three_maxima(hist, ind1, ind2, ind3);
+  int accepted = 0, removed = 0;
+  for (int i = tid; i < nF; i += BB_T) {
+    const int e = fmatch[i];
+    if (e < 0) continue;
+    ++accepted;
+    const int b = e >> 24;
+    if (P.checkOri && b != ind1 && b != ind2 && b != ind3) {
+      ++removed;
+      fmatch[i] = -1;
+    }
+  }
+  accepted = wave_sum(accepted);
+  removed = wave_sum(removed);
+  if (lane == 0) {
+    atomicAdd(&ctl[3], accepted);
+    atomicAdd(&ctl[4], removed);
+  }
+  __syncthreads();
+  const int nm = ctl[3] - ctl[4];
+  const bool enough = nm >= P.minMatches;
+  for (int i = tid; i < nF; i += BB_T) {
+    const int e = fmatch[i];
+    KM[i] = (enough && e >= 0) ? PI[e & 0xFFFFFF] : -1;
+  }
+  if (tid == 0) {
+    info[p].n_matches = nm;
+    info[p].n_accepted = ctl[3];
+    info[p].n_common_nodes = ctl[2];
+    info[p].n_tried = ctl[1];
+    info[p].enough = enough;
+  }
+}
+
+// dynamic LDS of one k_bow_batch workgroup at `stride` keypoint slots
+static size_t bow_batch_lds(int stride) {
+  return 8 * (((size_t)stride + 3) & ~(size_t)3);
+}
+
+extern "C" int orb_k_bow_batch_max_stride(void) {
+  // 8 B per slot plus the static part within 160 KiB; the match word holds 24
+  // index bits
+  int s = (int)((ORB_LDS_PER_CU - BB_STATIC_LDS) / 8) & ~3;
+  while (bow_batch_lds(s) + BB_STATIC_LDS > ORB_LDS_PER_CU) s -= 4;
+  return std::min(s, (1 << 24) - 4);
+}
+
+extern "C" hipError_t orb_k_bow_batch(const BowBatchParams* params, int32_t* kpMatch,
+                                      orb_bow_match_info_t* info, hipStream_t s) {
+  const BowBatchParams P = *params;
+  if (P.stride <= 0 || P.stride > orb_k_bow_batch_max_stride()) return hipErrorInvalidValue;
+  const size_t lds = bow_batch_lds(P.stride);
+  if (lds > 65536 - BB_STATIC_LDS) {
+    hipError_t e = hipFuncSetAttribute((const void*)k_bow_batch,
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(k_bow_batch, dim3(P.nProblems), dim3(BB_T), lds, s, P, kpMatch, info);
   return hipGetLastError();
 }

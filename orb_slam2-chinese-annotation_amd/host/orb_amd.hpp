@@ -830,6 +830,49 @@ class ORBmatcher {
                                            d_info, d_out, stream),
           "track_discard_outliers_batch");
   }
+  // The same with the match counts read from d_n_matches[p * n_matches_stride]
+  // (int32 units): the first field of either matcher's info records, stride 5
+  // (orb_track_discard_outliers_batch_n; src/Tracking.cc:928-951).
+  void track_discard_outliers_batch_n(int n_problems, const int32_t* d_nkeys, int kp_stride,
+                                      int32_t* d_kp_match, uint8_t* d_outlier,
+                                      orb_map_point_t* d_points, int mp_stride, bool mark_seen,
+                                      const int32_t* d_n_matches, int n_matches_stride,
+                                      orb_track_discard_info_t* d_out, void* stream = nullptr) {
+    check(orb_track_discard_outliers_batch_n(h_, n_problems, d_nkeys, kp_stride, d_kp_match,
+                                             d_outlier, d_points, mp_stride, mark_seen ? 1 : 0,
+                                             d_n_matches, n_matches_stride, d_out, stream),
+          "track_discard_outliers_batch_n");
+  }
+
+  // One side's slots of search_by_bow_batch: what ORBextractor's batch and
+  // ORBVocabulary::transform_batch write with the same stride.
+  struct BowSlots {
+    const KeyPoint* d_keys;
+    const uint8_t* d_desc;
+    const int32_t* d_nkeys;
+    const uint32_t* d_fv_nodes;
+    const int32_t* d_fv_offs;
+    const uint32_t* d_fv_feats;
+    const int32_t* d_n_fv_nodes;
+  };
+  // Device-batched SearchByBoW(pKF, F, vpMapPointMatches) (orb_match_bow_batch;
+  // src/ORBmatcher.cc:164-306 as src/Tracking.cc:904-954 and :1592-1616 call
+  // it) with mfNNratio and mbCheckOrientation.  d_kf_index, d_f_index and
+  // d_points may be null (identity slots / no bad point).
+  void search_by_bow_batch(int n_problems, const int32_t* d_kf_index, const int32_t* d_f_index,
+                           const BowSlots& kf, const int32_t* d_kf_point_index, const BowSlots& f,
+                           int kp_stride, const orb_map_point_t* d_points, long long mp_stride,
+                           int min_matches, int32_t* d_kp_match, orb_bow_match_info_t* d_info,
+                           void* stream = nullptr) {
+    check(orb_match_bow_batch(h_, n_problems, d_kf_index, d_f_index, kf.d_keys, kf.d_desc,
+                              kf.d_nkeys, d_kf_point_index, kf.d_fv_nodes, kf.d_fv_offs,
+                              kf.d_fv_feats, kf.d_n_fv_nodes, f.d_keys, f.d_desc, f.d_nkeys,
+                              f.d_fv_nodes, f.d_fv_offs, f.d_fv_feats, f.d_n_fv_nodes, kp_stride,
+                              d_points, mp_stride, mfNNratio, mbCheckOrientation ? 1 : 0,
+                              min_matches, d_kp_match, d_info, stream),
+          "search_by_bow_batch");
+  }
+  static int search_by_bow_batch_max_stride() { return orb_match_bow_batch_max_stride(); }
 
   float mfNNratio;
   bool mbCheckOrientation;

@@ -40,6 +40,14 @@ results table:
       of 20), also 1, 64 and 256 problems; against orb_match_projection_frame
       over the same problems one call at a time (host clock; run once more
       with ORB_AMD_LIB naming the parent build for the baseline) + exact check
+  B1  TrackReferenceKeyFrame / Relocalization's SearchByBoW(KF, F): B1a 1,024
+      problems over 32 distinct bow_pair scenes (1241x376, 1,000 features,
+      nnratio 0.7, orientation on, min_matches 15) in one launch, B1b one frame
+      slot against 64 keyframe slots (nnratio 0.75); device events around the
+      launch (median of 20, minimum, maximum), also 1, 64 and 256 problems;
+      against orb_match_bow over the same problems one call at a time (host
+      clock; run once more with ORB_AMD_LIB naming the parent build for the
+      baseline row alone) + exact check of four problems
   R1  RGB-D: 640x480 (TUM1 intrinsics and distortion, DepthMapFactor 5000),
       1000 features, 256 frames per launch, device-resident: extract ->
       undistort -> ComputeStereoFromRGBD -> closest points + UnprojectStereo ->
@@ -47,7 +55,7 @@ results table:
       same pipeline without the RGB-D stages (monocular matcher), each new
       kernel alone by HIP events with its algorithmic bytes + exact check
 
-Usage: python tools/bench_configs.py [--configs C1,C2,C3,C5,F1,F3,P1,R1,T1,M1] [--steps K]
+Usage: python tools/bench_configs.py [--configs C1,C2,C3,C5,F1,F3,P1,R1,T1,M1,B1] [--steps K]
 The oracle (CPU restatement) is used only for the CPU rows and parity checks.
 """
 import argparse
@@ -781,6 +789,129 @@ def m1(args, orb, oracle, torch):
     return out
 
 
+def b1(args, orb, oracle, torch):
+    import bow_batch_ref as BR
+    import scenarios as S
+    B, DISTINCT, K, MIN = 1024, 32, 64, 15
+    probs = [BR.from_bow(S.bow_pair(oracle, 40 + i, rng_seed=i)) for i in range(DISTINCT)]
+    stride = max(len(s["desc"]) for p in probs for s in (p["kf"], p["f"]))
+    ma, mb = orb.ORBmatcher(0.7, True), orb.ORBmatcher(0.75, True)
+
+    def bad_flags(p):
+        mp = p["kf"]["pidx"]
+        return np.where(mp >= 0, p["points"]["bad"][np.maximum(mp, 0)], 0).astype(np.uint8)
+    bad = [bad_flags(p) for p in probs]
+
+    def one(m, k, f):   # keyframe of scene k against the frame of scene f, one blocking call
+        kf, fr = probs[k]["kf"], probs[f]["f"]
+        return m.SearchByBoW(kf["desc"], kf["angle"], kf["pidx"], bad[k], kf["fv"], fr["desc"],
+                             fr["angle"], fr["fv"])
+
+    def latency(m, pairs, reps):
+        for k, f in pairs:
+            one(m, k, f)
+        lat = []
+        for _ in range(reps):
+            for k, f in pairs:
+                t0 = time.perf_counter()
+                one(m, k, f)
+                lat.append((time.perf_counter() - t0) * 1e3)
+        return sorted(lat)
+    lat = latency(ma, [(i, i) for i in range(DISTINCT)], 4)
+    reloc_pairs = [(k % DISTINCT, 0) for k in range(K)]
+    t0 = time.perf_counter()
+    for k, f in reloc_pairs:
+        one(mb, k, f)
+    reloc_serial_ms = (time.perf_counter() - t0) * 1e3
+    nodes = [len(p["f"]["fv"][0]) for p in probs]
+    out = {"config": "B1", "library": str(orb.LIB_PATH),
+           "workload": f"SearchByBoW(KF, F), {B} problems x {stride} keypoint slots, "
+                       f"{int(np.mean(nodes))} frame nodes on average, largest node "
+                       f"{max(int(np.diff(p['f']['fv'][1]).max()) for p in probs)} features, "
+                       f"nnratio 0.7, min_matches {MIN} ({DISTINCT} distinct problems); "
+                       f"relocalisation: 1 frame x {K} keyframes, nnratio 0.75",
+           "one_call_ms_median": lat[len(lat) // 2], "one_call_ms_min": lat[0],
+           "one_call_ms_max": lat[-1], "one_call_samples": len(lat),
+           "reloc_serial_ms": reloc_serial_ms}
+    if not hasattr(orb.lib(), "orb_match_bow_batch"):
+        return out  # a build from before the batch entry: the baseline row only
+
+    def dev(a):
+        return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).cuda()
+    ka = BR.pack_slots([probs[p % DISTINCT]["kf"] for p in range(B)], stride)
+    fa = BR.pack_slots([probs[p % DISTINCT]["f"] for p in range(B)], stride)
+    pts, mps = BR.pack_points([p["points"] for p in probs])   # scene i's array at i * mps
+    dk, df = {k: dev(a) for k, a in ka.items()}, {k: dev(a) for k, a in fa.items()}
+    # the 1,024 problems read the 32 point arrays through a per-problem copy
+    d_pts = dev(np.concatenate([pts[(p % DISTINCT) * mps:(p % DISTINCT + 1) * mps] for p in range(B)]))
+    d_km = torch.zeros(B * stride, dtype=torch.int32, device="cuda")
+    d_info = torch.zeros(B * 5, dtype=torch.int32, device="cuda")
+    d_zero = torch.zeros(K, dtype=torch.int32, device="cuda")
+    d_kidx = dev(np.arange(K, dtype=np.int32))
+    stream = torch.cuda.Stream()
+
+    def run(m, nprob, kidx=0, fidx=0, mp_stride=mps):
+        m.search_by_bow_batch(
+            nprob, kidx, fidx, dk["keys"].data_ptr(), dk["desc"].data_ptr(), dk["nkeys"].data_ptr(),
+            dk["pidx"].data_ptr(), dk["fv_nodes"].data_ptr(), dk["fv_offs"].data_ptr(),
+            dk["fv_feats"].data_ptr(), dk["n_fv_nodes"].data_ptr(), df["keys"].data_ptr(),
+            df["desc"].data_ptr(), df["nkeys"].data_ptr(), df["fv_nodes"].data_ptr(),
+            df["fv_offs"].data_ptr(), df["fv_feats"].data_ptr(), df["n_fv_nodes"].data_ptr(),
+            stride, d_pts.data_ptr(), mp_stride, MIN, d_km.data_ptr(), d_info.data_ptr(),
+            stream=stream.cuda_stream)
+
+    def events(fn, reps):
+        t = []
+        for _ in range(reps):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            fn()
+            e1.record(stream)
+            torch.cuda.synchronize()
+            t.append(e0.elapsed_time(e1))
+        return sorted(t)
+
+    def fetch(n):
+        torch.cuda.synchronize()
+        return (d_km.cpu().numpy().reshape(B, stride)[:n].copy(),
+                d_info.cpu().numpy().view(orb.BOW_MATCH_INFO_DTYPE)[:n].copy())
+    for _ in range(3):
+        run(ma, B)
+    torch.cuda.synchronize()
+    ms = events(lambda: run(ma, B), 20)
+    by_size = {str(n): events(lambda n=n: run(ma, n), 20)[10] for n in (1, 64, 256)}
+    run(ma, B)
+    km, info = fetch(B)
+    exact = True
+    for p in (0, 1, DISTINCT + 1, B - 1):
+        n1, fm1 = one(ma, p % DISTINCT, p % DISTINCT)
+        want = fm1 if n1 >= MIN else np.full(len(fm1), -1, np.int32)
+        exact &= n1 == int(info[p]["n_matches"]) and bool(np.array_equal(want, km[p, :len(fm1)]))
+    # B1b: K keyframe slots against frame slot 0, each with its own point array
+    reloc = lambda: run(mb, K, d_kidx.data_ptr(), d_zero.data_ptr())
+    reloc()
+    rms = events(reloc, 20)
+    reloc()
+    rkm, rinfo = fetch(K)
+    for k in (0, 1, K - 1):
+        n1, fm1 = one(mb, k % DISTINCT, 0)
+        want = fm1 if n1 >= MIN else np.full(len(fm1), -1, np.int32)
+        exact &= n1 == int(rinfo[k]["n_matches"]) and bool(np.array_equal(want, rkm[k, :len(fm1)]))
+    batch_ms = ms[len(ms) // 2]
+    out.update({"batch_ms_median": batch_ms, "batch_ms_min": ms[0], "batch_ms_max": ms[-1],
+                "launch_ms_by_problems": by_size, "problems_per_s": B / (batch_ms * 1e-3),
+                "batch_us_per_problem": batch_ms * 1e3 / B,
+                "one_call_over_batch_per_problem": lat[len(lat) // 2] / (batch_ms / B),
+                "matches_mean": float(info["n_matches"].mean()),
+                "tried_mean": float(info["n_tried"].mean()),
+                "reloc_ms_median": rms[len(rms) // 2], "reloc_ms_min": rms[0],
+                "reloc_ms_max": rms[-1], "reloc_enough": int(rinfo["enough"].sum()),
+                "reloc_serial_over_batch": reloc_serial_ms / rms[len(rms) // 2],
+                "kp_stride": stride, "max_stride": orb.match_bow_batch_max_stride(),
+                "exact_vs_one_problem_entry": bool(exact)})
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--configs", default="C1,C2,C3,C5")
@@ -817,6 +948,8 @@ def main():
             r = t1(args, orb, oracle, torch)
         elif c == "M1":
             r = m1(args, orb, oracle, torch)
+        elif c == "B1":
+            r = b1(args, orb, oracle, torch)
         else:
             raise SystemExit(f"unknown config {c}")
         print(json.dumps(r), flush=True)
