@@ -38,13 +38,6 @@
 #define PYR_IMAGES_PER_WG 16  // images per k_pyr_resize workgroup
 #endif
 #define PYR_TH 32
-#ifndef PYR_TARGET_WGS
-// > 0: fewer images per workgroup below this many workgroups per level.  At
-// 2048, 16 C5 frames resize in 0.138 instead of 0.198 ms and C3 gains 2.5 %,
-// but C5's pipelined rate loses 5.5 % (the wider resize crowds the matcher's
-// 16-CU resolve) and the headline is unchanged (profiles/r05_resize_target.txt)
-#define PYR_TARGET_WGS 0
-#endif
 // Staged source window (rows x dwords): >= the source rows a 32-row output
 // tile touches, multiple of 4, and >= the dwords of source row a 128-column
 // tile touches + 2 read-ahead.  Narrow: scale factors <= 1.25 (every ORB-SLAM2
@@ -93,9 +86,6 @@ __global__ __launch_bounds__(256) void k_pyr_resize_generic(
 // group (+ one dword for the realignment of an unaligned source) instead of
 // one or two dword loads per dword, one b128 LDS store.  The window's dword
 // pitch is a multiple of 4 and >= 4 nG, so a group never crosses a row.
-#ifndef PYR_LOAD16
-#define PYR_LOAD16 1
-#endif
 template <int NQ>
 struct TilePrefetch16 {
   uint32_t w[NQ][5], sh[NQ];
@@ -177,20 +167,20 @@ __global__ __launch_bounds__(256) void k_pyr_resize(
   const int syA = min(max(yofs[y0], 0), sh - 1), syB = min(max(yofs[yl] + 1, 0), sh - 1);
   const int colBase = sxA & ~3;
   const int nW = ((sxB - colBase) >> 2) + 1, nR = syB - syA + 1;
-  // staging: ALIGNED sources need one dword load per LDS dword, others two
-  // (realigned with v_alignbyte); PYR_LOAD16: one b128 (+ one dword) per 4
+  // staging in 16-byte groups: one b128 load per 4 LDS dwords, plus one dword
+  // for the realignment (v_alignbyte) of a source that is not ALIGNED
   static_assert(SW % 4 == 0, "window pitch must hold whole 16-byte groups");
-  const int nStage = PYR_LOAD16 ? (nW + 3) >> 2 : nW;  // staged elements per row
+  const int nStage = (nW + 3) >> 2;  // staged groups per row
   const uint32_t magic = div_magic(nStage);
-  constexpr int NQ = PYR_LOAD16 ? (SROWS * (SW / 4) + 255) / 256 : (SROWS * SW + 255) / 256;
-  typename std::conditional<PYR_LOAD16, TilePrefetch16<NQ>, TilePrefetch<NQ>>::type pf;
+  constexpr int NQ = (SROWS * (SW / 4) + 255) / 256;
+  TilePrefetch16<NQ> pf;
   // staged element q of this thread: the same offset in every image, computed once
   uint32_t eoff[NQ];
 #pragma unroll
   for (int q = 0; q < NQ; ++q) {
     const uint32_t i = (uint32_t)min(q * 256 + tid, nR * nStage - 1);
     const uint32_t r = __umulhi(i << 1, magic), c = i - r * (uint32_t)nStage;
-    eoff[q] = (syA + r) * (uint32_t)srcStride + (uint32_t)colBase + (PYR_LOAD16 ? 16 : 4) * c;
+    eoff[q] = (syA + r) * (uint32_t)srcStride + (uint32_t)colBase + 16 * c;
   }
   auto issue = [&](int z) {
     pf.issue(img_rsrc(src + (long long)z * srcImgPitch, (uint32_t)((sh - 1) * srcStride + sw)),
@@ -255,11 +245,7 @@ __global__ __launch_bounds__(256) void k_pyr_resize(
   };
   for (; z < nImg; z += gridDim.z) {
     __syncthreads();  // the previous image's taps have read the window
-#if PYR_LOAD16
     pf.commit(&tile[0][0], SW, nR, nStage, magic, ALIGNED);
-#else
-    pf.commit(&tile[0][0], SW, nR, nStage, magic);
-#endif
     if (z + (int)gridDim.z < nImg) issue(z + gridDim.z);
     __syncthreads();
     if (xs >= dw) continue;
@@ -544,9 +530,6 @@ __device__ __forceinline__ unsigned long long bit_run(const uint32_t* bits, int 
   return n >= 64 ? v : (v & ((1ull << n) - 1ull));
 }
 
-#ifndef FC_PRETEST4
-#define FC_PRETEST4 1
-#endif
 // Compass pretest of a pixel pair (f16 halves): a pixel can be a FAST(t)
 // corner only if two circularly adjacent compass pixels (circle positions
 // 0,4,8,12) are both darker than v - t or both brighter than v + t.  Each
@@ -563,17 +546,11 @@ __device__ __forceinline__ uint32_t pretest_pair(uint32_t v, uint32_t q0, uint32
                                                 __builtin_elementwise_minimum(Q4, Q12));
   const h16x2 B = __builtin_elementwise_minimum(__builtin_elementwise_maximum(Q0, Q8),
                                                 __builtin_elementwise_maximum(Q4, Q12));
-#if FC_PRETEST4
   // dark <=> V - A >= T, bright <=> B - V >= T: one max and one subtraction
   // of T instead of V -+ T, two differences and an AND (exact: every operand
   // is a small integer in f16)
   const h16x2 r = __builtin_elementwise_maximum(V - A, B - V) - T;
   return __builtin_bit_cast(uint32_t, r);
-#else
-  const h16x2 x = (V - T) - A;  // >= +0: dark
-  const h16x2 y = B - (V + T);  // >= +0: bright
-  return __builtin_bit_cast(uint32_t, x) & __builtin_bit_cast(uint32_t, y);
-#endif
 }
 
 __global__ __launch_bounds__(256) void k_fast_band(
@@ -950,15 +927,6 @@ __global__ __launch_bounds__(256) void k_fast_band(
   }  // band loop
 }
 
-// v_cndmask with a wave-uniform 64-bit lane mask as the condition: lanes whose
-// bit is set take ifSet.  (A select on a per-lane bool derived from a ballot
-// makes hipcc rebuild the mask through VGPR 0/1 values and compares.)
-__device__ __forceinline__ int lane_select(unsigned long long mask, int ifSet, int ifClear) {
-  int r;
-  asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(r) : "v"(ifClear), "v"(ifSet), "s"(mask));
-  return r;
-}
-
 __device__ __forceinline__ void wave_lds_sync() {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
@@ -969,13 +937,13 @@ __device__ __forceinline__ void wave_lds_sync() {
 // FAST per cell, one wave per cell (src/ORBextractor.cc:816-865), no
 // workgroup barriers: a wave stages its cell's ROI (cell + the 3-px FAST
 // border) as bytes in its own LDS slice, pretests 8 pixels per lane (compass
-// test), queues the candidates with wave ballots, scores them (arc strengths),
-// lists the corners (m > t), runs the cell-local 3x3 NMS into a row bitmap and
-// compacts it row by row (lane = window row).  A cell without a keypoint at
-// iniThFAST reruns the same at minThFAST over its window, keeping the
-// strengths already computed (:846-850).  Output per cell: keys in row-major
-// window order (cv::FAST's order), packed x | y << 12 | score << 24 in level
-// coordinates, and their count.
+// test), queues the candidates in row-major order, scores them (arc
+// strengths), lists the corners (m > t) and runs the cell-local 3x3 NMS over
+// the list, each survivor's key written at its output position.  A cell
+// without a keypoint at iniThFAST reruns the same at minThFAST over its
+// window, keeping the strengths already computed (:846-850).  Output per
+// cell: keys in row-major window order (cv::FAST's order), packed
+// x | y << 12 | score << 24 in level coordinates, and their count.
 //
 // Arithmetic: a pixel byte I is read as the f16 whose bit pattern is I, i.e.
 // the subnormal I * 2^-24 (f16 subnormals are kept: the kernel runs with
@@ -1001,45 +969,28 @@ __device__ __forceinline__ void wave_lds_sync() {
 #ifndef FC_CCAP
 #define FC_CCAP 256     // corner list per wave; beyond it the NMS runs densely
 #endif
-#ifndef FC_PAD
-#define FC_PAD 0        // extra LDS row pitch (bytes, multiple of 8)
-#endif
-#ifndef FC_LOAD3
-#define FC_LOAD3 0      // three 16-byte row loads instead of four where the ROI fits (A/B knob)
-#endif
-#ifndef FC_ROWMAJOR
-#define FC_ROWMAJOR 1   // candidates queued in row-major order, keys written by NMS in order
-#endif
-#ifndef FC_PERM
-#define FC_PERM (!FC_ROWMAJOR)  // pretest lane -> pixel-group permutation (LDS banking)
-#endif
 // Attribution builds (phase stubs, per-phase clock stamps; results wrong,
 // never shipped) are patches against this file: tools/attribution/.
 
 // LDS row pitch (bytes) of a cell ROI C pixels wide: byte 5 is ROI column 0,
 // byte 8 interior column 0 (ROI column 3); groups of 8 interior pixels read
-// [8k, 8k + 24).  FC_TIGHT: the pitch only has to hold the row (bytes 0 ..
+// [8k, 8k + 24).  The pitch only has to hold the row (bytes 0 ..
 // C + 4, a multiple of 8 for the b64 reads): a row's last group may read up to
 // 12 bytes into the next row, but only for pixels past the interior, which the
 // pass mask drops (every ORB-SLAM2 grid: ROI widths 36-43 -> 48 instead of 56
-// bytes, and with the NMS bitmap gone from the row-major path, 7.0 -> 5.9 KB
+// bytes, and with the column-major queue's NMS bitmap gone, 7.0 -> 5.9 KB
 // of LDS per wave: 22 -> 27 waves per CU, the limit of this kernel's occupancy)
-#ifndef FC_TIGHT
-#define FC_TIGHT 1
-#endif
 __host__ __device__ inline int fc_pitch(int C) {
-  return (FC_TIGHT ? ((C + 12) & ~7) : ((C + 20) & ~7)) + FC_PAD;
+  return (C + 12) & ~7;
 }
 __host__ __device__ inline int fc_tile_elems(int maxRows, int maxCols) {
   return (maxRows * fc_pitch(maxCols) + 15) & ~15;  // 16-byte aligned strength map
 }
 __host__ __device__ inline int fc_wave_bytes(int tileElems) {
-  // byte tile + strengths + queue + corners (+ 64 rows x 64-bit NMS bitmap,
-  // column-major path only)
-  return ((2 * tileElems + 2 * FC_QCAP + 2 * FC_CCAP + ((FC_ROWMAJOR && FC_TIGHT) ? 0 : 512)) + 15) &
-         ~15;
+  // byte tile + strengths + queue + corners
+  return ((2 * tileElems + 2 * FC_QCAP + 2 * FC_CCAP) + 15) & ~15;
 }
-#define FC_CONST_PITCH (FC_TIGHT ? 48 : 56)  // the compile-time instance
+#define FC_CONST_PITCH 48  // the compile-time instance
 
 // f16 pair {byte i0, byte i1} of the 8 bytes {hi:lo} (i in 0..7, lo first)
 __device__ __forceinline__ uint32_t byte_pair(uint32_t hi, uint32_t lo, int i0, int i1) {
@@ -1054,9 +1005,6 @@ __device__ __forceinline__ uint32_t byte_pair(uint32_t hi, uint32_t lo, int i0, 
 // conversion; the pixel value enters once at the end:
 //   dark = max_k min_arc (v - c) = v + max_k (-max_arc c),
 //   bright = max_k min_arc (c - v) = max_k min_arc c - v.
-#ifndef FC_SCORE_RAW
-#define FC_SCORE_RAW 1
-#endif
 __device__ __forceinline__ uint32_t pk_min3_negpair(uint32_t a, uint32_t b, uint32_t c) {
   uint32_t r;
   asm("v_pk_minimum3_f16 %0, %1, %2, %3 op_sel_hi:[0,0,0] neg_lo:[1,1,1]"
@@ -1069,7 +1017,6 @@ __device__ __forceinline__ int fast_score_u8(const uint8_t* tile, int coff, int 
   const int off[16] = {3 * p,      3 * p + 1,  2 * p + 2,  p + 3,       3,  -p + 3,
                        -2 * p + 2, -3 * p + 1, -3 * p,     -3 * p - 1, -2 * p - 2, -p - 3,
                        -3,         p - 3,      2 * p - 2,  3 * p - 1};
-#if FC_SCORE_RAW
   // one base at the ring's top-left corner: every read is a non-negative
   // immediate offset when p is a compile-time constant
   // (the base offset is made opaque: hipcc would otherwise fold it back into
@@ -1083,22 +1030,6 @@ __device__ __forceinline__ int fast_score_u8(const uint8_t* tile, int coff, int 
 #pragma unroll
   for (int k = 0; k < 16; ++k)
     w3[k] = __builtin_bit_cast(h16x2, pk_min3_negpair(r[k], r[(k + 1) & 15], r[(k + 2) & 15]));
-#else
-  const _Float16 v = __builtin_bit_cast(_Float16, (uint16_t)c[0]);
-  const h16x2 vv = {v, -v}, sg = {(_Float16)-1.0f, (_Float16)1.0f};
-  h16x2 q[16];
-#pragma unroll
-  for (int k = 0; k < 16; ++k) {
-    const _Float16 ck = __builtin_bit_cast(_Float16, (uint16_t)c[off[k]]);
-    const h16x2 cc = {ck, ck};
-    q[k] = __builtin_elementwise_fma(cc, sg, vv);  // (v - ck, ck - v), exact
-  }
-  h16x2 w3[16];
-#pragma unroll
-  for (int k = 0; k < 16; ++k)
-    w3[k] = __builtin_elementwise_minimum(__builtin_elementwise_minimum(q[k], q[(k + 1) & 15]),
-                                          q[(k + 2) & 15]);
-#endif
   h16x2 w9[16];
 #pragma unroll
   for (int k = 0; k < 16; ++k)
@@ -1113,13 +1044,9 @@ __device__ __forceinline__ int fast_score_u8(const uint8_t* tile, int coff, int 
   const h16x2 ma = __builtin_elementwise_maximum(__builtin_elementwise_maximum(m5[0], m5[1]), m5[2]);
   const h16x2 mb = __builtin_elementwise_maximum(__builtin_elementwise_maximum(m5[3], m5[4]), m5[5]);
   h16x2 best = __builtin_elementwise_maximum(ma, mb);
-#if FC_SCORE_RAW
-  {
-    const _Float16 v = __builtin_bit_cast(_Float16, (uint16_t)c[0]);
-    const h16x2 vv = {v, -v};
-    best = best + vv;  // (dark, bright): exact sums of subnormals
-  }
-#endif
+  const _Float16 v = __builtin_bit_cast(_Float16, (uint16_t)c[0]);
+  const h16x2 vv = {v, -v};
+  best = best + vv;  // (dark, bright): exact sums of subnormals
   // the subnormal's bit pattern is the integer strength; negative -> 0
   const int s = (int)(short)__builtin_bit_cast(uint16_t, __builtin_fmaxf16(best.x, best.y));
   return min(max(s, 0), 255);
@@ -1136,11 +1063,7 @@ __device__ __forceinline__ int fast_score_u8(const uint8_t* tile, int coff, int 
 #define FC_WPE 7
 #endif
 template <int PT>
-#if FC_WPE > 0
 __global__ __launch_bounds__(64 * FC_WAVES) __attribute__((amdgpu_waves_per_eu(FC_WPE)))
-#else
-__global__ __launch_bounds__(64 * FC_WAVES)
-#endif
 void k_fast_cells(
     const uint8_t* __restrict__ img0, long long img0Pitch, int img0Stride,
     const uint8_t* __restrict__ arena, long long arenaPitch, OrbPlanDesc plan,
@@ -1159,7 +1082,6 @@ void k_fast_cells(
   uint8_t* sc = tile + tileElems;  // strengths, same byte layout as the tile
   uint16_t* queue = (uint16_t*)(sc + tileElems);
   uint16_t* corners = queue + FC_QCAP;
-  uint32_t* bits = (uint32_t*)(corners + FC_CCAP);  // row y: words 2y, 2y+1
   // this wave's cells: (bx * FC_CPW + j) * FC_WAVES + wave, j < FC_CPW; the
   // next cell's ROI is loaded into registers while this one is processed
   auto cell_of = [&](int j) { return cellBeg + (bx * FC_CPW + j) * FC_WAVES + wave; };
@@ -1183,17 +1105,8 @@ void k_fast_cells(
     const uint32_t o = (uint32_t)((q.y0 + r) * pitch + q.x0 - FAST_LPAD) + im.sh;
     rsh = o & 3u;
     const uint32_t a0 = o & ~3u;
-#if FC_LOAD3
-    // the row's bytes 0 .. C + 4 end inside the first 48 loaded bytes unless
-    // the cell is wider than 40 - rsh: the 4th 16-byte load only then (the
-    // stored bytes past C + 4 are never read for an interior pixel)
-    const int nLoads = (int)rsh + (q.x1 - q.x0) + FAST_LPAD > 48 ? 4 : 3;
-#else
-    const int nLoads = 4;
-#endif
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      if (k == 3 && nLoads < 4) break;
       const auto v = __builtin_amdgcn_raw_buffer_load_b128(im.r, (int)(a0 + 16 * k), 0, 0);
       raw[4 * k] = (uint32_t)v[0];
       raw[4 * k + 1] = (uint32_t)v[1];
@@ -1221,14 +1134,12 @@ void k_fast_cells(
                             __builtin_amdgcn_alignbyte(raw[2 * k + 2], raw[2 * k + 1], rsh));
     }
   }
-#if FC_ROWMAJOR
   // strengths start at 0 over the whole map: the halo and the columns past the
   // interior are never scored, so NMS reads 0 there without bounds tests
   {
     uint4* sc16 = reinterpret_cast<uint4*>(tile + tileElems);
     for (int i = lane; i < (tileElems >> 4); i += 64) sc16[i] = make_uint4(0u, 0u, 0u, 0u);
   }
-#endif
   const int ciNext = jc + 1 < FC_CPW ? cell_of(jc + 1) : cellEnd;
   if (ciNext < cellEnd) {
     ncd = cells[ciNext];
@@ -1242,8 +1153,6 @@ void k_fast_cells(
   const int iw = C - 6, ih = R - 6;
   const int nK = (iw + 7) >> 3;  // 8-pixel groups per interior row
   const int nvLast = iw - 8 * (nK - 1);
-  [[maybe_unused]] const unsigned long long outsideLast =
-      nvLast >= 8 ? 0ull : (0x0101010101010101ull << (8 * nvLast));
   const int ti = min(max(plan.iniTh, 0), 255), tm = min(max(plan.minTh, 0), 255);
   // quotients q = (int)((x + 0.5) * (1 / d)) for x < 2^13, d <= 88 are exact
   // with the hardware reciprocal (<= 1 ulp): (x + 0.5) / d sits >= 0.5 / d
@@ -1289,33 +1198,18 @@ void k_fast_cells(
   // corners.  Lane state: its pixel group (group k of an interior row) and the
   // group's tile byte `off`, advanced by 64 groups per round with adds.
   // Invalid lanes (past the window) and the pixels past the interior in a
-  // row's last group are masked out of the queue by SGPR lane masks; the
-  // queue writes of lanes that do not pass go to a per-lane trash word (the
-  // NMS bitmap, unused while a pass runs) instead of branching on EXEC.
+  // row's last group are masked out of the queue by the lane's pass mask.
   auto fast_pass = [&](int t, bool fresh) {
     h16x2 T;
     T.x = T.y = __builtin_bit_cast(_Float16, (uint16_t)(t + 1));
     const int nG = ih * nK;
-#if FC_PERM
-    // The queue is a set (scores, corners and the NMS bitmap do not depend on
-    // its order), so lanes may take the round's 64 pixel groups in any order:
-    // spread each LDS lane group's rows over the banks.
-    const int pl = 4 * (int)((0xFEAB6732DC894510ull >> (4 * (lane >> 2))) & 15u) + (lane & 3);
-#else
-    const int pl = lane;
-#endif
-    const int rr0 = (int)(((float)pl + 0.5f) * invK);
-    int k = pl - rr0 * nK;
+    const int rr0 = (int)(((float)lane + 0.5f) * invK);
+    int k = lane - rr0 * nK;
     int off = (rr0 + 3) * P + 8 + 8 * k;  // byte of interior column 8k
     const int rInc = (int)(64.5f * invK), kInc = 64 - rInc * nK;  // wave-uniform, = 64 / nK
     const int dOff = rInc * P + 8 * kInc, wrapOff = P - 8 * nK;
-    // trash slots in the NMS bitmap, as indices into the queue (u16) and the
-    // strength map (u64 words): 4- and 8-byte lane strides
-    [[maybe_unused]] const int trashQ = (int)(reinterpret_cast<uint16_t*>(bits) - queue) + 2 * lane;
-    unsigned long long* const sc64 = reinterpret_cast<unsigned long long*>(sc);
-    [[maybe_unused]] const int trashS = (int)(reinterpret_cast<unsigned long long*>(bits) - sc64) + lane;
     for (int g0 = 0; g0 < nG; g0 += 64) {
-      const bool valid = g0 + pl < nG;
+      const bool valid = g0 + lane < nG;
       const bool last = k == nK - 1;
       const int o = valid ? off : 3 * P + 8;  // invalid lanes read group 0 (masked below)
       {
@@ -1339,11 +1233,6 @@ void k_fast_cells(
       uint32_t rp[4];
 #pragma unroll
       for (int i = 0; i < 4; ++i) rp[i] = pretest_pair(V[i], Q0[i], Q4[i], Q8[i], Q12[i], T);
-#if !FC_ROWMAJOR
-      if (fresh)  // strengths start at 0, FAST_OUTSIDE past the interior (o is a multiple of 8)
-        sc64[valid ? (o >> 3) : trashS] = last ? outsideLast : 0ull;
-#endif
-#if FC_ROWMAJOR
       // lane-major append: lane = pixel group in row-major order, so the queue
       // (and the corner list built from it) is in cv::FAST's row-major order
       // and NMS can write the keys in place.  Pass mask: the sign bits of the
@@ -1370,20 +1259,6 @@ void k_fast_cells(
         queue[pos++] = (uint16_t)(off + j);
       }
       nq += __builtin_amdgcn_readlane(incl, 63);
-#else
-      // pixel j of a valid lane is interior when j < nvLast or the group is not a row's last
-      const unsigned long long vm = __ballot(valid), vIn = __ballot(valid && !last);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const uint32_t w = rp[j >> 1];
-        const bool sgn = (j & 1) ? ((int)w >= 0) : ((short)(w & 0xFFFFu) >= 0);
-        const unsigned long long bj = __ballot(sgn) & (j < nvLast ? vm : vIn);
-        const int pos = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(bj >> 32),
-                                                       __builtin_amdgcn_mbcnt_lo((uint32_t)bj, (uint32_t)nq));
-        queue[lane_select(bj, pos, trashQ)] = (uint16_t)(off + j);
-        nq += __popcll(bj);
-      }
-#endif
       }  // pretest
       k += kInc;
       off += dOff;
@@ -1398,44 +1273,11 @@ void k_fast_cells(
       }
     }
   };
-  // cell-local NMS at t into the row bitmap: a corner survives iff no
-  // neighbour inside the window has nb > t && nb >= m (outside counts as 0)
-  auto nms = [&](int t) {
-    for (int i = lane; i < 2 * ih; i += 64) bits[i] = 0;
-    wave_lds_sync();
-    const bool dense = nc > FC_CCAP;
-    const int nItems = dense ? ih * iw : nc;
-    for (int j = lane; j < nItems; j += 64) {
-      int x, y, off;
-      if (dense) {
-        y = (int)(((float)j + 0.5f) * invW);
-        x = j - y * iw;
-        off = (y + 3) * P + (x + 8);
-      } else {
-        off = corners[j];
-        const int ry = (int)(((float)off + 0.5f) * invP);
-        y = ry - 3;
-        x = off - ry * P - 8;
-      }
-      const uint8_t* cp = sc + off;
-      const int m = cp[0];
-      const int r0 = cp[-P - 1], r1 = cp[-P], r2 = cp[-P + 1], r3 = cp[-1], r4 = cp[1],
-                r5 = cp[P - 1], r6 = cp[P], r7 = cp[P + 1];
-      if (m <= t || m < 2) continue;
-      const bool L = x > 0, Rt = x < iw - 1, U = y > 0, D = y < ih - 1;
-      const int nb[8] = {(U && L) ? r0 : 0, U ? r1 : 0, (U && Rt) ? r2 : 0, L ? r3 : 0,
-                         Rt ? r4 : 0, (D && L) ? r5 : 0, D ? r6 : 0, (D && Rt) ? r7 : 0};
-      bool ok = true;
-#pragma unroll
-      for (int k = 0; k < 8; ++k) ok = ok && !(nb[k] > t && nb[k] >= m);
-      if (ok) atomicOr(&bits[2 * y + (x >> 5)], 1u << (x & 31));
-    }
-    wave_lds_sync();
-  };
-  // keys of the window in row-major order (lane = window row, ih <= 64)
+  // cell-local NMS at t: a corner survives iff no neighbour inside the window
+  // has nb > t && nb >= m (outside counts as 0).  The corner list (or, dense,
+  // the window) is in row-major order, so each survivor's key goes straight to
+  // its output position
   uint32_t* out = cellKeys + slot * plan.keyCap;
-  // FC_ROWMAJOR: the corner list (or, dense, the window) is in row-major
-  // order, so each survivor's key goes straight to its output position
   auto nms_emit = [&](int t) -> int {
     const bool dense = nc > FC_CCAP;
     const int nItems = dense ? ih * iw : nc;
@@ -1476,53 +1318,14 @@ void k_fast_cells(
     }
     return nOut;
   };
-  auto compact = [&]() -> int {
-    unsigned long long row = 0ull;
-    if (lane < ih) {
-      const uint2 w = *reinterpret_cast<const uint2*>(bits + 2 * lane);
-      row = (unsigned long long)w.x | ((unsigned long long)w.y << 32);
-    }
-    const int cnt = __popcll(row);
-    const int incl = wave_incl_scan(cnt);
-    const int total = __builtin_amdgcn_readlane(incl, 63);
-    int o = incl - cnt;
-    const uint8_t* srow = sc + (lane + 3) * P + 8;
-    const uint32_t kx = (uint32_t)(cd.x0 + 3), ky = (uint32_t)(cd.y0 + 3 + lane);
-    while (row) {
-      const int x0 = __builtin_ctzll(row);
-      row &= row - 1;
-      const bool two = row != 0;
-      const int x1 = two ? __builtin_ctzll(row) : x0;
-      if (two) row &= row - 1;
-      const int m0 = srow[x0], m1 = srow[x1];
-      out[o] = pack_key(kx + x0, ky, m0 - 1);
-      if (two) out[o + 1] = pack_key(kx + x1, ky, m1 - 1);
-      o += two ? 2 : 1;
-    }
-    return total;
-  };
   // ---- phase A at iniThFAST
-#if FC_ROWMAJOR
-  (void)nms;
-  (void)compact;
-#endif
   fast_pass(ti, true);
-#if FC_ROWMAJOR
   int n = nms_emit(ti);
-#else
-  nms(ti);
-  int n = compact();
-#endif
   if (n == 0 && tm != ti) {
     // ---- phase B: no keypoint at iniThFAST -> minThFAST (:846-850)
     nc = 0;
     fast_pass(tm, false);
-#if FC_ROWMAJOR
     n = nms_emit(tm);
-#else
-    nms(tm);
-    n = compact();
-#endif
   }
   if (lane == 0) cellCount[slot] = n;
   ci = ciNext;
@@ -2496,32 +2299,12 @@ struct DescWaveLds {
 #ifndef DESC_PPW
 #define DESC_PPW 4  // slot pairs per wave (software-pipelined: the next pair's window loads overlap this one)
 #endif
-#ifndef DESC_MIN_WAVES
-#define DESC_MIN_WAVES 0  // __launch_bounds__ minimum waves per SIMD (A/B knob: 5 -> <= 96 VGPRs)
-#endif
-#if DESC_MIN_WAVES > 0
-#define DESC_LAUNCH_BOUNDS __launch_bounds__(256, DESC_MIN_WAVES)
-#else
-#define DESC_LAUNCH_BOUNDS __launch_bounds__(256)
-#endif
-#ifndef DESC_LDS_TABLES
-#define DESC_LDS_TABLES 1  // rBRIEF pattern floats and column weights in LDS (k_orient_desc)
-#endif
-#ifndef DESC_MAGIC_ROUND
-#define DESC_MAGIC_ROUND 1  // rBRIEF sample coordinates rounded by the 1.5 * 2^23 adder
-#endif
-#ifndef DESC_ROW37
-#define DESC_ROW37 1     // row pass stops at column 36, the last one a sample reaches
-#endif
-#ifndef DESC_SMALL_CT
-#define DESC_SMALL_CT 1   // one-pair calls take k_orient_desc<1> (compile-time count), else <0>
-#endif
 // Attribution builds (phase stubs) and the measured-slower variants (LDS-DMA
 // window staging, double-buffered rows, MFMA row pass, packed rotation) are
 // patches against this file: tools/attribution/.
 
 template <int PPW>
-__global__ DESC_LAUNCH_BOUNDS void k_orient_desc(
+__global__ __launch_bounds__(256) void k_orient_desc(
     const uint8_t* __restrict__ img0, long long img0Pitch, int img0Stride,
     const uint8_t* __restrict__ arena, long long arenaPitch, OrbPlanDesc plan,
     const uint32_t* __restrict__ outKeys, const int32_t* __restrict__ outCount,
@@ -2532,7 +2315,6 @@ __global__ DESC_LAUNCH_BOUNDS void k_orient_desc(
   // PPW == 0: ppwRt
   const int ppw = PPW ? PPW : ppwRt;
   __shared__ __attribute__((aligned(16))) DescWaveLds sm[4];
-#if DESC_LDS_TABLES
   // per workgroup: the rBRIEF pattern as floats (one ds_read_b128 per test
   // pair of points instead of a constant-memory load and four conversions),
   // and the column-pass weights of both row parities (one ds_read_b128 per
@@ -2548,7 +2330,6 @@ __global__ DESC_LAUNCH_BOUNDS void k_orient_desc(
                      : make_uint4(18u << 16, 34u | 49u << 16, 55u | 49u << 16, 34u | 18u << 16);
     __syncthreads();  // before any wave can leave early
   }
-#endif
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
   const int half = lane >> 5, hl = lane & 31;
   int bx, img;
@@ -2677,8 +2458,6 @@ __global__ DESC_LAUNCH_BOUNDS void k_orient_desc(
  [[maybe_unused]] constexpr uint32_t T2a = (k0 << 16) | (k1 << 24), T2b = k2 | (k3 << 8) | (k4 << 16) | (k5 << 24), T2c = k6;
  [[maybe_unused]] constexpr uint32_t T3a = k0 << 24, T3b = k1 | (k2 << 8) | (k3 << 16) | (k4 << 24), T3c = k5 | (k6 << 8);
   typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
-  const u16x2 E0 = {18, 34}, E1 = {49, 55}, E2 = {49, 34}, E3 = {18, 0};
-  const u16x2 O0 = {0, 18}, O1 = {34, 49}, O2 = {55, 49}, O3 = {34, 18};
 
   // IC_Angle byte masks of the lane's two rows (the rows are the same for
   // every keypoint pair): loaded once instead of per pair
@@ -2761,13 +2540,12 @@ __global__ DESC_LAUNCH_BOUNDS void k_orient_desc(
       wave_lds_sync();
     }
     // ---- row pass: row-sum column c of staged row r = sum_i k_i * byte(r, c + i)
-    // ---- row pass: row-sum column c of staged row r = sum_i k_i * byte(r, c + i)
     if (second) {  // the lane's row pair from registers, group by group
       // (samples reach columns 0..36 only: |rotated pattern point| <= 18.4,
       // so the last group computes column 36 alone)
 #pragma unroll
       for (int g = 0; g < 10; ++g) {
-        if (DESC_ROW37 && g == 9) {
+        if (g == 9) {
           const uint32_t c0 = __builtin_amdgcn_udot4(RA[9], T0a, __builtin_amdgcn_udot4(RA[10], T0b, 0u, false), false);
           const uint32_t c1 = __builtin_amdgcn_udot4(RB[9], T0a, __builtin_amdgcn_udot4(RB[10], T0b, 0u, false), false);
           rsp[hl][36] = __builtin_amdgcn_perm(c1, c0, 0x05040100u);
@@ -2811,19 +2589,11 @@ __global__ DESC_LAUNCH_BOUNDS void k_orient_desc(
       a = cs;
       b = sn;
     }
-    const uint32_t wE[4] = {__builtin_bit_cast(uint32_t, E0), __builtin_bit_cast(uint32_t, E1),
-                            __builtin_bit_cast(uint32_t, E2), __builtin_bit_cast(uint32_t, E3)};
-    const uint32_t wO[4] = {__builtin_bit_cast(uint32_t, O0), __builtin_bit_cast(uint32_t, O1),
-                            __builtin_bit_cast(uint32_t, O2), __builtin_bit_cast(uint32_t, O3)};
-#if DESC_LDS_TABLES
-    (void)wE;
-    (void)wO;
     // the patch centre's row-sum pair (an opaque base: hipcc would split the
     // constant between the address and the 8-bit ds_read2 offsets)
     const uint32_t* rs0 = &sm[0].rsp[0][0][0];
     int rsc = (int)(&rsp[0][0] - rs0) + (18 * (DESC_RS_DW / 2) + 18);
     __asm__ volatile("" : "+v"(rsc));
-#if DESC_MAGIC_ROUND
     // cvRound by the adder: for |v| < 2^22, the bits of v + 1.5 * 2^23 are
     // 0x4B400000 + rint(v) (round half to even, as rintf), so a coordinate
     // costs one v_add_f32 instead of v_rndne + v_cvt; the biases of both
@@ -2835,16 +2605,6 @@ __global__ DESC_LAUNCH_BOUNDS void k_orient_desc(
     auto blurred = [&](int by, int bx) -> int {
       const uint32_t* p = rs0 + (rsc + __mul24(by & ~1, DESC_RS_DW / 2) + bx);
       const uint4 wv = sW[by & 1];
-#else
-    auto blurred = [&](float fy, float fx) -> int {
-      const int ry = cv_round(fy), rx = cv_round(fx);
-      // pair row (ry + 18) >> 1, column rx + 18: the constant part folds into
-      // the LDS offset, (ry & ~1) * (DESC_RS_DW / 2) is a signed 24-bit
-      // multiply (ry is -18..18; hipcc cannot bound a plain int product and
-      // emits the quarter-rate v_mul_lo_u32), the parity row is ry & 1
-      const uint32_t* p = rs0 + (rsc + __mul24(ry & ~1, DESC_RS_DW / 2) + rx);
-      const uint4 wv = sW[ry & 1];
-#endif
       const uint32_t wk[4] = {wv.x, wv.y, wv.z, wv.w};
       uint32_t s = 1u << 15;
 #pragma unroll
@@ -2853,40 +2613,16 @@ __global__ DESC_LAUNCH_BOUNDS void k_orient_desc(
                                    __builtin_bit_cast(u16x2, wk[k]), s, false);
       return min((int)(s >> 16), 255);
     };
-#else
-    auto blurred = [&](float fy, float fx) -> int {
-      const int ry = cv_round(fy), rx = cv_round(fx);
-      const int y = ry + 18;
-      const uint32_t* p = &rsp[y >> 1][rx + 18];
-      uint32_t s = 1u << 15;
-      const bool odd = y & 1;
-#pragma unroll
-      for (int k = 0; k < 4; ++k)
-        s = __builtin_amdgcn_udot2(__builtin_bit_cast(u16x2, p[k * DESC_RS_DW]),
-                                   __builtin_bit_cast(u16x2, odd ? wO[k] : wE[k]), s, false);
-      return min((int)(s >> 16), 255);
-    };
-#endif
     unsigned long long words[8];
 #pragma unroll
     for (int kq = 0; kq < 8; ++kq) {
       const int test = hl + 32 * kq;
-#if DESC_LDS_TABLES
       const float4 pt = sPat[test];
       const float px0 = pt.x, py0 = pt.y, px1 = pt.z, py1 = pt.w;
-#else
-      const float px0 = (float)c_pattern[4 * test], py0 = (float)c_pattern[4 * test + 1];
-      const float px1 = (float)c_pattern[4 * test + 2], py1 = (float)c_pattern[4 * test + 3];
-#endif
-#if DESC_MAGIC_ROUND
       const int v0 = blurred(__builtin_bit_cast(int, (px0 * b + py0 * a) + 12582912.0f),
                              __builtin_bit_cast(int, (px0 * a - py0 * b) + 12582912.0f));
       const int v1 = blurred(__builtin_bit_cast(int, (px1 * b + py1 * a) + 12582912.0f),
                              __builtin_bit_cast(int, (px1 * a - py1 * b) + 12582912.0f));
-#else
-      const int v0 = blurred(px0 * b + py0 * a, px0 * a - py0 * b);
-      const int v1 = blurred(px1 * b + py1 * a, px1 * a - py1 * b);
-#endif
       words[kq] = __ballot(v0 < v1);
     }
     if (P.active && hl == 0) {
@@ -3013,15 +2749,13 @@ hipError_t orb_k_pyr_resize(const uint8_t* src, long long srcImgPitch, int srcSt
   // each workgroup resizes one tile of PYR_IMAGES_PER_WG images (default
   // 16: with two extraction lanes 12 / 16 / 24 measured 323.8k / 322.3-324.4k /
   // 324.7k against 321.3-321.8k frames/s for 8, profiles/r03_lanes.txt)
-  // PYR_IMAGES_PER_WG images per workgroup; with PYR_TARGET_WGS > 0 fewer when
-  // the level would launch under that many workgroups (a workgroup walks its
-  // images one after another: C5's 16 1920x1080 frames are 510 workgroups of
-  // 16 images on level 1)
-  const int tiles = ((dw + PYR_TW - 1) / PYR_TW) * ((dh + PYR_TH - 1) / PYR_TH);
-  const int perWg =
-      PYR_TARGET_WGS > 0
-          ? std::max(1, std::min(PYR_IMAGES_PER_WG, (int)((long long)tiles * nimg / std::max(PYR_TARGET_WGS, 1))))
-          : PYR_IMAGES_PER_WG;
+  // (a workgroup walks its images one after another: C5's 16 1920x1080 frames
+  // are 510 workgroups of 16 images on level 1.  Fewer images per workgroup on
+  // levels that launch under 2048 workgroups resized those frames in 0.138
+  // instead of 0.198 ms, but C5's pipelined rate lost 5.5 % -- the wider resize
+  // crowds the matcher's 16-CU resolve -- and the headline did not move:
+  // profiles/r05_resize_target.txt)
+  const int perWg = PYR_IMAGES_PER_WG;
   dim3 grid((dw + PYR_TW - 1) / PYR_TW, (dh + PYR_TH - 1) / PYR_TH, (nimg + perWg - 1) / perWg),
       block(256);
   // every image base and row start 4-aligned: one load per staged dword
@@ -3159,7 +2893,7 @@ hipError_t orb_k_fast_cells(const uint8_t* img0, long long img0Pitch, int img0St
   const int tileElems = fc_tile_elems(mr, mc);
   const size_t lds = orb_k_fast_cells_lds(mr, mc);
   // every W = 30 cell grid of the ORB-SLAM2 configurations has ROI widths of
-  // 36-43 pixels: pitch 48 (56 without FC_TIGHT), the compile-time instance
+  // 36-43 pixels: pitch 48, the compile-time instance
   const bool p56 = fc_pitch(mc) == FC_CONST_PITCH;
   const void* fn = p56 ? (const void*)k_fast_cells<FC_CONST_PITCH> : (const void*)k_fast_cells<0>;
   if (lds > 65536) {
@@ -3273,7 +3007,7 @@ hipError_t orb_k_orient_desc(const uint8_t* img0, long long img0Pitch, int img0S
     hipLaunchKernelGGL(k_orient_desc<DESC_PPW>, grid, block, 0, s, img0, img0Pitch, img0Stride,
                        arena, arenaPitch, *plan, outKeys, outCount, errFlag, kps, desc, capacity,
                        counts, DESC_PPW, slotBeg, slotEnd);
-  else if (ppw == 1 && DESC_SMALL_CT)
+  else if (ppw == 1)
     hipLaunchKernelGGL(k_orient_desc<1>, grid, block, 0, s, img0, img0Pitch, img0Stride, arena,
                        arenaPitch, *plan, outKeys, outCount, errFlag, kps, desc, capacity, counts,
                        1, slotBeg, slotEnd);

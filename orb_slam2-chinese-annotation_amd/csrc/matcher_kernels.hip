@@ -307,17 +307,9 @@ __global__ __launch_bounds__(256) void k_grid_build4(const orb_keypoint_t* __res
 #ifndef PROJ_QB
 #define PROJ_QB 4  // window candidates scored per batch of descriptor loads
 #endif
-#ifndef PROJ_XCD
-#define PROJ_XCD 1  // XCD-contiguous workgroup order (A/B knob)
-#endif
 #ifndef PROJ_WG
 #define PROJ_WG 512  // map points per workgroup (grid staged once per workgroup; swept 256-1024)
 #endif
-// DIRECT: the staged grid and the cell table are read where k_grid_build left
-// them (L2-resident: 64 KB + 12 KB per C5 frame, the problem's workgroups
-// share one XCD) instead of being copied into LDS by every workgroup; the
-// workgroup then holds no LDS and the chip is not limited to two 1024-point
-// workgroups per CU
 // ncand of the projection matcher: the candidate count, with the point's
 // has_obs (a claim by it locks the keypoint) in bit 30, so the resolve reads one
 // word per point for both; -1 = not in view / bad
@@ -334,7 +326,7 @@ __device__ __forceinline__ const uint32_t* ovf_list(const ProjParams& P, int p, 
 
 // PPT: map points per thread (a workgroup covers WG * PPT points, the grid
 // staged once for all of them)
-template <int WG, bool DIRECT = false, int PPT = 1>
+template <int WG, int PPT = 1>
 __global__ __launch_bounds__(WG) void k_proj_candidates(
     const orb_keypoint_t* __restrict__ keys, const uint8_t* __restrict__ desc,
     const float* __restrict__ uright, const uint8_t* __restrict__ locked, int kpStride,
@@ -343,18 +335,13 @@ __global__ __launch_bounds__(WG) void k_proj_candidates(
     const int32_t* __restrict__ cellStart, const int32_t* __restrict__ cellIdx,
     const uint4* __restrict__ stagedGrid, int stageCap, ProjParams P,
     uint32_t* __restrict__ topk, int32_t* __restrict__ ncand) {
-  __shared__ int sCS[DIRECT ? 1 : GRID_CELLS + 1];
+  __shared__ int sCS[GRID_CELLS + 1];
   extern __shared__ __attribute__((aligned(16))) uint4 sKp[];  // min(kpStride, PROJ_STAGE)
   __shared__ float sScale[ORB_MAX_LEVELS];
   // XCD-contiguous order: a problem's workgroups share one L2, which then
   // serves the staged grid and the frame's descriptors to all of them
   int bx, p;
-#if PROJ_XCD
   xcd_swizzle(bx, p);
-#else
-  bx = blockIdx.x;
-  p = blockIdx.y;
-#endif
   const int tid = threadIdx.x;
   const int M = nmps[p], N = nkeys[p];
   if (bx * WG * PPT >= M) return;  // whole workgroup idle (uniform)
@@ -364,18 +351,12 @@ __global__ __launch_bounds__(WG) void k_proj_candidates(
   const float* UR = uright ? uright + (size_t)p * kpStride : nullptr;
   const int32_t* cs = cellStart + (size_t)p * (GRID_CELLS + 1);
   const int32_t* ci = cellIdx + (size_t)p * kpStride;
-  const bool staged = DIRECT || N <= stageCap;
+  const bool staged = N <= stageCap;
 #pragma unroll
   for (int i = 0; i < ORB_MAX_LEVELS; ++i)
     if (tid == i) sScale[i] = P.scale[i];
-  // the cell table and the cell-ordered keypoints scanned below: LDS copies,
-  // or (DIRECT) the global arrays themselves
-  const int* gCS = sCS;
-  const uint4* gKp = sKp;
-  if (DIRECT) {
-    gCS = cs;
-    gKp = stagedGrid + (size_t)p * kpStride;
-  } else if (staged) {
+  // LDS copies of the cell table and the cell-ordered keypoints scanned below
+  if (staged) {
     // (batches of loads issued before their stores: a load-store loop waits
     // one memory latency per iteration)
     const int nInGrid = cs[GRID_CELLS];
@@ -462,8 +443,8 @@ __global__ __launch_bounds__(WG) void k_proj_candidates(
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         const int col = min(ix0 + k, nMaxCellX) * ORB_GRID_ROWS;
-        lo[k] = gCS[col + nMinCellY];
-        len[k] = gCS[col + nMaxCellY + 1] - lo[k];
+        lo[k] = sCS[col + nMinCellY];
+        len[k] = sCS[col + nMaxCellY + 1] - lo[k];
       }
 #pragma unroll
       for (int k = 1; k < 4; ++k)
@@ -472,7 +453,7 @@ __global__ __launch_bounds__(WG) void k_proj_candidates(
       const int o1 = lo[1] - c1, o2 = lo[2] - c2, o3 = lo[3] - c3;
       for (int t = 0; t < total; ++t) {
         const int j = t + (t < c1 ? lo[0] : t < c2 ? o1 : t < c3 ? o2 : o3);
-        const uint4 E = gKp[j];
+        const uint4 E = sKp[j];
         const int oct = (int)((E.z >> 24) & 0x7Fu);
         if (oct < minL || oct > maxL) continue;
         const float dx = __uint_as_float(E.x) - x, dy = __uint_as_float(E.y) - y;
@@ -973,24 +954,11 @@ __device__ __forceinline__ int fp_choose(const uint32_t (&e)[TOPK], int nc, int 
 // ever needs more than its top 4 candidates).  Claims are double-buffered
 // (round r reads buffer (r-1)&1, writes r&1); a committed lock is -1 in both
 // buffers.  Every memory access of the window loop is LDS: the inputs of the
-// windows two and three ahead are loaded while the current one iterates
-// (FP_AHEAD), and the keypoint -> point result (kpMatch) is kept in LDS and
+// next two windows are loaded while the current one iterates,
+// and the keypoint -> point result (kpMatch) is kept in LDS and
 // written out once at the end, so no wait on a global access (loads, or the
 // kpMatch atomics, which share the in-order vmcnt counter with the loads on
 // gfx9) sits inside the loop; rounds synchronise on LDS only.
-#ifndef FP_AHEAD
-#define FP_AHEAD 2  // windows of inputs in flight ahead of the current one (1 or 2)
-#endif
-#ifndef FP_DEBUG
-#define FP_DEBUG 0  // diagnostic build: per-window rounds and clock stamps of problem 0
-#endif
-#if FP_DEBUG
-// [0] windows, then per window: rounds, cycles (s_memtime) at its end
-__device__ unsigned long long g_fp_dbg[2 + 2 * 256];
-extern "C" hipError_t orb_k_fp_debug(unsigned long long* out, int n) {
-  return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_fp_dbg), (size_t)n * 8, 0, hipMemcpyDeviceToHost);
-}
-#endif
 // PPT points per thread: a window of T * PPT points
 template <int T, int PPT = 1>
 __global__ __launch_bounds__(T) void k_proj_resolve_fp(
@@ -1040,20 +1008,14 @@ __global__ __launch_bounds__(T) void k_proj_resolve_fp(
   In inA[PPT], inB[PPT];
 #pragma unroll
   for (int k = 0; k < PPT; ++k) load(inA[k], k * T + t);
-#if FP_AHEAD > 1
   asm volatile("" ::: "memory");  // A's loads all issue before B's (in-order counts)
   __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
   for (int k = 0; k < PPT; ++k) load(inB[k], W + k * T + t);
-#endif
   __syncthreads();  // LDS reset before any window's claims
   int round = 0;  // global round counter: buffer parity and change flags
-#if FP_DEBUG
-  int dbgW = 0;
-  if (p == 0 && t == 0) g_fp_dbg[1] = __builtin_amdgcn_s_memtime();
-#endif
-  // one window: its inputs leave `in` (loaded FP_AHEAD windows earlier) and
-  // `in` is reloaded with the inputs FP_AHEAD windows on
+  // one window: its inputs leave `in` (loaded two windows earlier) and `in` is
+  // reloaded with the inputs two windows on
   auto window = [&](int start, In (&in)[PPT]) {
     uint32_t e[PPT][TOPK];
     int nc[PPT], prev[PPT], acc[PPT];
@@ -1115,25 +1077,13 @@ __global__ __launch_bounds__(T) void k_proj_resolve_fp(
     // the registers they came from (no copy, so no wait for them before the
     // window that uses them)
 #pragma unroll
-    for (int k = 0; k < PPT; ++k) load(in[k], start + FP_AHEAD * W + k * T + t);
+    for (int k = 0; k < PPT; ++k) load(in[k], start + 2 * W + k * T + t);
     lds_barrier();
-#if FP_DEBUG
-    if (p == 0 && t == 0 && dbgW < 256) {
-      g_fp_dbg[2 + 2 * dbgW] = (unsigned long long)round;
-      g_fp_dbg[3 + 2 * dbgW] = __builtin_amdgcn_s_memtime();
-      g_fp_dbg[0] = (unsigned long long)(dbgW + 1);
-    }
-    ++dbgW;
-#endif
   };
-#if FP_AHEAD > 1
   for (int start = 0; start < M; start += 2 * W) {
     window(start, inA);
     window(start + W, inB);  // (past M: one round in which nothing changes)
   }
-#else
-  for (int start = 0; start < M; start += W) window(start, inA);
-#endif
   int32_t* km = kpMatch + (size_t)p * kpStride;
   for (int i = t; i < n; i += T) km[i] = skm[i];
   matches = wave_sum(matches);
@@ -1327,15 +1277,10 @@ hipError_t orb_k_grid_build_staged(const orb_keypoint_t* keys, const int32_t* nk
 
 int orb_k_grid_stage_max(void) { return GB_LDS_KEYS; }
 
-// Compile-time variants of the candidate scan (tools/build_variant.sh; the
-// default build instantiates only the defaults):
-//   PROJ_DIRECT 1     scan the staged grid in global memory (no LDS copy)
-//   PROJ_PPT_LARGE 2  two map points per thread for large maps
-#ifndef PROJ_DIRECT
-#define PROJ_DIRECT 0
-#endif
+// Map points per thread of the candidate scan (tools/build_variant.sh sweeps
+// them; the default build instantiates only the defaults)
 #ifndef PROJ_PPT_LARGE
-#define PROJ_PPT_LARGE 1
+#define PROJ_PPT_LARGE 1  // for maps of at least PROJ_LARGE_MAP points
 #endif
 #ifndef PROJ_PPT_SMALL
 #define PROJ_PPT_SMALL 1  // map points per thread of the candidate scan for maps under PROJ_LARGE_MAP
@@ -1357,20 +1302,17 @@ hipError_t orb_k_proj_candidates(const orb_keypoint_t* keys, const uint8_t* desc
   // dynamic LDS: the staged keypoints of a frame, sized to the key capacity
   const int stageCap = std::min(kpStride, PROJ_STAGE);
   const bool large = stageCap > 2048 && mpMax >= PROJ_LARGE_MAP;
-  const bool direct = PROJ_DIRECT && stagedGrid;
-  const size_t lds = direct ? 0 : (size_t)stageCap * sizeof(uint4);
+  const size_t lds = (size_t)stageCap * sizeof(uint4);
   const void* fn;
   dim3 grid;
   int wg;
   if (large) {
-    constexpr int ppt = PROJ_DIRECT ? 1 : PROJ_PPT_LARGE;
-    fn = direct ? (const void*)k_proj_candidates<1024, true> : (const void*)k_proj_candidates<1024, false, ppt>;
-    grid = dim3((mpMax + 1024 * (direct ? 1 : ppt) - 1) / (1024 * (direct ? 1 : ppt)), nproblems);
+    fn = (const void*)k_proj_candidates<1024, PROJ_PPT_LARGE>;
+    grid = dim3((mpMax + 1024 * PROJ_PPT_LARGE - 1) / (1024 * PROJ_PPT_LARGE), nproblems);
     wg = 1024;
   } else {
-    fn = direct ? (const void*)k_proj_candidates<PROJ_WG, true>
-                : (const void*)k_proj_candidates<PROJ_WG, false, PROJ_PPT_SMALL>;
-    const int per = PROJ_WG * (direct ? 1 : PROJ_PPT_SMALL);
+    fn = (const void*)k_proj_candidates<PROJ_WG, PROJ_PPT_SMALL>;
+    const int per = PROJ_WG * PROJ_PPT_SMALL;
     grid = dim3((mpMax + per - 1) / per, nproblems);
     wg = PROJ_WG;
   }
@@ -1379,20 +1321,12 @@ hipError_t orb_k_proj_candidates(const orb_keypoint_t* keys, const uint8_t* desc
     if (e != hipSuccess) return e;
   }
   const uint4* sg = (const uint4*)stagedGrid;
-  if (large && direct)
-    hipLaunchKernelGGL((k_proj_candidates<1024, true>), grid, dim3(wg), lds, s, keys, desc, uright,
-                       locked, kpStride, nkeys, mps, mpDesc, nmps, mpStride, cellStart, cellIdx, sg,
-                       stageCap, P, topk, ncand);
-  else if (large)
-    hipLaunchKernelGGL((k_proj_candidates<1024, false, PROJ_PPT_LARGE>), grid, dim3(wg), lds, s, keys,
+  if (large)
+    hipLaunchKernelGGL((k_proj_candidates<1024, PROJ_PPT_LARGE>), grid, dim3(wg), lds, s, keys,
                        desc, uright, locked, kpStride, nkeys, mps, mpDesc, nmps, mpStride, cellStart,
                        cellIdx, sg, stageCap, P, topk, ncand);
-  else if (direct)
-    hipLaunchKernelGGL((k_proj_candidates<PROJ_WG, true>), grid, dim3(wg), lds, s, keys, desc, uright,
-                       locked, kpStride, nkeys, mps, mpDesc, nmps, mpStride, cellStart, cellIdx, sg,
-                       stageCap, P, topk, ncand);
   else
-    hipLaunchKernelGGL((k_proj_candidates<PROJ_WG, false, PROJ_PPT_SMALL>), grid, dim3(wg), lds, s, keys,
+    hipLaunchKernelGGL((k_proj_candidates<PROJ_WG, PROJ_PPT_SMALL>), grid, dim3(wg), lds, s, keys,
                        desc, uright, locked, kpStride, nkeys, mps, mpDesc, nmps, mpStride, cellStart,
                        cellIdx, sg, stageCap, P, topk, ncand);
   return hipGetLastError();
@@ -1426,9 +1360,6 @@ hipError_t orb_k_proj_candidates(const orb_keypoint_t* keys, const uint8_t* desc
 #endif
 #define RESOLVE_FP_MIN_MAP 20000
 #define RESOLVE_FP_FEW 8
-#ifndef RESOLVE_AUTO_FP
-#define RESOLVE_AUTO_FP 0  // 1: every call takes the fixed-point kernel (A/B knob)
-#endif
 #ifndef RESOLVE_W1_MIN
 #define RESOLVE_W1_MIN 128  // calls of at least this many problems take k_proj_resolve<1> (A/B knob)
 #endif
@@ -1439,8 +1370,7 @@ int orb_k_proj_resolve_kernel(int nproblems, int kpStride, int mpStride, int sch
   if (fpFits) {
     if (schedule == ORB_RESOLVE_JACOBI) return ORB_RESOLVE_KERNEL_JACOBI;
     if (schedule == ORB_RESOLVE_FIXED_POINT) return ORB_RESOLVE_KERNEL_FIXED_POINT;
-    if (schedule == ORB_RESOLVE_AUTO && (mpStride >= RESOLVE_FP_MIN_MAP || nproblems <= RESOLVE_FP_FEW ||
-                                         RESOLVE_AUTO_FP))
+    if (schedule == ORB_RESOLVE_AUTO && (mpStride >= RESOLVE_FP_MIN_MAP || nproblems <= RESOLVE_FP_FEW))
       return ORB_RESOLVE_KERNEL_FIXED_POINT;
   }
   if (mpStride >= RESOLVE_FP_MIN_MAP) return ORB_RESOLVE_KERNEL_PREFIX_W8;
@@ -1601,152 +1531,12 @@ __global__ __launch_bounds__(1024) void k_stereo_rows(const orb_keypoint_t* __re
   }
 }
 
-__global__ __launch_bounds__(256) void k_stereo_match(
-    const orb_keypoint_t* __restrict__ lkeys, const uint8_t* __restrict__ ldesc,
-    const int32_t* __restrict__ nleft, const orb_keypoint_t* __restrict__ rkeys,
-    const uint8_t* __restrict__ rdesc, const int32_t* __restrict__ nright, int kpStride,
-    const StereoPairLevels* __restrict__ pyr, StereoParams P, float* __restrict__ uRight,
-    float* __restrict__ depth, int32_t* __restrict__ sad, const int32_t* __restrict__ rowStart,
-    const int32_t* __restrict__ rowIdx, int rowCap) {
-  const int pair = blockIdx.y, lane = threadIdx.x & 63;
-  const int iL = blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int NL = nleft[pair], NR = nright[pair];
-  if (iL >= NL) return;
-  const size_t base = (size_t)pair * kpStride;
-  const orb_keypoint_t kpL = lkeys[base + iL];
-  float ur = -1.0f, dp = -1.0f;
-  int sadOut = -1;
-  const float mb = P.bf / P.fx;
-  const float minZ = mb, minD = 0.f, maxD = P.bf / minZ;
-  const int levelL = kpL.octave;
-  const float vL = kpL.y, uL = kpL.x;
-  const int row = (int)vL;  // vRowIndices[vL]: float -> size_t truncation
-  const float minU = uL - maxD, maxU = uL - minD;
-  int bestDist = 1 << 30, bestIdx = 1 << 30;
-  float bestX = 0.f;
-  (void)NR;
-  if (maxU >= 0 && row >= 0 && row < P.h[0]) {
-    const ulonglong4 dL = load_desc(ldesc + (base + iL) * 32);
-    // vCandidates = vRowIndices[vL]: the right keypoints whose band holds the row
-    const int32_t* rs = rowStart + (size_t)pair * (P.h[0] + 1);
-    const int32_t* ri = rowIdx + (size_t)pair * 2 * rowCap;
-    const float* rx = reinterpret_cast<const float*>(ri + rowCap);
-    const int jEnd = min(rs[row + 1], rowCap);
-    for (int j = rs[row] + lane; j < jEnd; j += 64) {
-      const int e = ri[j];
-      const float uR = rx[j];
-      const int iR = e & 0xFFFFFF, octR = e >> 24;
-      if (octR < levelL - 1 || octR > levelL + 1) continue;
-      if (!(uR >= minU && uR <= maxU)) continue;
-      const int dist = hamming256(dL, load_desc(rdesc + (base + iR) * 32));
-      // (distance, iR) order: a row list holds its entries in no particular order
-      if (dist < bestDist || (dist == bestDist && iR < bestIdx)) { bestDist = dist; bestIdx = iR; bestX = uR; }
-    }
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const int od = __shfl_xor(bestDist, o, 64), oi = __shfl_xor(bestIdx, o, 64);
-    const float ox = __shfl_xor(bestX, o, 64);
-    if (od < bestDist || (od == bestDist && oi < bestIdx)) { bestDist = od; bestIdx = oi; bestX = ox; }
-  }
-  // bestDist starts at TH_HIGH=100 in the reference; accept below (100+50)/2
-  if (maxU >= 0 && bestDist < 75) {
-    const float uR0 = bestX;
-    const float sf = P.invScale[levelL];
-    const float scaleduL = round_half_away(kpL.x * sf);
-    const float scaledvL = round_half_away(kpL.y * sf);
-    const float scaleduR0 = round_half_away(uR0 * sf);
-    const int w = 5, L = 5;
-    const float iniu = scaleduR0 + L - w;
-    const float endu = scaleduR0 + L + w + 1;
-    if (!(iniu < 0 || endu >= P.w[levelL])) {
-      const uint8_t* IL = pyr[pair].L[levelL];
-      const uint8_t* IR = pyr[pair].R[levelL];
-      const int sL = P.strideL[levelL], sR = P.strideR[levelL];
-      const int y0 = (int)scaledvL - w, xl0 = (int)scaleduL - w;
-      const int cL = IL[(long long)(y0 + w) * sL + xl0 + w];
-      // lane p < 121 (two rounds) owns patch pixel (yy, xx): its left value
-      // once, and the 11 right values it meets over the 11 shifts, which are
-      // consecutive bytes of one right row (four dword loads, realigned); the
-      // shifts' right centres come from lanes 0..10.  Per-shift SADs are
-      // < 121 * 255 < 2^16, so two share a word through the wave reduction.
-      const int xrb = (int)scaleduR0 - L - w;  // right patch column of shift -L
-      const int cRv = lane < 2 * L + 1 ? (int)IR[(long long)(y0 + w) * sR + xrb + w + lane] : 0;
-      uint32_t acc[11];
-      // |(l - cL) - (r - cR_k)| as one v_sad_u16 on values biased by 256
-      // (both in [1, 511]); the right byte and its shift's bias in one add
-      uint32_t rbias[11];
-#pragma unroll
-      for (int k = 0; k < 11; ++k) {
-        acc[k] = 0u;
-        rbias[k] = (uint32_t)(256 - __builtin_amdgcn_readlane(cRv, k));
-      }
-#pragma unroll
-      for (int q = 0; q < 2; ++q) {
-        const int p = lane + 64 * q;
-        if (p < 121) {
-          const int yy = p / 11, xx = p - yy * 11;
-          const uint32_t ab = (uint32_t)((int)IL[(long long)(y0 + yy) * sL + xl0 + xx] - cL + 256);
-          const uint8_t* rrow = IR + (long long)(y0 + yy) * sR + xrb + xx;
-          const uintptr_t ra = (uintptr_t)rrow;
-          const uint32_t* rw = reinterpret_cast<const uint32_t*>(ra & ~(uintptr_t)3);
-          const uint32_t shb = (uint32_t)(ra & 3);
-          uint32_t wv[4];
-#pragma unroll
-          for (int k = 0; k < 4; ++k) wv[k] = rw[k];
-          uint32_t bw[3];
-#pragma unroll
-          for (int k = 0; k < 3; ++k) bw[k] = __builtin_amdgcn_alignbyte(wv[k + 1], wv[k], shb);
-#pragma unroll
-          for (int k = 0; k < 11; ++k) {
-            const uint32_t bb = ((bw[k >> 2] >> (8 * (k & 3))) & 0xFFu) + rbias[k];
-            acc[k] = __builtin_amdgcn_sad_u16(ab, bb, acc[k]);
-          }
-        }
-      }
-      int dists[11];
-#pragma unroll
-      for (int k = 0; k < 11; k += 2) {
-        const int packed = (int)(acc[k] | (k + 1 < 11 ? acc[k + 1] << 16 : 0u));
-        const int sum = wave_sum(packed);
-        dists[k] = sum & 0xFFFF;
-        if (k + 1 < 11) dists[k + 1] = (int)((uint32_t)sum >> 16);
-      }
-      int bestSad = 2147483647, bestinc = 0;
-#pragma unroll
-      for (int inc = -L; inc <= L; ++inc)
-        if ((float)dists[inc + L] < (float)bestSad) { bestSad = dists[inc + L]; bestinc = inc; }
-      if (bestinc != -L && bestinc != L) {
-        const float dist1 = (float)dists[L + bestinc - 1], dist2 = (float)dists[L + bestinc],
-                    dist3 = (float)dists[L + bestinc + 1];
-        const float deltaR = __fdiv_rn(dist1 - dist3, 2.0f * (dist1 + dist3 - 2.0f * dist2));
-        if (!(deltaR < -1 || deltaR > 1)) {
-          float bestuR = P.scale[levelL] * ((float)scaleduR0 + (float)bestinc + deltaR);
-          float disparity = uL - bestuR;
-          if (disparity >= minD && disparity < maxD) {
-            if (disparity <= 0) {
-              disparity = 0.01f;
-              bestuR = (float)((double)uL - 0.01);
-            }
-            dp = __fdiv_rn(P.bf, disparity);
-            ur = bestuR;
-            sadOut = bestSad;
-          }
-        }
-      }
-    }
-  }
-  if (lane == 0) {
-    uRight[base + iL] = ur;
-    depth[base + iL] = dp;
-    sad[base + iL] = sadOut;
-  }
-}
-
-// 64 / G left keypoints per wave (lane group h = lanes G h .. G h + G - 1
-// takes keypoint (64 / G) w + h): the same steps as k_stereo_match, with the
-// candidate reduction, the right centres and the SAD sums kept inside each
-// group.  The kernel is a chain of dependent loads per keypoint (row band,
+// ComputeStereoMatches' per-keypoint search: the best right descriptor among
+// the row's candidates, then the 11-shift SAD refinement around it and the
+// parabola fit.  64 / G left keypoints per wave (lane group h = lanes G h ..
+// G h + G - 1 takes keypoint (64 / G) w + h), with the candidate reduction,
+// the right centres and the SAD sums kept inside each group.
+// The kernel is a chain of dependent loads per keypoint (row band,
 // candidates, descriptors, then the patches), so its cost beside the
 // extraction is the wave slots it holds: C3's stereo match 0.535 ms per 256
 // pairs with one keypoint per wave, 0.445 with two, 0.412 with four
@@ -1791,6 +1581,7 @@ __global__ __launch_bounds__(256) void k_stereo_match2(
   const bool scan = live && maxU >= 0 && row >= 0 && row < P.h[0];
   if (scan) {
     const ulonglong4 dL = load_desc(ldesc + (base + iL) * 32);
+    // vCandidates = vRowIndices[vL]: the right keypoints whose band holds the row
     const int32_t* rs = rowStart + (size_t)pair * (P.h[0] + 1);
     const int32_t* ri = rowIdx + (size_t)pair * 2 * rowCap;
     const float* rx = reinterpret_cast<const float*>(ri + rowCap);
@@ -1812,6 +1603,7 @@ __global__ __launch_bounds__(256) void k_stereo_match2(
     const float ox = __shfl_xor(bestX, o, 64);
     if (od < bestDist || (od == bestDist && oi < bestIdx)) { bestDist = od; bestIdx = oi; bestX = ox; }
   }
+  // bestDist starts at TH_HIGH=100 in the reference; accept below (100+50)/2
   const bool matched = scan && bestDist < 75;  // uniform within the half
   float scaleduR0 = 0.f;
   bool patch = false;
@@ -1841,12 +1633,19 @@ __global__ __launch_bounds__(256) void k_stereo_match2(
     // the half's lanes 0..10 load its shifts' right centres; every lane of
     // the half takes them by a lane shuffle inside the half
     const int cRv = (patch && hl < 2 * L + 1) ? (int)IR[(long long)(y0 + w) * sR + xrb + w + hl] : 0;
+    // |(l - cL) - (r - cR_k)| as one v_sad_u16 on values biased by 256
+    // (both in [1, 511]); the right byte and its shift's bias in one add
     uint32_t acc[11], rbias[11];
 #pragma unroll
     for (int k = 0; k < 11; ++k) {
       acc[k] = 0u;
       rbias[k] = (uint32_t)(256 - __shfl(cRv, (lane & ~(G - 1)) + k, 64));
     }
+    // group lane p < 121 (in rounds of G) owns patch pixel (yy, xx): its left
+    // value once, and the 11 right values it meets over the 11 shifts, which
+    // are consecutive bytes of one right row (four dword loads, realigned).
+    // Per-shift SADs are < 121 * 255 < 2^16, so two share a word through the
+    // group reduction.
     if (patch) {
 #pragma unroll
       for (int q = 0; q < (121 + G - 1) / G; ++q) {
@@ -1911,10 +1710,6 @@ __global__ __launch_bounds__(256) void k_stereo_match2(
     sad[base + iL] = sadOut;
   }
 }
-
-#ifndef STEREO_KPW
-#define STEREO_KPW 4  // left keypoints per wave of the stereo match: 4 (16-lane groups), 2, or 1 (k_stereo_match)
-#endif
 
 // Median-based outlier rejection: k-th smallest SAD by bisection on the value
 // (k = V/2 of the V valid matches, == vDistIdx[size/2] after the sort), then
@@ -1986,21 +1781,11 @@ extern "C" hipError_t orb_k_stereo(const orb_keypoint_t* lkeys, const uint8_t* l
                      kpStride, P, rowStart, rowIdx, (int)(idxInts / 2));
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  if (STEREO_KPW == 4)
-    hipLaunchKernelGGL(k_stereo_match2<16>, dim3((maxLeft + 15) / 16, npairs), dim3(256), 0, s, lkeys,
-                       ldesc, nleft, rkeys, rdesc, nright, kpStride,
-                       pyr, P, uRight, depth, sad, rowStart, rowIdx,
-                       (int)(idxInts / 2));
-  else if (STEREO_KPW == 2)
-    hipLaunchKernelGGL(k_stereo_match2<32>, dim3((maxLeft + 7) / 8, npairs), dim3(256), 0, s, lkeys,
-                       ldesc, nleft, rkeys, rdesc, nright, kpStride,
-                       pyr, P, uRight, depth, sad, rowStart, rowIdx,
-                       (int)(idxInts / 2));
-  else
-    hipLaunchKernelGGL(k_stereo_match, dim3((maxLeft + 3) / 4, npairs), dim3(256), 0, s, lkeys,
-                       ldesc, nleft, rkeys, rdesc, nright, kpStride,
-                       pyr, P, uRight, depth, sad, rowStart, rowIdx,
-                       (int)(idxInts / 2));
+  // four left keypoints per wave (16-lane groups)
+  hipLaunchKernelGGL(k_stereo_match2<16>, dim3((maxLeft + 15) / 16, npairs), dim3(256), 0, s, lkeys,
+                     ldesc, nleft, rkeys, rdesc, nright, kpStride,
+                     pyr, P, uRight, depth, sad, rowStart, rowIdx,
+                     (int)(idxInts / 2));
   e = hipGetLastError();
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(k_stereo_prune, dim3(npairs), dim3(256), 0, s, nleft, kpStride, uRight,

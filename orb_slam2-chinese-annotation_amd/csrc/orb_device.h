@@ -278,17 +278,9 @@ __device__ __forceinline__ int key_s(uint32_t k) { return (int)(k >> 24); }
 // every XCD fetches every image.  xcd_swizzle remaps the linear id so that XCD
 // k runs one contiguous range of (blockIdx.x, blockIdx.y): the workgroups in
 // flight on an XCD cover a couple of images, whose rows its L2 then serves.
-#ifndef ORB_XCD_SWIZZLE
-#define ORB_XCD_SWIZZLE 1
-#endif
 __device__ __forceinline__ void xcd_swizzle(int& bx, int& by) {
   const int gx = gridDim.x, n = gx * gridDim.y;
   const int L = blockIdx.x + gx * blockIdx.y;
-  if (!ORB_XCD_SWIZZLE) {
-    bx = blockIdx.x;
-    by = blockIdx.y;
-    return;
-  }
   const int xcd = L & 7, pos = L >> 3, q = n >> 3, r = n & 7;
   const int logical = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + pos;
   by = logical / gx;
@@ -296,17 +288,8 @@ __device__ __forceinline__ void xcd_swizzle(int& bx, int& by) {
 }
 // The same over a 3-D grid (x fastest, then y, then z): XCD k runs one
 // contiguous range of (x, y, z).
-#ifndef ORB_XCD_SWIZZLE3
-#define ORB_XCD_SWIZZLE3 1
-#endif
 __device__ __forceinline__ void xcd_swizzle3(int& bx, int& by, int& bz) {
   const int gx = gridDim.x, gxy = gx * gridDim.y, n = gxy * gridDim.z;
-  if (!ORB_XCD_SWIZZLE3) {
-    bx = blockIdx.x;
-    by = blockIdx.y;
-    bz = blockIdx.z;
-    return;
-  }
   const int L = blockIdx.x + gx * blockIdx.y + gxy * blockIdx.z;
   const int xcd = L & 7, pos = L >> 3, q = n >> 3, r = n & 7;
   const int logical = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + pos;

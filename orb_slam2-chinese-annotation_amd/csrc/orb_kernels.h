@@ -60,7 +60,6 @@ hipError_t orb_k_orient_desc(const uint8_t* img0, long long img0Pitch, int img0S
                              int levelEnd, hipStream_t s);
 
 // ------------------------------------------------------ matcher_kernels.hip
-hipError_t orb_k_fp_debug(unsigned long long* out, int n);
 hipError_t orb_k_hamming(const uint8_t* a, const uint8_t* b, int n, int32_t* out, hipStream_t s);
 hipError_t orb_k_grid_build(const orb_keypoint_t* keys, const int32_t* nkeys, int kpStride,
                             float minX, float minY, float invW, float invH, int32_t* cellStart,

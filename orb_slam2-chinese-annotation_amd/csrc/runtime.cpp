@@ -89,11 +89,7 @@ struct CallOrder {
 // the stream's last operation (profiles/r06_dropin_timeline.txt); polling the
 // stream returns within a query (~1 us) of it.  Bounded: past 2 ms of polling
 // the wait blocks as hipStreamSynchronize does.
-#ifndef ORB_POLL_WAIT
-#define ORB_POLL_WAIT 1  // A/B knob (0: hipStreamSynchronize)
-#endif
 static hipError_t stream_wait(hipStream_t s) {
-  if (!ORB_POLL_WAIT) return hipStreamSynchronize(s);
   const auto t0 = std::chrono::steady_clock::now();
   for (unsigned i = 1;; ++i) {
     const hipError_t e = hipStreamQuery(s);
@@ -370,9 +366,6 @@ static void compute_tables(orb_extractor* h) {
 
 // Build the plan for a W x H input (level sizes, resize tables, FAST cells,
 // octree roots, output slots) and upload its tables.
-#ifndef PYR_FUSE2
-#define PYR_FUSE2 1  // level pairs in one k_pyr_resize2 launch where they fit (0: one launch per level)
-#endif
 #ifndef PYR_PAIR_MAX_IMAGES
 // calls of at most this many images take the level pairs; larger batches one
 // launch per level: the pairs save a frame 4 us of latency but cost batches
@@ -579,7 +572,7 @@ static orb_status_t build_plan(orb_extractor* h, int W, int H) {
   for (int l = 1; l < L;) {
     OrbLevelDesc& d = P.lv[l];
     d.resize2 = 0;
-    if (PYR_FUSE2 && l + 1 < L && d.resizeMode == ORB_RESIZE_NARROW &&
+    if (l + 1 < L && d.resizeMode == ORB_RESIZE_NARROW &&
         P.lv[l + 1].resizeMode == ORB_RESIZE_NARROW) {
       const OrbLevelDesc& e = P.lv[l + 1];
       d.resize2 = orb_k_pyr_resize2_fits(P.lv[l - 1].w, P.lv[l - 1].h, d.w, d.h, &rtab[d.rtabX],
@@ -671,7 +664,7 @@ static orb_status_t ensure_batch(orb_extractor* h, int B) {
   return ORB_OK;
 }
 
-static int stream_prio(bool least);
+static int least_stream_prio();
 // The shared side streams (shared_side_stream below) are destroyed by an exit
 // handler; run_batch holds g_sideUse shared while it enqueues, and a call that
 // starts after the release fails with ORB_EDEVICE instead of launching on a
@@ -713,7 +706,7 @@ static orb_status_t run_batch(orb_extractor* h, const uint8_t* d_images, int B, 
   {
     if (capturing) {
       if (!h->privSide &&
-          hipStreamCreateWithPriority(&h->privSide, hipStreamNonBlocking, stream_prio(true)) != hipSuccess) {
+          hipStreamCreateWithPriority(&h->privSide, hipStreamNonBlocking, least_stream_prio()) != hipSuccess) {
         h->privSide = nullptr;
         return ORB_EDEVICE;
       }
@@ -861,18 +854,12 @@ orb_status_t orb_device_count(int* n) {
   return c > 0 ? ORB_OK : ORB_ENODEV;
 }
 
-// Stream priorities: the least (least == true) or the normal stream priority of
-// the device; SIDE_PRIO (compile-time A/B: 0 least, 1 normal, 2 greatest) picks
-// the "least" one for the pooled side stream of a SIDE_CUMASK=0 build and for
-// the handles' own streams.
-#ifndef SIDE_PRIO
-#define SIDE_PRIO 0
-#endif
-static int stream_prio(bool least) {
+// The device's least stream priority: the handles' own streams take it (see
+// create_own_stream).
+static int least_stream_prio() {
   int lo = 0, hi = 0;
   hipDeviceGetStreamPriorityRange(&lo, &hi);
-  if (!least) return 0;
-  return SIDE_PRIO == 0 ? lo : SIDE_PRIO == 1 ? 0 : hi;
+  return lo;
 }
 // One side stream per device, shared by every extractor handle of the process.
 // Each stream holds an HSA queue, and a process with more queues than the
@@ -881,9 +868,6 @@ static int stream_prio(bool least) {
 // its extraction by 30-50 % whenever a matcher ran beside it
 // (profiles/r03_streams.txt).  Handles on one device share it safely: fork /
 // join are per-handle events.
-#ifndef SIDE_CUMASK
-#define SIDE_CUMASK 1  // the side stream on an HSA queue of its own (a full-CU-mask stream)
-#endif
 static std::mutex g_sideMu;
 static hipStream_t g_side[64] = {};
 // The side streams are released by the process's exit handlers before the HIP
@@ -900,7 +884,7 @@ static void release_side_streams() {
       st = nullptr;
     }
 }
-static hipStream_t shared_side_stream(int device, int prio) {
+static hipStream_t shared_side_stream(int device) {
   hipStream_t* s = g_side;
   if (device < 0 || device >= 64) return nullptr;
   std::lock_guard<std::mutex> g(g_sideMu);
@@ -910,19 +894,14 @@ static hipStream_t shared_side_stream(int device, int prio) {
 #endif
   if (SIDE_RELEASE_AT_EXIT && !registered) registered = std::atexit(release_side_streams) == 0;
   if (!s[device]) {
-    hipError_t e;
-    if (SIDE_CUMASK) {
-      // HIP gives a CU-masked stream an HSA queue of its own instead of a
-      // pooled one: a mask of every CU of the device
-      hipDeviceProp_t prop;
-      e = hipGetDeviceProperties(&prop, device);
-      if (e == hipSuccess) {
-        std::vector<uint32_t> mask((prop.multiProcessorCount + 31) / 32, 0u);
-        for (int c = 0; c < prop.multiProcessorCount; ++c) mask[c >> 5] |= 1u << (c & 31);
-        e = hipExtStreamCreateWithCUMask(&s[device], (uint32_t)mask.size(), mask.data());
-      }
-    } else {
-      e = hipStreamCreateWithPriority(&s[device], hipStreamNonBlocking, prio);
+    // HIP gives a CU-masked stream an HSA queue of its own instead of a
+    // pooled one: a mask of every CU of the device
+    hipDeviceProp_t prop;
+    hipError_t e = hipGetDeviceProperties(&prop, device);
+    if (e == hipSuccess) {
+      std::vector<uint32_t> mask((prop.multiProcessorCount + 31) / 32, 0u);
+      for (int c = 0; c < prop.multiProcessorCount; ++c) mask[c >> 5] |= 1u << (c & 31);
+      e = hipExtStreamCreateWithCUMask(&s[device], (uint32_t)mask.size(), mask.data());
     }
     if (e != hipSuccess) s[device] = nullptr;
   }
@@ -939,23 +918,20 @@ static hipStream_t shared_side_stream(int device, int prio) {
 // after three idle normal streams had been created first, with or without
 // this library (tools/probe/contention_probe.py, profiles/r05_contention.txt).
 // The least priority keeps the library out of the pools the caller's streams
-// use (the side stream has a queue of its own, SIDE_CUMASK).
-#ifndef OWN_PRIO
-#define OWN_PRIO 0  // handles' own streams: 0 least priority, 1 normal (compile-time A/B)
-#endif
+// use (the side stream has a queue of its own, a full-CU-mask stream).
 static hipError_t create_own_stream(hipStream_t* s) {
-  return hipStreamCreateWithPriority(s, hipStreamNonBlocking, OWN_PRIO ? 0 : stream_prio(true));
+  return hipStreamCreateWithPriority(s, hipStreamNonBlocking, least_stream_prio());
 }
 
 static bool create_side_streams(orb_extractor* h) {
   // The side stream must not share an HSA queue with the caller's stream: two
   // streams on one queue run in submission order, which would serialise level
   // 0's FAST with the resize chain.  It is a full-CU-mask stream (a queue of
-  // its own, round 5); a SIDE_CUMASK=0 build takes a least-priority pooled
-  // stream instead (round 3: the chain on the caller's stream then wins the
-  // CUs the side FAST also wants, extraction 1.703 vs 1.727 ms per 512
-  // frames; profiles/r03_streams.txt)
-  h->stream2 = shared_side_stream(h->device, stream_prio(true));
+  // its own, round 5).  Round 3 took a least-priority pooled stream instead:
+  // the chain on the caller's stream then wins the CUs the side FAST also
+  // wants, extraction 1.703 vs 1.727 ms per 512 frames
+  // (profiles/r03_streams.txt)
+  h->stream2 = shared_side_stream(h->device);
   return h->stream2 != nullptr;
 }
 
@@ -1093,11 +1069,8 @@ orb_status_t orb_extractor_extract_batch(orb_extractor_t* h, const uint8_t* d_im
 // Row pitch of the one-frame path's staged image (pinned and device): the
 // width itself (the kernels take any stride), so a contiguous caller image is
 // staged with one memcpy instead of one per row
-#ifndef ONE_PITCH_ALIGN
-#define ONE_PITCH_ALIGN 1  // (A/B knob: 64 = rows padded to 64 bytes)
-#endif
 static size_t one_stride(int width) {
-  return ((size_t)width + ONE_PITCH_ALIGN - 1) / ONE_PITCH_ALIGN * ONE_PITCH_ALIGN;
+  return (size_t)width;
 }
 
 orb_status_t orb_extractor_extract(orb_extractor_t* h, const uint8_t* image, int width,

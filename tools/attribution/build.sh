@@ -26,6 +26,9 @@
 # Select the build with ORB_AMD_LIB=<path>.  variants.patch is the diff from
 # the product file to the round-5 source that held these blocks inline
 # (regenerate: tools/unifdef.py resolves them, see its docstring).
+# Every patch here must apply to csrc/ as it stands, without fuzz
+# (tests/test_attribution_patches.py); the A/B switches whose question is
+# settled are not kept as patches (DESIGN.md §11 names the commit that has them).
 set -e
 NAME=$1; FLAGS=$2
 R=$(cd "$(dirname "$0")/../.." && pwd)

@@ -6,7 +6,7 @@ the given macros, keep every other conditional as it is.
 
 Used to keep the attribution builds (phase stubs, clock stamps) out of the
 product source: the product holds the resolved text, and tools/attribution/
-keeps each variant as a patch against it (tools/attribution/apply.sh).
+keeps each variant as a patch against it (tools/attribution/build.sh).
 """
 import re
 import sys
