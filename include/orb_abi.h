@@ -447,7 +447,27 @@ orb_status_t orb_frustum_batch(orb_matcher_t* m, int n_problems, const orb_map_p
 /* Frame::ComputeStereoMatches for one rectified pair.  Left/right keypoints
  * and descriptors as produced by the two extractors, plus both pyramids
  * (level l of side s at pyr[s][l] with the given stride/size).  Writes
- * mvuRight / mvDepth (-1 = no match). Host buffers. */
+ * mvuRight / mvDepth (-1 = no match). Host buffers.
+ *
+ * Defined input domain (this entry, _batch and _extracted alike).  The
+ * reference indexes vRowIndices and cuts its 11x11 windows without a bounds
+ * check (src/Frame.cc:543,565,619,639), so it is defined only where
+ *   - every octave lies in [0, n_levels);
+ *   - every right keypoint's row band [floor(y - 2 s), ceil(y + 2 s)], s its
+ *     octave's scale factor, lies in [0, H - 1], H = level_height[0], and every
+ *     left keypoint's (int)y does;
+ *   - every left keypoint's window fits its level: 5 <= roundf(x * inv) <=
+ *     width - 6 and 5 <= roundf(y * inv) <= height - 6 at its octave;
+ *   - every right keypoint that can be a left keypoint's best candidate has
+ *     roundf(uR * inv) >= 10 at the LEFT keypoint's octave: the 11 shifts reach
+ *     10 columns left of it (the right side is guarded, :633).
+ * Keypoints of the extractors satisfy all four (EDGE_THRESHOLD = 19).  Inside
+ * the domain the outputs equal the reference's bit for bit.  Outside it the
+ * device code clamps the row bands to the image and skips a left keypoint
+ * whose row is outside it, but the windows are read as given: the result is
+ * unspecified and the reads may leave the level.
+ * With no match at all (the reference then indexes an empty vector, :691)
+ * every output is -1. */
 typedef struct orb_stereo_input {
   const orb_frame_t* left;       /* mvKeys, mDescriptors (u_right ignored) */
   int32_t n_right;
@@ -471,7 +491,15 @@ orb_status_t orb_stereo_match(orb_matcher_t* m, const orb_stereo_input_t* in,
  * and right images went through orb_extractor_extract_batch on left_ext and
  * right_ext (pyramids are read from those handles).  Keypoints/descriptors as
  * written by the two batches (pair i at i*kp_stride), counts d_left_n/d_right_n.
- * Writes d_u_right / d_depth (-1 = none) and d_sad (SAD of kept matches, -1). */
+ * Writes, for i < d_left_n[pair] only (slots past the count are not touched):
+ * d_u_right / d_depth (-1 = none), and d_sad = the best SAD (vDistIdx's first
+ * member, src/Frame.cc:685) of every match found, INCLUDING those the median
+ * test of :690-703 then resets to -1 in d_u_right / d_depth; -1 where no match
+ * was found.  So d_sad[i] >= 0 with d_u_right[i] == -1 marks a pruned match.
+ * The match kernel reads right-image rows in aligned 16-byte spans, of which
+ * it uses the 11 bytes inside the level: a span may end up to 4 bytes past
+ * its row, so past the last row of the right batch's last image (level 0 is
+ * the caller's d_images) up to 4 bytes may be read and ignored. */
 orb_status_t orb_stereo_match_batch(orb_matcher_t* m, int n_pairs, orb_extractor_t* left_ext,
                                     orb_extractor_t* right_ext, const orb_keypoint_t* d_left_keys,
                                     const uint8_t* d_left_desc, const int32_t* d_left_n,

@@ -285,11 +285,18 @@ def stereo_struct(lkeys, ldesc, scale, rkeys, rdesc, lpyr, rpyr, inv_scale, bf, 
     return s, (f, keep, rkeys, rdesc, lp, rp, lptr, rptr, w, h, st, inv)
 
 
-def stereo_match(*args):
+def stereo_match(*args, with_sad=False):
+    """(mvuRight, mvDepth); with_sad adds the int32 best SAD of every match accepted
+    before the median prune (vDistIdx's first member), -1 elsewhere."""
     s, keep = stereo_struct(*args)
     n = keep[0].n
     ur = np.full(n, -1, np.float32)
     dp = np.full(n, -1, np.float32)
+    if with_sad:
+        sad = np.full(n, -1, np.int32)
+        lib().oracle_stereo_match_sad.argtypes = [ctypes.c_void_p] * 4
+        lib().oracle_stereo_match_sad(ctypes.byref(s), _p(ur), _p(dp), _p(sad))
+        return ur, dp, sad
     lib().oracle_stereo_match.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
     lib().oracle_stereo_match(ctypes.byref(s), _p(ur), _p(dp))
     return ur, dp

@@ -1036,10 +1036,14 @@ static int search_by_bow(int n_kf, const uint8_t* kf_desc, const float* kf_angle
 }
 
 // a11: ComputeStereoMatches, src/Frame.cc:516-704 (debug ofstream of :556,652 omitted)
-static void stereo_matches(const orb_stereo_input_t* in, float* uRight, float* depth) {
+// sad (optional): vDistIdx's first member per left keypoint, i.e. the best SAD of
+// every match accepted at :676-686 whether or not :694-703 then resets it; -1 elsewhere.
+static void stereo_matches(const orb_stereo_input_t* in, float* uRight, float* depth,
+                           int32_t* sad = nullptr) {
   const orb_frame_t* F = in->left;
   const int N = F->n;
   for (int i = 0; i < N; ++i) { uRight[i] = -1.0f; depth[i] = -1.0f; }
+  if (sad) for (int i = 0; i < N; ++i) sad[i] = -1;
   const int thOrbDist = (100 + 50) / 2;
   const int nRows = in->level_height[0];
   std::vector<std::vector<size_t>> rowIdx(nRows);
@@ -1118,6 +1122,7 @@ static void stereo_matches(const orb_stereo_input_t* in, float* uRight, float* d
         depth[iL] = in->bf / disparity;
         uRight[iL] = bestuR;
         distIdx.push_back(std::make_pair(bestSad, iL));
+        if (sad) sad[iL] = bestSad;
       }
     }
   }
@@ -1958,6 +1963,11 @@ int oracle_search_for_triangulation(const orb_frame_t* K1, const uint8_t* has_mp
                                   only_stereo, check_ori, match12);
 }
 
+int oracle_stereo_match_sad(const orb_stereo_input_t* in, float* u_right, float* depth,
+                            int32_t* sad) {
+  stereo_matches(in, u_right, depth, sad);
+  return 0;
+}
 int oracle_stereo_match(const orb_stereo_input_t* in, float* u_right, float* depth) {
   stereo_matches(in, u_right, depth);
   return 0;

@@ -1983,7 +1983,9 @@ orb_status_t orb_stereo_match(orb_matcher_t* m, const orb_stereo_input_t* in, fl
     off[l] = total;
     total += 2 * (size_t)P.strideL[l] * P.h[l];
   }
-  if ((st = m->dPyr.ensure(total))) return st;
+  // (16 bytes more: the match kernel reads a right row in aligned 16-byte
+  // spans, which end up to 4 bytes past a row as wide as its pitch)
+  if ((st = m->dPyr.ensure(total + 16))) return st;
   StereoPairLevels lv;
   memset(&lv, 0, sizeof(lv));
   uint8_t* base = m->dPyr.as<uint8_t>();

@@ -1019,3 +1019,172 @@ def undistort_points(xy, K, dist):
         ww = 1.0 / (K[6] * x + K[7] * y + K[8])
         out[i] = (np.float32(xx * ww), np.float32(yy * ww))
     return out
+
+
+# ------------------------------------------- Frame::ComputeStereoMatches (a11)
+_POP8 = np.array([bin(i).count("1") for i in range(256)], np.int32)
+
+
+def _roundf(x, even=False):
+    """roundf on a float32: half away from zero (np.rint, half to even, is the
+    wrong neighbour `round_even`)."""
+    x = np.float32(x)
+    if even:
+        return np.float32(np.rint(x))
+    return np.float32(math.copysign(math.floor(abs(float(x)) + 0.5), float(x)))
+
+
+def stereo_match(lkeys, ldesc, scale, rkeys, rdesc, lpyr, rpyr, inv_scale, bf, fx, width, height,
+                 rules=(), trace=None):
+    """Frame::ComputeStereoMatches, src/Frame.cc:516-704, restated: (u_right,
+    depth, sad).  sad = the best SAD of every match accepted at :676-686,
+    whether or not the median prune of :690-703 then resets it, -1 elsewhere.
+    Float arithmetic is np.float32 wherever the reference computes in float.
+
+    rules: the wrong neighbours of the reference's rules (test_stereo_edge_cases
+    lists which input separates which).  trace: a dict that receives, per left
+    keypoint and for the prune, what the census functions count."""
+    F = np.float32
+    rules = set(rules)
+    N, NR = len(lkeys), len(rkeys)
+    ur, dp, sad = np.full(N, -1, F), np.full(N, -1, F), np.full(N, -1, np.int32)
+    scale, inv = np.asarray(scale, F), np.asarray(inv_scale, F)
+    ldesc = np.asarray(ldesc, np.uint8).reshape(N, 32)
+    rdesc = np.asarray(rdesc, np.uint8).reshape(NR, 32)
+    nrows = lpyr[0].shape[0]
+    even = "round_even" in rules
+    # :531-544, vRowIndices
+    rows = [[] for _ in range(nrows)]
+    bands = []
+    for iR in range(NR):
+        y = F(rkeys["y"][iR])
+        r = F(2.0) * scale[int(rkeys["octave"][iR])]
+        if "band_round" in rules:
+            lo, hi = int(_roundf(y - r)), int(_roundf(y + r))
+        else:
+            lo, hi = int(math.floor(y - r)), int(math.ceil(y + r))
+        bands.append((lo, hi))
+        for yi in range(lo, hi + 1):
+            rows[yi].append(iR)
+    mb = F(bf) / F(fx)
+    minD, maxD = F(0), F(bf) / mb
+    rx, roct = rkeys["x"].astype(F), rkeys["octave"].astype(np.int64)
+    accepted = []
+    kps = []
+    for iL in range(N):
+        t = dict(stage="none")
+        kps.append(t)
+        lvl = int(lkeys["octave"][iL])
+        uL, vL = F(lkeys["x"][iL]), F(lkeys["y"][iL])
+        row = int(_roundf(vL)) if "row_round" in rules else int(vL)   # float -> size_t
+        cand = np.asarray(rows[row] if row < nrows else [], np.int64)
+        t["row_len"] = len(cand)
+        if len(cand) == 0:
+            continue
+        minU, maxU = uL - maxD, uL - minD
+        if maxU < 0:
+            continue
+        dlim = 2 if "octave_pm2" in rules else 1
+        octd = roct[cand] - lvl
+        t["oct_delta"] = sorted(set(int(v) for v in octd))
+        uR = rx[cand]
+        lo_ok = (uR > minU) if "minu_strict" in rules else (uR >= minU)
+        hi_ok = (uR < maxU) if "maxu_strict" in rules else (uR <= maxU)
+        inoct = np.abs(octd) <= 1
+        t["ur_eq_minu"] = int((inoct & (uR == minU)).sum())
+        t["ur_eq_maxu"] = int((inoct & (uR == maxU)).sum())
+        t["ur_below_minu"] = int((inoct & (uR == np.nextafter(minU, F(-np.inf)))).sum())
+        t["ur_above_maxu"] = int((inoct & (uR == np.nextafter(maxU, F(np.inf)))).sum())
+        ok = (np.abs(octd) <= dlim) & lo_ok & hi_ok
+        c = cand[ok]
+        t["n_pass"] = len(c)
+        if len(c) == 0:
+            continue
+        d = _POP8[np.bitwise_xor(rdesc[c], ldesc[iL][None, :])].sum(axis=1)
+        best = int(d.min())
+        where = np.nonzero(d == best)[0]
+        k = int(where[-1] if "tie_last" in rules else where[0])   # strict <: the first minimum
+        t.update(best_dist=best, n_tied=len(where), best_pos=int(np.nonzero(ok)[0][k]),
+                 best_idx=int(c[k]), best_oct_delta=int(roct[c[k]] - lvl))
+        if not (best < 75 or ("hamming_le" in rules and best <= 75)) or best >= 100:
+            continue
+        t["stage"] = "descriptor"
+        uR0 = rx[c[k]]
+        sf = inv[lvl]
+        suL, svL, suR0 = _roundf(uL * sf, even), _roundf(vL * sf, even), _roundf(uR0 * sf, even)
+        half = lambda v: abs(float(v) - math.trunc(float(v))) == 0.5
+        t["halves"] = int(half(uL * sf)) + int(half(vL * sf)) + int(half(uR0 * sf))
+        IL, IR = lpyr[lvl], rpyr[lvl]
+        cols = IR.shape[1]
+        w, L = 5, 5
+        iniu, endu = suR0 + F(L) - F(w), suR0 + F(L) + F(w) + F(1)
+        t.update(level=lvl, endu=float(endu), cols=cols, sx=float(suR0))
+        if iniu < 0 or (endu > cols if "endu_gt" in rules else endu >= cols):
+            t["stage"] = "border"
+            continue
+        x0, y0, xr = int(suL) - w, int(svL) - w, int(suR0) - L - w
+        assert x0 >= 0 and y0 >= 0 and xr >= 0, "outside the defined domain"
+        assert y0 + 11 <= IL.shape[0] and x0 + 11 <= IL.shape[1] and xr + 21 <= cols
+        pl = IL[y0:y0 + 11, x0:x0 + 11].astype(np.int64)
+        pl = pl - pl[w, w]
+        strip = IR[y0:y0 + 11, xr:xr + 21].astype(np.int64)
+        dists = []
+        for s in range(2 * L + 1):
+            pr = strip[:, s:s + 11] - strip[w, s + w]
+            dists.append(int(np.abs(pl - pr).sum()))
+        t["sads"] = list(dists)
+        if "sad_s16" in rules:   # the odd shifts ride in the high half of a packed word
+            dists = [v - 65536 if (s & 1) and v >= 32768 else v for s, v in enumerate(dists)]
+        best_sad, inc = 2147483647, 0
+        for s, v in enumerate(dists):
+            if F(v) < F(best_sad) or ("sad_first_vs_last" in rules and F(v) <= F(best_sad)):
+                best_sad, inc = v, s - L
+        t.update(best_sad=best_sad, inc=inc, sad_ties=sum(v == best_sad for v in dists))
+        if inc in (-L, L):
+            if "edge_inc_kept" not in rules:
+                t["stage"] = "edge_inc"
+                continue
+            delta = F(0)
+        else:
+            d1, d2, d3 = F(dists[L + inc - 1]), F(dists[L + inc]), F(dists[L + inc + 1])
+            with np.errstate(all="ignore"):
+                delta = (d1 - d3) / (F(2.0) * (d1 + d3 - F(2.0) * d2))
+        t["delta"] = float(delta)
+        if delta < -1 or delta > 1:
+            t["stage"] = "delta"
+            continue
+        best_ur = scale[lvl] * ((suR0 + F(inc)) + delta)
+        disp = uL - best_ur
+        t["disparity"] = float(disp)
+        t["maxd"] = float(maxD)
+        if not (disp >= minD and (disp < maxD or ("maxd_le" in rules and disp <= maxD))):
+            t["stage"] = "disparity"
+            continue
+        if disp <= 0 and "no_zero_disp_branch" not in rules:
+            disp = F(0.01)
+            best_ur = F(np.float64(uL) - 0.01)
+            t["zero_branch"] = True
+        with np.errstate(all="ignore"):
+            dp[iL] = F(bf) / disp
+        ur[iL] = best_ur
+        sad[iL] = best_sad
+        accepted.append((best_sad, iL))
+        t["stage"] = "accepted"
+    prune = dict(V=len(accepted))
+    if accepted:   # the reference indexes an empty vector otherwise (undefined)
+        accepted.sort()
+        V = len(accepted)
+        median = F(accepted[(V - 1) // 2 if "median_lower" in rules else V // 2][0])
+        th = F(1.5) * F(1.4) * median
+        n_reset = 0
+        for s, iL in reversed(accepted):
+            if F(s) < th or ("prune_le" in rules and F(s) <= th):
+                break
+            ur[iL] = dp[iL] = F(-1)
+            kps[iL]["stage"] = "pruned"
+            n_reset += 1
+        prune.update(median=float(median), th=float(th), reset=n_reset,
+                     at_th=sum(float(s) == float(th) for s, _ in accepted))
+    if trace is not None:
+        trace.update(kp=kps, bands=bands, prune=prune, nrows=nrows)
+    return ur, dp, sad
