@@ -78,6 +78,14 @@
  *                                  src/Tracking.cc:904-954 and Relocalization :1592-1616 call it
  *   orb_track_discard_outliers_batch_n  the discard loop with the match count read through a
  *                                  strided pointer (src/Tracking.cc:928-951 after SearchByBoW)
+ *   orb_update_local_map_batch     Tracking::UpdateLocalMap src/Tracking.cc:1395-1404:
+ *                                  UpdateLocalKeyFrames :1437-1558 and UpdateLocalPoints
+ *                                  :1407-1434 over a device-resident map view, with the
+ *                                  already-matched marking of SearchLocalPoints :1333-1354
+ *   orb_track_local_merge_batch    F.mvpMapPoints[bestIdx] = pMP (src/ORBmatcher.cc:127) of the
+ *                                  local matcher, as global point indices
+ *   orb_track_local_map_finish_batch  mnMatchesInliers and the stereo outlier reset of
+ *                                  Tracking::TrackLocalMap src/Tracking.cc:1109-1135
  *   orb_vocabulary_create / _load_text / _destroy
  *                                  DBoW2 TemplatedVocabulary ctor + loadFromTextFile
  *                                  Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:1362-1448
@@ -1056,6 +1064,150 @@ orb_status_t orb_match_bow_batch(
     long long mp_stride, float nnratio, int check_orientation, int min_matches,
     int32_t* d_kp_match, orb_bow_match_info_t* d_info, void* stream);
 int orb_match_bow_batch_max_stride(void);
+
+/* ------------------------------------------------ UpdateLocalMap on the device */
+
+/* The map as Tracking::UpdateLocalMap reads it: a host struct of device
+ * pointers that the caller owns, keeps resident and keeps well-formed (the
+ * integrator updates it where LocalMapping inserts or culls keyframes and
+ * points).  Keyframes are numbered 0..n_kf-1 and map points
+ * 0..n_mp-1; a `*_offs` array has n + 1 ascending entries and list i is
+ * [offs[i], offs[i+1]).  Nothing of it is validated: an index outside its
+ * array, a decreasing offset or a kf_rank that is not a permutation is the
+ * caller's promise and is NOT checked, as the point indices of
+ * orb_match_projection_frame_batch are not.  Every pointer is required (an
+ * empty list array may be any valid device pointer). */
+typedef struct orb_map_view {
+  int32_t n_kf, n_mp;
+  const int32_t* kf_rank;      /* n_kf: position of keyframe k in the iteration order of
+                                  std::map<KeyFrame*,..> / std::set<KeyFrame*> (pointer order in
+                                  the drop-in); a permutation of 0..n_kf-1, NOT checked */
+  const int32_t* kf_by_rank;   /* its inverse */
+  const uint8_t* kf_bad;       /* KeyFrame::isBad() (src/KeyFrame.cc:572) */
+  const int32_t* kf_parent;    /* GetParent() (:431), -1 none */
+  const int32_t* kf_cov_offs;   const int32_t* kf_cov;   /* mvpOrderedConnectedKeyFrames, best first (:141-187) */
+  const int32_t* kf_child_offs; const int32_t* kf_child; /* mspChildrens, any order (:425) */
+  const int32_t* kf_mp_offs;    const int32_t* kf_mp;    /* GetMapPointMatches() by keypoint index, <0 = NULL (:283) */
+  const int32_t* mp_obs_offs;   const int32_t* mp_obs;   /* keyframes of GetObservations(), any order (src/MapPoint.cc:142) */
+  const orb_map_point_t* points;  /* n_mp; bad and has_obs are read and copied through */
+  const uint8_t* mp_desc;         /* n_mp x 32 */
+} orb_map_view_t;
+
+typedef struct orb_local_map_info {
+  int32_t n_local_kf;     /* mvpLocalKeyFrames.size() on return */
+  int32_t n_voted;        /* keyframeCounter.size(), bad keyframes included */
+  int32_t n_added;        /* keyframes the neighbour pass appended */
+  int32_t ref_kf;         /* pKFmax, -1 when none (mpReferenceKF is then left as it is) */
+  int32_t max_votes;      /* max */
+  int32_t n_local_points; /* mvpLocalMapPoints.size(): the full count, may exceed mp_stride */
+  int32_t n_nulled;       /* matched points found bad and set to NULL (:1457) */
+  int32_t kept;           /* 1: the counter was empty, the list was kept (:1462) */
+} orb_local_map_info_t;   /* 32 bytes */
+
+/* Tracking::UpdateLocalMap (src/Tracking.cc:1395-1404) for n_problems
+ * independent frames against one map view, every per-problem array a device
+ * pointer, asynchronous on `stream`, no host synchronisation, upload or
+ * download.  `view` is a host pointer, read during the call.
+ * In: problem p reads d_nkeys[p] (clamped to [0, kp_stride]) and its matches
+ * d_kp_match + p * kp_stride (in/out): global point indices as the tracking
+ * batches write them with mp_stride 0; any negative value is NULL and is left
+ * as it is.  It also reads the list it left for the previous frame,
+ * d_local_kf + p * kf_stride with the count d_n_local_kf[p] (both in/out, the
+ * count clamped to [0, kf_stride] on entry): when no keyframe gets a vote the
+ * reference returns before it clears mvpLocalKeyFrames (:1462), so the list
+ * stays exactly as on entry and the points are gathered from it (info.kept =
+ * 1; its keyframes are not re-checked for isBad(), as there).  kf_stride >=
+ * view->n_kf.
+ * Semantics, the reference restated:
+ *   vote (:1441-1460): per keypoint, a matched point that is bad becomes -1 in
+ *     d_kp_match (n_nulled); every other matched point gives one vote to each
+ *     keyframe of its observation list.
+ *   voted keyframes in kf_rank order (:1472-1489): bad ones are skipped, the
+ *     first whose count is strictly greater than the running maximum is pKFmax
+ *     (ref_kf, max_votes), every one that is not bad is appended.  All bad:
+ *     the list is empty, ref_kf = -1, there are no local points.
+ *   neighbour pass (:1494-1550) over the voted, appended keyframes only: stop
+ *     when the list holds more than 80; of the first min(10, size) covisibles
+ *     append the first that is not bad and not yet included; append the child
+ *     of smallest kf_rank that is not bad and not yet included; a parent that
+ *     is not yet included is appended whatever its isBad() and ends the whole
+ *     pass (the break at :1546 leaves the outer loop).
+ *   UpdateLocalPoints (:1407-1434): the final list in order, each keyframe's
+ *     kf_mp in keypoint order; negatives, points already taken for this
+ *     problem and bad points are skipped, the rest appended.
+ *   SearchLocalPoints' first loop (:1333-1354): a local point that a keypoint
+ *     of this frame holds (after the nulling) gets seen = 1 in its gathered
+ *     record, every other local point seen = 0, whatever the map's own byte.
+ *   IncreaseVisible and the other MapPoint side effects stay with the caller.
+ * Out, per problem: the keyframe list and its count; d_local_index +
+ * p * mp_stride, the global index of each local point in order; d_mps +
+ * p * mp_stride, the gathered records; d_mp_desc + 32 * p * mp_stride, their
+ * descriptors; d_nmps[p] = min(n_local_points, mp_stride), only that many
+ * entries are written; d_locked + p * kp_stride (d_nkeys[p] entries) =
+ * kp_match >= 0 && has_obs; d_info[p].  d_mps, d_mp_desc and d_nmps are
+ * orb_frustum_batch's inputs and d_locked is
+ * orb_match_projection_local_batch[_stereo]'s, unchanged.
+ * Capacity: one workgroup per problem keeps 12 bytes and one bit per keyframe
+ * slot in LDS, over K = (kf_stride + 32) & ~31 slots, beside a 12,288-entry
+ * hash table (8 bytes each), 2,320 words of staged neighbourhoods and 512
+ * static bytes: 98,304 + 9,280 + 12 K + K / 8 + 512 <= 163,840.
+ * orb_update_local_map_max_keyframes() is the largest kf_stride that fits (a
+ * pure function, callable without a device); view->n_kf or kf_stride above it:
+ * ORB_ECAPACITY before anything is launched, nothing is written.
+ * The slots of one problem's local keyframes total fewer than 2^30.
+ * Tiers: the union's first-occurrence table is that LDS hash table while the
+ * local keyframes' slots name at most 9,216 distinct points; a problem that
+ * names more runs the union on a table indexed by point id in the handle's
+ * device scratch (4 * n_mp bytes per problem, allocated only when n_mp >
+ * 9,216).  Because of that scratch the call follows the handle's call-order
+ * rule: on a stream other than the previous call's it first makes its stream
+ * wait for that call (on the device).
+ * ORB_EINVAL: a null required pointer, a negative count, kp_stride <= 0,
+ * mp_stride <= 0, kf_stride < view->n_kf.  n_problems == 0: ORB_OK, no launch.
+ * The caller's promises, NOT checked: view->mp_desc and d_mp_desc are 16-byte
+ * aligned (the gather moves descriptors as two 16-byte words; the records are
+ * moved as 4-byte words); the entries of a list that is kept (the first
+ * d_n_local_kf[p] of d_local_kf + p * kf_stride on entry) are keyframe numbers
+ * in [0, view->n_kf); every non-negative d_kp_match entry is below view->n_mp. */
+orb_status_t orb_update_local_map_batch(
+    orb_matcher_t* m, int n_problems, const orb_map_view_t* view, const int32_t* d_nkeys,
+    int32_t* d_kp_match, int kp_stride, int32_t* d_local_kf, int32_t* d_n_local_kf,
+    int kf_stride, int32_t* d_local_index, orb_map_point_t* d_mps, uint8_t* d_mp_desc,
+    int32_t* d_nmps, int mp_stride, uint8_t* d_locked, orb_local_map_info_t* d_info,
+    void* stream);
+int orb_update_local_map_max_keyframes(void);
+
+/* After orb_match_projection_local_batch[_stereo] on the local map above: per
+ * problem and keypoint i < d_nkeys[p], d_kp_match[i] = d_local_index[d_km_local[i]]
+ * where d_km_local[i] >= 0 (both match arrays at p * kp_stride, d_local_index at
+ * p * mp_stride); other entries are unchanged.  The local matcher's last writer
+ * has already won inside d_km_local (F.mvpMapPoints[bestIdx] = pMP).  The
+ * result is orb_pose_optimization_batch's d_point_index over the view's shared
+ * `points` (pt_stride 0).  Every non-negative d_km_local entry is below d_nmps[p]
+ * (and so below mp_stride), as the local matcher writes it: the caller's
+ * promise, NOT checked.  ORB_EINVAL: a null pointer, a negative count,
+ * kp_stride <= 0, mp_stride <= 0.  Asynchronous on `stream`. */
+orb_status_t orb_track_local_merge_batch(orb_matcher_t* m, int n_problems,
+                                         const int32_t* d_nkeys, int kp_stride,
+                                         const int32_t* d_km_local,
+                                         const int32_t* d_local_index, int mp_stride,
+                                         int32_t* d_kp_match, void* stream);
+
+/* Tracking::TrackLocalMap after PoseOptimization (src/Tracking.cc:1109-1135):
+ * d_n_inliers[p] (mnMatchesInliers) counts the keypoints that hold a point
+ * (d_kp_match >= 0, an index into d_points + p * pt_stride; pt_stride 0: one
+ * shared array), are not flagged in d_outlier and for which only_tracking ||
+ * has_obs holds.  null_outliers != 0 (mSensor == System::STEREO only) sets an
+ * outlier's d_kp_match to -1.  IncreaseFound and the < 30 / < 50 decision stay
+ * with the caller.  ORB_EINVAL: a null pointer, a negative count or stride,
+ * kp_stride <= 0.  Asynchronous on `stream`. */
+orb_status_t orb_track_local_map_finish_batch(orb_matcher_t* m, int n_problems,
+                                              const int32_t* d_nkeys, int kp_stride,
+                                              int32_t* d_kp_match, const uint8_t* d_outlier,
+                                              const orb_map_point_t* d_points,
+                                              long long pt_stride, int only_tracking,
+                                              int null_outliers, int32_t* d_n_inliers,
+                                              void* stream);
 
 /* ------------------------------------------------------ DBoW2 vocabulary */
 

@@ -56,6 +56,10 @@ TRACK_DISCARD_INFO_DTYPE = np.dtype([("n_matches", "<i4"), ("n_matches_map", "<i
                                      ("n_discarded", "<i4")])
 BOW_MATCH_INFO_DTYPE = np.dtype([("n_matches", "<i4"), ("n_accepted", "<i4"),
                                  ("n_common_nodes", "<i4"), ("n_tried", "<i4"), ("enough", "<i4")])
+LOCAL_MAP_INFO_DTYPE = np.dtype([("n_local_kf", "<i4"), ("n_voted", "<i4"), ("n_added", "<i4"),
+                                 ("ref_kf", "<i4"), ("max_votes", "<i4"),
+                                 ("n_local_points", "<i4"), ("n_nulled", "<i4"), ("kept", "<i4")])
+assert LOCAL_MAP_INFO_DTYPE.itemsize == 32
 ORB_DEPTH_U16, ORB_DEPTH_F32 = 0, 1
 
 
@@ -81,6 +85,14 @@ class _Frame(ctypes.Structure):
         ("min_y", ctypes.c_float), ("max_y", ctypes.c_float), ("n_levels", ctypes.c_int32),
         ("scale_factors", ctypes.c_void_p),
     ]
+
+
+class _MapView(ctypes.Structure):
+    _fields_ = [("n_kf", ctypes.c_int32), ("n_mp", ctypes.c_int32)] + [
+        (name, ctypes.c_void_p) for name in (
+            "kf_rank", "kf_by_rank", "kf_bad", "kf_parent", "kf_cov_offs", "kf_cov",
+            "kf_child_offs", "kf_child", "kf_mp_offs", "kf_mp", "mp_obs_offs", "mp_obs",
+            "points", "mp_desc")]
 
 
 def lib() -> ctypes.CDLL:
@@ -220,6 +232,12 @@ def lib() -> ctypes.CDLL:
         "orb_match_bow_batch": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
                                       vp, vp, vp, vp, i32, vp, i64, f32, i32, i32, vp, vp, vp]),
         "orb_match_bow_batch_max_stride": (i32, []),
+        "orb_update_local_map_batch": (i32, [vp, i32, vp, vp, vp, i32, vp, vp, i32, vp, vp, vp,
+                                             vp, i32, vp, vp, vp]),
+        "orb_update_local_map_max_keyframes": (i32, []),
+        "orb_track_local_merge_batch": (i32, [vp, i32, vp, i32, vp, vp, i32, vp, vp]),
+        "orb_track_local_map_finish_batch": (i32, [vp, i32, vp, i32, vp, vp, vp, i64, i32, i32,
+                                                   vp, vp]),
         "orb_synth_image": (None, [ctypes.c_uint64, i32, i32, i32, i32, vp, sz]),
         "orb_synth_local_map": (None, [ctypes.c_uint64, vp, vp, i32, i32, i32, i32, vp, vp, vp]),
     }
@@ -227,7 +245,9 @@ def lib() -> ctypes.CDLL:
     # measurement) does not have; calling one there is an AttributeError
     newer = ("orb_match_projection_frame_batch", "orb_match_projection_frame_batch_max_stride",
              "orb_track_discard_outliers_batch", "orb_track_discard_outliers_batch_n",
-             "orb_match_bow_batch", "orb_match_bow_batch_max_stride")
+             "orb_match_bow_batch", "orb_match_bow_batch_max_stride",
+             "orb_update_local_map_batch", "orb_update_local_map_max_keyframes",
+             "orb_track_local_merge_batch", "orb_track_local_map_finish_batch")
     for name, (res, args) in sig.items():
         if name in newer and "ORB_AMD_LIB" in os.environ and not hasattr(L, name):
             continue
@@ -266,6 +286,58 @@ def match_bow_batch_max_stride() -> int:
     """orb_match_bow_batch_max_stride(): a pure function of k_bow_batch's LDS
     layout, callable without a device."""
     return lib().orb_match_bow_batch_max_stride()
+
+
+def update_local_map_max_keyframes() -> int:
+    """orb_update_local_map_max_keyframes(): the largest keyframe count (and
+    kf_stride) update_local_map_batch accepts; a pure function of k_local_map's
+    LDS layout, callable without a device."""
+    return lib().orb_update_local_map_max_keyframes()
+
+
+class MapView:
+    """orb_map_view_t from numpy arrays: the map as Tracking::UpdateLocalMap
+    reads it, copied to the device once and kept there.
+
+    kf_rank (n_kf): position of each keyframe in std::map / std::set<KeyFrame*>
+    order; kf_bad, kf_parent (-1 none); cov / child / kf_mp: per keyframe a CSR
+    pair (offs of n_kf + 1 entries, values); mp_obs likewise per map point;
+    points (MAP_POINT_DTYPE, n_mp) and mp_desc (n_mp x 32).  to_device(a) copies
+    one contiguous array to the device and returns an object with data_ptr()
+    (default: a torch CUDA tensor).  Nothing is validated, as in the C entry."""
+
+    def __init__(self, kf_rank, kf_bad, kf_parent, kf_cov_offs, kf_cov, kf_child_offs, kf_child,
+                 kf_mp_offs, kf_mp, mp_obs_offs, mp_obs, points, mp_desc, to_device=None):
+        if to_device is None:
+            import torch
+
+            def to_device(a):
+                return torch.from_numpy(a.view(np.uint8).reshape(-1).copy()).cuda()
+        i32 = lambda a: np.ascontiguousarray(a, np.int32).reshape(-1)
+        rank = i32(kf_rank)
+        self.n_kf = len(rank)
+        by_rank = np.zeros(self.n_kf, np.int32)
+        by_rank[rank] = np.arange(self.n_kf, dtype=np.int32)
+        pts = np.ascontiguousarray(points, MAP_POINT_DTYPE).reshape(-1)
+        self.n_mp = len(pts)
+        host = dict(kf_rank=rank, kf_by_rank=by_rank,
+                    kf_bad=np.ascontiguousarray(kf_bad, np.uint8).reshape(-1),
+                    kf_parent=i32(kf_parent), kf_cov_offs=i32(kf_cov_offs), kf_cov=i32(kf_cov),
+                    kf_child_offs=i32(kf_child_offs), kf_child=i32(kf_child),
+                    kf_mp_offs=i32(kf_mp_offs), kf_mp=i32(kf_mp), mp_obs_offs=i32(mp_obs_offs),
+                    mp_obs=i32(mp_obs), points=pts,
+                    mp_desc=np.ascontiguousarray(mp_desc, np.uint8).reshape(-1))
+        self.host = host
+        self.dev = {}
+        self.c = _MapView(n_kf=self.n_kf, n_mp=self.n_mp)
+        for name, a in host.items():
+            # an empty list array still needs a valid device address
+            t = to_device(a if a.size else np.zeros(16, np.uint8))
+            self.dev[name] = t
+            setattr(self.c, name, t.data_ptr())
+
+    def addr(self) -> int:
+        return ctypes.addressof(self.c)
 
 
 def device_count() -> int:
@@ -1233,6 +1305,47 @@ class ORBmatcher:
     def search_by_bow_batch_max_stride() -> int:
         """Largest kp_stride search_by_bow_batch accepts."""
         return lib().orb_match_bow_batch_max_stride()
+
+    # ------------------------------------------------ TrackLocalMap, device batch
+    def update_local_map_batch(self, n_problems, view, d_nkeys, d_kp_match, kp_stride,
+                               d_local_kf, d_n_local_kf, kf_stride, d_local_index, d_mps,
+                               d_mp_desc, d_nmps, mp_stride, d_locked, d_info, stream: int = 0):
+        """Tracking::UpdateLocalMap (UpdateLocalKeyFrames, UpdateLocalPoints and
+        SearchLocalPoints' already-matched marking) for n_problems frames against
+        `view` (a MapView) (orb_update_local_map_batch).  d_* are device
+        addresses; d_kp_match, d_local_kf and d_n_local_kf are in/out; d_info
+        holds n_problems LOCAL_MAP_INFO_DTYPE records.  Asynchronous on `stream`."""
+        _check(lib().orb_update_local_map_batch(
+            self._h, n_problems, view.addr() if view is not None else None, d_nkeys or None,
+            d_kp_match or None, kp_stride, d_local_kf or None, d_n_local_kf or None, kf_stride,
+            d_local_index or None, d_mps or None, d_mp_desc or None, d_nmps or None, mp_stride,
+            d_locked or None, d_info or None, stream or None), "update_local_map_batch")
+
+    @staticmethod
+    def update_local_map_max_keyframes() -> int:
+        """Largest keyframe count and kf_stride update_local_map_batch accepts."""
+        return lib().orb_update_local_map_max_keyframes()
+
+    def track_local_merge_batch(self, n_problems, d_nkeys, kp_stride, d_km_local, d_local_index,
+                                mp_stride, d_kp_match, stream: int = 0):
+        """d_kp_match[i] = d_local_index[d_km_local[i]] where the local matcher
+        matched keypoint i (orb_track_local_merge_batch)."""
+        _check(lib().orb_track_local_merge_batch(
+            self._h, n_problems, d_nkeys or None, kp_stride, d_km_local or None,
+            d_local_index or None, mp_stride, d_kp_match or None, stream or None),
+            "track_local_merge_batch")
+
+    def track_local_map_finish_batch(self, n_problems, d_nkeys, kp_stride, d_kp_match, d_outlier,
+                                     d_points, pt_stride, only_tracking, null_outliers,
+                                     d_n_inliers, stream: int = 0):
+        """mnMatchesInliers per problem and, with null_outliers (stereo), the
+        outliers' matches reset (orb_track_local_map_finish_batch;
+        src/Tracking.cc:1109-1135)."""
+        _check(lib().orb_track_local_map_finish_batch(
+            self._h, n_problems, d_nkeys or None, kp_stride, d_kp_match or None,
+            d_outlier or None, d_points or None, pt_stride, int(bool(only_tracking)),
+            int(bool(null_outliers)), d_n_inliers or None, stream or None),
+            "track_local_map_finish_batch")
 
     # ------------------------------------------ MapPoint::ComputeDistinctiveDescriptors
     def ComputeDistinctiveDescriptors(self, obs_offs, obs_desc, descriptors=None):

@@ -234,3 +234,24 @@ struct BowBatchParams {
   float nnratio;
   int checkOri, minMatches;
 };
+
+// ----------------------------------------------------- localmap_kernels.hip
+// Tracking::UpdateLocalMap over nProblems frames against one map view (by
+// value): the view's device pointers, the per-problem arrays and strides
+struct LocalMapParams {
+  int nProblems;
+  int nKf, nMp;
+  int kpStride, kfStride, mpStride;
+  orb_map_view_t view;
+  const int32_t* nkeys;
+  int32_t* kpMatch;       // in/out
+  int32_t* localKf;       // in/out
+  int32_t* nLocalKf;      // in/out
+  int32_t* localIndex;
+  orb_map_point_t* mps;
+  uint8_t* mpDesc;
+  int32_t* nmps;
+  uint8_t* locked;
+  orb_local_map_info_t* info;
+  int32_t* table;         // the scratch tier's per-problem table, nMp entries each
+};

@@ -228,4 +228,18 @@ hipError_t orb_k_track_discard(int nProblems, int stride, long long mpStride, in
 int orb_k_bow_batch_max_stride(void);
 hipError_t orb_k_bow_batch(const BowBatchParams* params, int32_t* kpMatch,
                            orb_bow_match_info_t* info, hipStream_t s);
+hipError_t orb_k_track_local_merge(int nProblems, int stride, int mpStride, const int32_t* nkeys,
+                                   const int32_t* kmLocal, const int32_t* localIndex,
+                                   int32_t* kpMatch, hipStream_t s);
+hipError_t orb_k_track_local_finish(int nProblems, int stride, long long ptStride,
+                                    int onlyTracking, int nullOutliers, const int32_t* nkeys,
+                                    int32_t* kpMatch, const uint8_t* outlier,
+                                    const orb_map_point_t* points, int32_t* nInliers,
+                                    hipStream_t s);
+// ----------------------------------------------------- localmap_kernels.hip
+// largest keyframe-slot count (kf_stride >= n_kf) whose per-problem state fits one CU's LDS
+int orb_k_local_map_max_keyframes(void);
+// distinct point ids the LDS table takes before a problem runs on the scratch table
+int orb_k_local_map_hash_cap(void);
+hipError_t orb_k_local_map(const LocalMapParams* params, hipStream_t s);
 }

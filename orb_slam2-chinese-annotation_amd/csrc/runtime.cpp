@@ -1374,6 +1374,7 @@ struct orb_matcher {
   DevBuf dCpKeys;  // k_close_points' key scratch for frames above CP_LDS_KEYS slots
   DevBuf dPoKeys, dPoUr, dPoIdx, dPoPts, dPoOut;  // orb_pose_optimization's staged frame
   DevBuf dPoRecs;  // k_pose_optimization's edge records for frames above PO_LDS_EDGES slots
+  DevBuf dLmTable;  // k_local_map's first-occurrence table by point id (the scratch tier)
   DevBuf dOvf, dOvfCtr;  // candidate lists of SearchByProjection(F, localMap) (ProjParams.ovf)
   uint32_t ovfGen = 0;
   int stagedN = -1, stagedM = -1;  // orb_match_projection_local_stage's layout
@@ -4151,6 +4152,102 @@ orb_status_t orb_match_bow_batch(
   P.checkOri = check_orientation ? 1 : 0;
   P.minMatches = min_matches;
   HIP_TRY(orb_k_bow_batch(&P, d_kp_match, d_info, s));
+  return ORB_OK;
+}
+
+// ------------------------------------------- UpdateLocalMap as a device batch
+// (src/Tracking.cc:1395-1558, :1333-1354; localmap_kernels.hip).  CallOrder:
+// a problem whose slots name more distinct points than the LDS table takes
+// runs on dLmTable.
+int orb_update_local_map_max_keyframes(void) { return orb_k_local_map_max_keyframes(); }
+
+orb_status_t orb_update_local_map_batch(
+    orb_matcher_t* m, int n_problems, const orb_map_view_t* view, const int32_t* d_nkeys,
+    int32_t* d_kp_match, int kp_stride, int32_t* d_local_kf, int32_t* d_n_local_kf,
+    int kf_stride, int32_t* d_local_index, orb_map_point_t* d_mps, uint8_t* d_mp_desc,
+    int32_t* d_nmps, int mp_stride, uint8_t* d_locked, orb_local_map_info_t* d_info,
+    void* stream) {
+  if (!m || !view || n_problems < 0 || kp_stride <= 0 || mp_stride <= 0 || view->n_kf < 0 ||
+      view->n_mp < 0 || kf_stride < view->n_kf)
+    return ORB_EINVAL;
+  if (view->n_kf > orb_k_local_map_max_keyframes() ||
+      kf_stride > orb_k_local_map_max_keyframes())
+    return ORB_ECAPACITY;  // nothing is launched
+  if (n_problems == 0) return ORB_OK;
+  if (!view->kf_rank || !view->kf_by_rank || !view->kf_bad || !view->kf_parent ||
+      !view->kf_cov_offs || !view->kf_cov || !view->kf_child_offs || !view->kf_child ||
+      !view->kf_mp_offs || !view->kf_mp || !view->mp_obs_offs || !view->mp_obs ||
+      !view->points || !view->mp_desc || !d_nkeys || !d_kp_match || !d_local_kf ||
+      !d_n_local_kf || !d_local_index || !d_mps || !d_mp_desc || !d_nmps || !d_locked ||
+      !d_info)
+    return ORB_EINVAL;
+  std::lock_guard<std::mutex> g(m->mu);
+  hipSetDevice(m->device);
+  hipStream_t s = stream ? (hipStream_t)stream : m->stream;
+  CallOrder order(m->evLast, &m->lastStream, s);
+  if (order.status) return order.status;
+  orb_status_t st;
+  const bool scratch = view->n_mp > orb_k_local_map_hash_cap();
+  if (scratch && (st = m->dLmTable.ensure((size_t)n_problems * (size_t)view->n_mp * 4)))
+    return st;
+  LocalMapParams P;
+  memset(&P, 0, sizeof(P));
+  P.nProblems = n_problems;
+  P.nKf = view->n_kf;
+  P.nMp = view->n_mp;
+  P.kpStride = kp_stride;
+  P.kfStride = kf_stride;
+  P.mpStride = mp_stride;
+  P.view = *view;
+  P.nkeys = d_nkeys;
+  P.kpMatch = d_kp_match;
+  P.localKf = d_local_kf;
+  P.nLocalKf = d_n_local_kf;
+  P.localIndex = d_local_index;
+  P.mps = d_mps;
+  P.mpDesc = d_mp_desc;
+  P.nmps = d_nmps;
+  P.locked = d_locked;
+  P.info = d_info;
+  P.table = scratch ? m->dLmTable.as<int32_t>() : nullptr;
+  HIP_TRY(orb_k_local_map(&P, s));
+  return ORB_OK;
+}
+
+orb_status_t orb_track_local_merge_batch(orb_matcher_t* m, int n_problems,
+                                         const int32_t* d_nkeys, int kp_stride,
+                                         const int32_t* d_km_local,
+                                         const int32_t* d_local_index, int mp_stride,
+                                         int32_t* d_kp_match, void* stream) {
+  if (!m || n_problems < 0 || kp_stride <= 0 || mp_stride <= 0) return ORB_EINVAL;
+  if (n_problems == 0) return ORB_OK;
+  if (!d_nkeys || !d_km_local || !d_local_index || !d_kp_match)
+    return ORB_EINVAL;
+  std::lock_guard<std::mutex> g(m->mu);
+  hipSetDevice(m->device);
+  hipStream_t s = stream ? (hipStream_t)stream : m->stream;
+  HIP_TRY(orb_k_track_local_merge(n_problems, kp_stride, mp_stride, d_nkeys, d_km_local,
+                                  d_local_index, d_kp_match, s));
+  return ORB_OK;
+}
+
+orb_status_t orb_track_local_map_finish_batch(orb_matcher_t* m, int n_problems,
+                                              const int32_t* d_nkeys, int kp_stride,
+                                              int32_t* d_kp_match, const uint8_t* d_outlier,
+                                              const orb_map_point_t* d_points,
+                                              long long pt_stride, int only_tracking,
+                                              int null_outliers, int32_t* d_n_inliers,
+                                              void* stream) {
+  if (!m || n_problems < 0 || kp_stride <= 0 || pt_stride < 0) return ORB_EINVAL;
+  if (n_problems == 0) return ORB_OK;
+  if (!d_nkeys || !d_kp_match || !d_outlier || !d_points || !d_n_inliers)
+    return ORB_EINVAL;
+  std::lock_guard<std::mutex> g(m->mu);
+  hipSetDevice(m->device);
+  hipStream_t s = stream ? (hipStream_t)stream : m->stream;
+  HIP_TRY(orb_k_track_local_finish(n_problems, kp_stride, pt_stride, only_tracking ? 1 : 0,
+                                   null_outliers ? 1 : 0, d_nkeys, d_kp_match, d_outlier,
+                                   d_points, d_n_inliers, s));
   return ORB_OK;
 }
 

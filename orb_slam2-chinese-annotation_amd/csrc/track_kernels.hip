@@ -740,3 +740,74 @@ extern "C" hipError_t orb_k_bow_batch(const BowBatchParams* params, int32_t* kpM
   hipLaunchKernelGGL(k_bow_batch, dim3(P.nProblems), dim3(BB_T), lds, s, P, kpMatch, info);
   return hipGetLastError();
 }
+
+// ------------------------------------------ TrackLocalMap's two small tails
+// After SearchByProjection(F, localMap): the local matcher's matches (indices
+// into the problem's local map) become global point indices in the frame's
+// match array, F.mvpMapPoints[bestIdx] = pMP (src/ORBmatcher.cc:127).  A
+// keypoint is one entry of both arrays, so no two writes meet.
+__global__ __launch_bounds__(256) void k_track_local_merge(
+    int stride, int mpStride, const int32_t* __restrict__ nkeys,
+    const int32_t* __restrict__ kmLocal, const int32_t* __restrict__ localIndex,
+    int32_t* __restrict__ kpMatch) {
+  const int p = blockIdx.x;
+  const int n = min(max(nkeys[p], 0), stride);
+  const int32_t* KL = kmLocal + (size_t)p * stride;
+  const int32_t* LI = localIndex + (size_t)p * (size_t)mpStride;
+  int32_t* KM = kpMatch + (size_t)p * stride;
+  for (int i = threadIdx.x; i < n; i += 256) {
+    const int l = KL[i];
+    if (l >= 0) KM[i] = LI[l];
+  }
+}
+
+extern "C" hipError_t orb_k_track_local_merge(int nProblems, int stride, int mpStride,
+                                              const int32_t* nkeys, const int32_t* kmLocal,
+                                              const int32_t* localIndex, int32_t* kpMatch,
+                                              hipStream_t s) {
+  hipLaunchKernelGGL(k_track_local_merge, dim3(nProblems), dim3(256), 0, s, stride, mpStride,
+                     nkeys, kmLocal, localIndex, kpMatch);
+  return hipGetLastError();
+}
+
+// src/Tracking.cc:1109-1135 after PoseOptimization: mnMatchesInliers, and
+// (nullOutliers: mSensor == System::STEREO) the outliers' points set to NULL.
+__global__ __launch_bounds__(256) void k_track_local_finish(
+    int stride, long long ptStride, int onlyTracking, int nullOutliers,
+    const int32_t* __restrict__ nkeys, int32_t* __restrict__ kpMatch,
+    const uint8_t* __restrict__ outlier, const orb_map_point_t* __restrict__ points,
+    int32_t* __restrict__ nInliers) {
+  __shared__ int cnt;
+  const int p = blockIdx.x, tid = threadIdx.x;
+  const int n = min(max(nkeys[p], 0), stride);
+  int32_t* KM = kpMatch + (size_t)p * stride;
+  const uint8_t* OL = outlier + (size_t)p * stride;
+  const orb_map_point_t* PTS = points + (size_t)p * (size_t)ptStride;
+  if (tid == 0) cnt = 0;
+  __syncthreads();
+  int inl = 0;
+  for (int i = tid; i < n; i += 256) {
+    const int pi = KM[i];
+    if (pi < 0) continue;
+    if (!OL[i]) {
+      if (onlyTracking || PTS[pi].has_obs) ++inl;  // :1120-1129
+    } else if (nullOutliers) {
+      KM[i] = -1;  // :1131-1132
+    }
+  }
+  inl = wave_sum(inl);
+  if ((tid & 63) == 0 && inl) atomicAdd(&cnt, inl);
+  __syncthreads();
+  if (tid == 0) nInliers[p] = cnt;
+}
+
+extern "C" hipError_t orb_k_track_local_finish(int nProblems, int stride, long long ptStride,
+                                               int onlyTracking, int nullOutliers,
+                                               const int32_t* nkeys, int32_t* kpMatch,
+                                               const uint8_t* outlier,
+                                               const orb_map_point_t* points, int32_t* nInliers,
+                                               hipStream_t s) {
+  hipLaunchKernelGGL(k_track_local_finish, dim3(nProblems), dim3(256), 0, s, stride, ptStride,
+                     onlyTracking, nullOutliers, nkeys, kpMatch, outlier, points, nInliers);
+  return hipGetLastError();
+}

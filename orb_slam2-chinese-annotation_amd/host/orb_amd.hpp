@@ -874,6 +874,46 @@ class ORBmatcher {
   }
   static int search_by_bow_batch_max_stride() { return orb_match_bow_batch_max_stride(); }
 
+  // Tracking::UpdateLocalMap (src/Tracking.cc:1395-1404: UpdateLocalKeyFrames
+  // :1437-1558, UpdateLocalPoints :1407-1434, SearchLocalPoints' first loop
+  // :1333-1354) for n_problems frames against one device-resident map view
+  // (orb_update_local_map_batch).  d_kp_match, d_local_kf and d_n_local_kf are
+  // in/out; the gathered d_mps / d_mp_desc / d_nmps feed orb_frustum_batch and
+  // d_locked the local matcher.
+  void update_local_map_batch(int n_problems, const orb_map_view_t& view, const int32_t* d_nkeys,
+                              int32_t* d_kp_match, int kp_stride, int32_t* d_local_kf,
+                              int32_t* d_n_local_kf, int kf_stride, int32_t* d_local_index,
+                              orb_map_point_t* d_mps, uint8_t* d_mp_desc, int32_t* d_nmps,
+                              int mp_stride, uint8_t* d_locked, orb_local_map_info_t* d_info,
+                              void* stream = nullptr) {
+    check(orb_update_local_map_batch(h_, n_problems, &view, d_nkeys, d_kp_match, kp_stride,
+                                     d_local_kf, d_n_local_kf, kf_stride, d_local_index, d_mps,
+                                     d_mp_desc, d_nmps, mp_stride, d_locked, d_info, stream),
+          "update_local_map_batch");
+  }
+  static int update_local_map_max_keyframes() { return orb_update_local_map_max_keyframes(); }
+  // The local matcher's matches as global point indices in the frame's match
+  // array (orb_track_local_merge_batch).
+  void track_local_merge_batch(int n_problems, const int32_t* d_nkeys, int kp_stride,
+                               const int32_t* d_km_local, const int32_t* d_local_index,
+                               int mp_stride, int32_t* d_kp_match, void* stream = nullptr) {
+    check(orb_track_local_merge_batch(h_, n_problems, d_nkeys, kp_stride, d_km_local,
+                                      d_local_index, mp_stride, d_kp_match, stream),
+          "track_local_merge_batch");
+  }
+  // mnMatchesInliers and, with null_outliers (stereo), the outliers' matches
+  // reset (orb_track_local_map_finish_batch; src/Tracking.cc:1109-1135).
+  void track_local_map_finish_batch(int n_problems, const int32_t* d_nkeys, int kp_stride,
+                                    int32_t* d_kp_match, const uint8_t* d_outlier,
+                                    const orb_map_point_t* d_points, long long pt_stride,
+                                    bool only_tracking, bool null_outliers, int32_t* d_n_inliers,
+                                    void* stream = nullptr) {
+    check(orb_track_local_map_finish_batch(h_, n_problems, d_nkeys, kp_stride, d_kp_match,
+                                           d_outlier, d_points, pt_stride, only_tracking ? 1 : 0,
+                                           null_outliers ? 1 : 0, d_n_inliers, stream),
+          "track_local_map_finish_batch");
+  }
+
   float mfNNratio;
   bool mbCheckOrientation;
   orb_matcher_t* handle() { return h_; }
