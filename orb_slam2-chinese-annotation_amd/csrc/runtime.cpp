@@ -4,327 +4,11 @@
 // gfx950 kernels of extractor_kernels.hip / matcher_kernels.hip.  There is no
 // CPU compute path: every ORB result comes from the HIP kernels, and every
 // entry point fails with ORB_ENODEV / ORB_EDEVICE if the GPU path cannot run.
-#include <hip/hip_runtime.h>
-#include <math.h>
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include <algorithm>
-#include <array>
-#include <chrono>
-#include <mutex>
-#include <shared_mutex>
-#include <cmath>
-#include <unordered_map>
-#include <vector>
-
-#include "../../include/orb_abi.h"
-#include "orb_kernels.h"
+// (The vocabulary and the keyframe database: runtime_vocab.cpp.)
+#include "runtime_common.h"
 #include "orb_synth.h"
 
-namespace {
-
-#define HIP_TRY(expr)                                   \
-  do {                                                  \
-    hipError_t _e = (expr);                             \
-    if (_e != hipSuccess) {                             \
-      if (getenv("ORB_AMD_DEBUG"))                      \
-        fprintf(stderr, "[orb_amd] %s:%d %s -> %s\n", __FILE__, __LINE__, #expr, \
-                hipGetErrorString(_e));                 \
-      return _e == hipErrorOutOfMemory ? ORB_ENOMEM : ORB_EDEVICE; \
-    }                                                   \
-  } while (0)
-
-static inline int cvRoundF(float v) { return (int)lrintf(v); }
-static inline short satShort(int v) { return (short)std::min(std::max(v, -32768), 32767); }
-
-static bool stream_capturing(hipStream_t s) {
-  hipStreamCaptureStatus cst = hipStreamCaptureStatusNone;
-  return hipStreamIsCapturing(s, &cst) == hipSuccess && cst != hipStreamCaptureStatusNone;
-}
-
-// Call order on one handle.  Every call reuses the handle's device scratch
-// (the extractor's arena, cell keys and octree tables; the matcher's grid,
-// candidate lists and claim buffers), and a batch call runs asynchronously on
-// whatever stream its caller passes, so a call on a stream other than the
-// previous call's makes its stream wait for that call first (on the device, no
-// host synchronisation), and every call records where it ended.  The reference
-// has the same rule in host form: an ORBextractor is not reentrant
-// (include/ORBextractor.h:85), a Frame drives two instances concurrently
-// (src/Frame.cc:81-84).  A stream being captured into a graph is left to the
-// caller's ordering of the graph's launches.  (Growing a scratch buffer is
-// safe on its own: hipFree synchronises the device.)
-#ifndef ORB_CALL_ORDER
-#define ORB_CALL_ORDER 1  // 0: no cross-stream waits (the ordering test's negative control only)
-#endif
-static inline bool must_wait(hipStream_t last, hipStream_t s) {
-  return ORB_CALL_ORDER && last && last != s;
-}
-struct CallOrder {
-  hipEvent_t ev;
-  hipStream_t* last;
-  hipStream_t s;
-  bool capture;
-  orb_status_t status = ORB_OK;
-  CallOrder(hipEvent_t e, hipStream_t* l, hipStream_t st)
-      : ev(e), last(l), s(st), capture(stream_capturing(st)) {
-    if (!capture && must_wait(*last, s) && hipStreamWaitEvent(s, ev, 0) != hipSuccess)
-      status = ORB_EDEVICE;
-  }
-  // the call synchronised its stream: nothing of it is pending any more
-  void settled() {
-    if (!capture) *last = nullptr;
-    capture = true;
-  }
-  ~CallOrder() {
-    if (!capture && hipEventRecord(ev, s) == hipSuccess) *last = s;
-  }
-};
-
-// Wait for a stream whose results the caller reads next.  The synchronous
-// entry points (one frame, one SearchByProjection) sit on the tracking
-// thread's critical path, where hipStreamSynchronize returned 5-13 us after
-// the stream's last operation (profiles/r06_dropin_timeline.txt); polling the
-// stream returns within a query (~1 us) of it.  Bounded: past 2 ms of polling
-// the wait blocks as hipStreamSynchronize does.
-static hipError_t stream_wait(hipStream_t s) {
-  const auto t0 = std::chrono::steady_clock::now();
-  for (unsigned i = 1;; ++i) {
-    const hipError_t e = hipStreamQuery(s);
-    if (e != hipErrorNotReady) return e;
-    if ((i & 63) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2))
-      return hipStreamSynchronize(s);
-  }
-}
-
-// Growable device buffer, freed with the handle that owns it (the handle's
-// destroy function sets the device and drains its stream first).
-struct DevBuf {
-  void* p = nullptr;
-  size_t bytes = 0;
-  DevBuf() = default;
-  DevBuf(const DevBuf&) = delete;
-  DevBuf& operator=(const DevBuf&) = delete;
-  ~DevBuf() { release(); }
-  orb_status_t ensure(size_t n) {
-    if (n <= bytes) return ORB_OK;
-    if (p) hipFree(p);
-    p = nullptr;
-    bytes = 0;
-    if (hipMalloc(&p, n) != hipSuccess) return ORB_ENOMEM;
-    bytes = n;
-    return ORB_OK;
-  }
-  void release() {
-    if (p) hipFree(p);
-    p = nullptr;
-    bytes = 0;
-  }
-  template <typename T>
-  T* as() const { return (T*)p; }
-};
-
-// Pinned host staging for the host-buffer API: one contiguous DMA each way
-// (a 2-D copy from pageable memory goes row by row, ~7 us per row).
-struct HostBuf {
-  void* p = nullptr;
-  size_t bytes = 0;
-  HostBuf() = default;
-  HostBuf(const HostBuf&) = delete;
-  HostBuf& operator=(const HostBuf&) = delete;
-  ~HostBuf() { release(); }
-  orb_status_t ensure(size_t n) {
-    if (n <= bytes) return ORB_OK;
-    if (p) hipHostFree(p);
-    p = nullptr;
-    bytes = 0;
-    if (hipHostMalloc(&p, n, hipHostMallocDefault) != hipSuccess) return ORB_ENOMEM;
-    bytes = n;
-    return ORB_OK;
-  }
-  void release() {
-    if (p) hipHostFree(p);
-    p = nullptr;
-    bytes = 0;
-  }
-  template <typename T>
-  T* as() const { return (T*)p; }
-};
-
-// HIP-event timing of kernel stages on the stream they are launched on.  Each
-// profiled call takes a fresh set of events from a pool (no synchronisation in
-// the launch path); read() drains every recorded set and accumulates per-stage
-// milliseconds, so a timed region of K calls is measured without perturbing it.
-struct StageProfiler {
-  // Per call: (begin, end) event pairs per stage -- up to maxSeg[stage]
-  // segments, e.g. one per level for a stage launched level by level, whose
-  // durations are summed -- recorded on whichever stream runs that stage
-  // (stages may overlap), plus a (begin, end) pair for the whole call on the
-  // caller's stream.
-  static constexpr int kMaxStages = 8;
-  bool enabled = false;
-  bool serial = false;  // isolated timing: every stage on the caller's stream, one after another
-  int nStages = 0;
-  const char* names[kMaxStages] = {};
-  int maxSeg[kMaxStages] = {1, 1, 1, 1, 1, 1, 1, 1};
-  std::vector<std::vector<hipEvent_t>> pool;  // each: 2 * sum(maxSeg) + 2 events
-  std::vector<std::vector<uint8_t>> segs;     // per call: segments recorded per stage
-  size_t used = 0;
-  double ms[kMaxStages + 1] = {};
-  long launches[kMaxStages + 1] = {};
-  int launchesPerCall[kMaxStages] = {};
-
-  int base(int stage) const {
-    int o = 0;
-    for (int i = 0; i < stage; ++i) o += maxSeg[i];
-    return o;
-  }
-  int total() const { return base(nStages); }
-  void reset() {
-    used = 0;
-    for (int i = 0; i <= kMaxStages; ++i) { ms[i] = 0; launches[i] = 0; }
-  }
-  std::vector<hipEvent_t>* begin_call() {
-    if (!enabled) return nullptr;
-    if (used == pool.size()) {
-      pool.emplace_back(2 * total() + 2);
-      for (hipEvent_t& e : pool.back()) hipEventCreate(&e);
-      segs.emplace_back(kMaxStages, 0);
-    }
-    std::fill(segs[used].begin(), segs[used].end(), (uint8_t)1);
-    return &pool[used++];
-  }
-  // of the current call: stage not run / run as n segments
-  void not_run(int stage) { segs[used - 1][stage] = 0; }
-  void segments(int stage, int n) { segs[used - 1][stage] = (uint8_t)n; }
-  hipEvent_t b(std::vector<hipEvent_t>* ev, int stage, int seg = 0) const {
-    return (*ev)[2 * (base(stage) + seg)];
-  }
-  hipEvent_t e(std::vector<hipEvent_t>* ev, int stage, int seg = 0) const {
-    return (*ev)[2 * (base(stage) + seg) + 1];
-  }
-  hipEvent_t t0(std::vector<hipEvent_t>* ev) const { return (*ev)[2 * total()]; }
-  hipEvent_t t1(std::vector<hipEvent_t>* ev) const { return (*ev)[2 * total() + 1]; }
-  void drain() {
-    for (size_t c = 0; c < used; ++c) {
-      std::vector<hipEvent_t>& ev = pool[c];
-      if (hipEventSynchronize(t1(&ev)) != hipSuccess) continue;
-      for (int i = 0; i < nStages; ++i) {
-        if (launchesPerCall[i] == 0 || segs[c][i] == 0) continue;  // stage not run
-        bool ok = true;
-        double sum = 0;
-        for (int g = 0; g < segs[c][i] && ok; ++g) {
-          float t = 0.f;
-          ok = hipEventElapsedTime(&t, b(&ev, i, g), e(&ev, i, g)) == hipSuccess;
-          sum += t;
-        }
-        if (ok) {
-          ms[i] += sum;
-          launches[i] += launchesPerCall[i];
-        } else {
-          (void)hipGetLastError();  // clear it: torch checks the last error after its launches
-        }
-      }
-      float t = 0.f;
-      if (hipEventElapsedTime(&t, t0(&ev), t1(&ev)) == hipSuccess) {
-        ms[nStages] += t;
-        launches[nStages] += 1;
-      }
-    }
-    used = 0;
-  }
-  void destroy() {
-    for (auto& v : pool)
-      for (hipEvent_t ev : v) hipEventDestroy(ev);
-    pool.clear();
-    segs.clear();
-    used = 0;
-  }
-};
-
-#define PROF_REC(ev, evt, strm) \
-  do {                                            \
-    if (ev) HIP_TRY(hipEventRecord((evt), (strm))); \
-  } while (0)
-
-orb_status_t check_device(int device) {
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return ORB_ENODEV;
-  if (device < 0 || device >= n) return ORB_EINVAL;
-  hipDeviceProp_t prop;
-  if (hipGetDeviceProperties(&prop, device) != hipSuccess) return ORB_EDEVICE;
-  if (strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
-    if (getenv("ORB_AMD_DEBUG")) fprintf(stderr, "[orb_amd] device %d is %s, need gfx950\n", device, prop.gcnArchName);
-    return ORB_ENODEV;
-  }
-  return ORB_OK;
-}
-
-}  // namespace
-
 // ================================================================ extractor
-struct orb_extractor {
-  int device = 0;
-  int nfeatures = 0, nlevels = 0, iniTh = 0, minTh = 0;
-  float scaleFactorF = 1.2f;
-  double scaleFactor = 1.2;
-  std::vector<float> scale, invScale, sigma2, invSigma2;
-  std::vector<int> quota;
-  int umax[16];
-  hipStream_t stream = nullptr;
-  hipStream_t stream2 = nullptr;  // the device's shared side stream: FAST beside the resize chain
-  hipStream_t privSide = nullptr; // this handle's side stream while its caller's stream is captured
-  hipEvent_t evL0Fork = nullptr, evL0Join = nullptr;  // level-0 FAST beside the resize chain
-  hipEvent_t evLvl = nullptr;  // the resize chain has written level FAST_SIDE_LEVELS
-  hipEvent_t evBatch = nullptr;  // recorded at the end of every run_batch on its stream
-  hipStream_t lastStream = nullptr;  // the stream evBatch was last recorded on (null: none pending)
-  bool ownStream = false;
-  std::mutex mu;
-
-  // plan for the current image size
-  int planW = -1, planH = -1;
-  OrbPlanDesc plan;
-  std::vector<OrbCellDesc> cells;
-  long long arenaBytes = 0, blurBytes = 0;
-  int maxCellsPerLevel = 0, nodeCapMax = 0, ldsKeyCap = 0;
-  int nResizePairs = 0;  // resize launches per call with the level pairs (PYR_PAIR_MAX_IMAGES)
-  DevBuf dCells, dRtab, dTiles, dBands;
-
-  // batch scratch
-  int batchCap = 0;
-  DevBuf dBlur;  // one image's blurred levels (orb_extractor_blurred_level, on demand)
-  DevBuf dArena, dCellKeys, dCellCount, dGKeys, dGNid, dOutKeys, dOutCount, dErr;
-  DevBuf dOctNodes;            // octree node tables in global memory (large nfeatures)
-  long long octNodeBytes = 0;  // per (image, level) slice; 0: node tables in LDS
-  // single-image API scratch
-  // single-image API: dImg (the image at a 64-B row pitch) and dOne = [count,
-  // pad x3 | cap keypoints | cap x 32 descriptors], mirrored by the pinned
-  // hImg / hOut so each call is one DMA in and one DMA out
-  DevBuf dImg, dOne;
-  HostBuf hImg, hOut, hLvl;  // hLvl: staging of orb_extractor_pyramid_level / _blurred_level
-  // host mirror of the single-frame call's levels 1.. (orb_extractor_host_pyramid):
-  // once asked for, the arena's D2H joins every later call's graph
-  HostBuf hPyr;
-  bool pyrReadback = false, hPyrValid = false;
-  int oneCap = 0;            // capacity of the dOne layout
-  bool lastSingle = false;   // the last call was orb_extractor_extract (dOne is current)
-  // the whole single-image call (H2D, every kernel, D2H) as one hipGraph per
-  // plan; keyed by the buffers it captured (any reallocation re-captures)
-  hipGraphExec_t oneExec = nullptr;
-  std::vector<const void*> oneKey;
-  int lastW = 0, lastH = 0;
-  size_t lastImgStride = 0;
-  const uint8_t* lastImg0 = nullptr;  // level 0 of the last batch (device)
-  size_t lastImg0Pitch = 0;
-  int lastImg0Stride = 0;
-
-  // profiling: stages k_pyr_resize (x nlevels-1), k_blur_levels, k_fast_band, k_octree,
-  // k_orient_desc
-  StageProfiler prof;
-};
-
 static void compute_tables(orb_extractor* h) {
   const int L = h->nlevels;
   h->scale.assign(L, 0.f);
@@ -664,7 +348,6 @@ static orb_status_t ensure_batch(orb_extractor* h, int B) {
   return ORB_OK;
 }
 
-static int least_stream_prio();
 // The shared side streams (shared_side_stream below) are destroyed by an exit
 // handler; run_batch holds g_sideUse shared while it enqueues, and a call that
 // starts after the release fails with ORB_EDEVICE instead of launching on a
@@ -854,13 +537,6 @@ orb_status_t orb_device_count(int* n) {
   return c > 0 ? ORB_OK : ORB_ENODEV;
 }
 
-// The device's least stream priority: the handles' own streams take it (see
-// create_own_stream).
-static int least_stream_prio() {
-  int lo = 0, hi = 0;
-  hipDeviceGetStreamPriorityRange(&lo, &hi);
-  return lo;
-}
 // One side stream per device, shared by every extractor handle of the process.
 // Each stream holds an HSA queue, and a process with more queues than the
 // hardware maps at once (the bench with its C3 / C5 handles: 11, with one
@@ -906,21 +582,6 @@ static hipStream_t shared_side_stream(int device) {
     if (e != hipSuccess) s[device] = nullptr;
   }
   return s[device];  // until exit
-}
-
-// A handle's own stream (single-frame calls, host-buffer matchers, readbacks,
-// graph capture) at the device's least priority.  HIP backs the streams of a
-// process by a few HSA queues per priority level and maps a new stream onto
-// the least-used queue of its level; normal-priority streams a library
-// creates early (ORB-SLAM2 builds its extractors and matchers at start-up)
-// take normal queues the caller's own streams then share: a caller's
-// high-priority stream ran 2x slower beside busy normal-priority streams
-// after three idle normal streams had been created first, with or without
-// this library (tools/probe/contention_probe.py, profiles/r05_contention.txt).
-// The least priority keeps the library out of the pools the caller's streams
-// use (the side stream has a queue of its own, a full-CU-mask stream).
-static hipError_t create_own_stream(hipStream_t* s) {
-  return hipStreamCreateWithPriority(s, hipStreamNonBlocking, least_stream_prio());
 }
 
 static bool create_side_streams(orb_extractor* h) {
@@ -1064,13 +725,6 @@ orb_status_t orb_extractor_extract_batch(orb_extractor_t* h, const uint8_t* d_im
   h->lastW = width;
   h->lastH = height;
   return ORB_OK;
-}
-
-// Row pitch of the one-frame path's staged image (pinned and device): the
-// width itself (the kernels take any stride), so a contiguous caller image is
-// staged with one memcpy instead of one per row
-static size_t one_stride(int width) {
-  return (size_t)width;
 }
 
 orb_status_t orb_extractor_extract(orb_extractor_t* h, const uint8_t* image, int width,
@@ -1347,59 +1001,6 @@ static FrustumParams frustum_params(const orb_camera_t* cam, float min_x, float 
   return f;
 }
 
-// orb_matcher::sx, the scratch of the projection-window variants (PP_*), of
-// KF-KF SearchByBoW (BW_*) and of SearchForTriangulation (TR_*): three calls
-// that never overlap name the same buffers.
-enum MatcherSlot {
-  PP_FRAME0 = 0, PP_FRAME1 = 4,  // two searched (key)frames: keys, desc, n, grid (PPFrame)
-  PP_MPS = 8, PP_MPDESC, PP_VALID, PP_SKIP, PP_ANGLE, PP_URIGHT, PP_RECS, PP_TOPK, PP_NCAND,
-  PP_BEST, PP_LOCKED, PP_KPMATCH, PP_COUNT, PP_BEST12, PP_BEST21, PP_MUTUAL, SX_COUNT,
-  BW_DESC1 = 0, BW_ANGLE1, BW_MP1, BW_BAD1, BW_IDS1, BW_OFFS1, BW_FEATS1,
-  BW_DESC2, BW_ANGLE2, BW_MP2, BW_BAD2, BW_IDS2, BW_OFFS2, BW_FEATS2, BW_MATCH, BW_ACC, BW_COUNT,
-  TR_KEYS1 = 0, TR_DESC1, TR_UR1, TR_HASMP1, TR_IDS1, TR_OFFS1, TR_FEATS1,
-  TR_KEYS2, TR_DESC2, TR_UR2, TR_HASMP2, TR_IDS2, TR_OFFS2, TR_FEATS2, TR_MATCH, TR_ACC, TR_COUNT
-};
-
-struct orb_matcher {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  hipEvent_t evLast = nullptr;        // recorded where the last call ended (CallOrder)
-  hipStream_t lastStream = nullptr;   // its stream (null: nothing pending)
-  std::mutex mu;
-  // profiling: stages k_grid_build, k_proj_candidates + k_proj_resolve
-  StageProfiler prof;
-  DevBuf dKeys, dDesc, dUr, dLocked, dNKeys, dMps, dMpDesc, dNMps, dCellStart, dCellIdx, dTopk,
-      dNcand, dKpMatch, dNMatch, dA, dB, dOut;
-  DevBuf dJac;  // Jacobi-resolve scratch (ORB_RESOLVE_JACOBI)
-  DevBuf dCpKeys;  // k_close_points' key scratch for frames above CP_LDS_KEYS slots
-  DevBuf dPoKeys, dPoUr, dPoIdx, dPoPts, dPoOut;  // orb_pose_optimization's staged frame
-  DevBuf dPoRecs;  // k_pose_optimization's edge records for frames above PO_LDS_EDGES slots
-  DevBuf dLmTable;  // k_local_map's first-occurrence table by point id (the scratch tier)
-  DevBuf dOvf, dOvfCtr;  // candidate lists of SearchByProjection(F, localMap) (ProjParams.ovf)
-  uint32_t ovfGen = 0;
-  int stagedN = -1, stagedM = -1;  // orb_match_projection_local_stage's layout
-  bool begun = false, begunStereo = false, begunLocked = false;  // _begin sent the frame's part
-  int resolveSchedule = ORB_RESOLVE_AUTO;  // orb_matcher_set_resolve
-  int jacobiRounds = 6;
-  // stereo / frame / BoW scratch
-  DevBuf dStRowStart, dStRowIdx;  // stereo vRowIndices (CSR per pair)
-  DevBuf dProjStage;              // cell-ordered keypoints for k_proj_candidates (16 B per slot)
-  DevBuf dRKeys, dRDesc, dNR, dPyr, dPairLv, dDepth, dSad, dBowA, dBowB, dBowC, dBowD, dBowE,
-      dBowF, dBowG, dBowH, dBowI, dBowJ, dBowK;
-  HostBuf hPyr;  // pinned staging of the host stereo pyramids (one DMA)
-  // orb_match_projection_local: every input in one pinned block / one DMA, and
-  // the matches + count back in one
-  HostBuf hIn, hOutM;
-  DevBuf dIn;
-  // frustum scratch
-  DevBuf dMapPts, dPose, dTracks, dNInView;
-  // SearchForInitialization / ComputeDistinctiveDescriptors scratch
-  DevBuf dK1, dD1, dK2, dD2, dN1, dN2, dPrev, dList, dM12, dOffs, dObsDesc, dBest, dBestDesc,
-      dInitQ, dInitStage, dInitCounts;
-  DevBuf sx[SX_COUNT];  // projection / triangulation / KF-KF BoW scratch (MatcherSlot)
-  std::vector<uint8_t> hostScratch;
-};
-
 extern "C" {
 
 int orb_descriptor_distance(const uint8_t* a, const uint8_t* b) {
@@ -1511,11 +1112,9 @@ static orb_status_t local_batch(
       !(max_y > min_y))
     return ORB_EINVAL;
   if (n_problems == 0) return ORB_OK;
-  std::lock_guard<std::mutex> g(m->mu);
-  hipSetDevice(m->device);
-  hipStream_t s = stream ? (hipStream_t)stream : m->stream;
-  CallOrder order(m->evLast, &m->lastStream, s);
-  if (order.status) return order.status;
+  MatcherCall call(m, stream);
+  if (call.status) return call.status;
+  const hipStream_t s = call.s;
   ProjParams P =
       proj_params(min_x, max_x, min_y, max_y, n_levels, scale_factors, th, nnratio);
   orb_status_t st;
@@ -1918,13 +1517,6 @@ orb_status_t orb_frustum_batch(orb_matcher_t* m, int n_problems, const orb_map_p
 }
 
 // ------------------------------------------------------------------ stereo
-static orb_status_t upload(DevBuf& b, const void* src, size_t n, hipStream_t s) {
-  orb_status_t st = b.ensure(std::max<size_t>(n, 16));
-  if (st) return st;
-  if (n) HIP_TRY(hipMemcpyAsync(b.p, src, n, hipMemcpyHostToDevice, s));
-  return ORB_OK;
-}
-
 // the row-index scratch of orb_k_stereo for n_pairs pairs
 static orb_status_t stereo_scratch(orb_matcher* m, const StereoParams* params, int kpStride,
                                    int npairs) {
@@ -1953,11 +1545,9 @@ orb_status_t orb_stereo_match(orb_matcher_t* m, const orb_stereo_input_t* in, fl
       return ORB_EINVAL;
   for (int i = 0; i < NL; ++i) { u_right[i] = -1.0f; depth[i] = -1.0f; }
   if (NL == 0) return ORB_OK;
-  std::lock_guard<std::mutex> g(m->mu);
-  hipSetDevice(m->device);
-  hipStream_t s = m->stream;
-  CallOrder order(m->evLast, &m->lastStream, s);
-  if (order.status) return order.status;
+  MatcherCall call(m);
+  if (call.status) return call.status;
+  const hipStream_t s = call.s;
   const int stride = std::max(NL, std::max(NR, 1));
   orb_status_t st;
   if ((st = upload(m->dKeys, F->keys, (size_t)NL * sizeof(orb_keypoint_t), s))) return st;
@@ -2019,8 +1609,7 @@ orb_status_t orb_stereo_match(orb_matcher_t* m, const orb_stereo_input_t* in, fl
                        m->dStRowStart.as<int32_t>(), m->dStRowIdx.as<int32_t>(), s));
   HIP_TRY(hipMemcpyAsync(u_right, m->dUr.p, (size_t)NL * 4, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipMemcpyAsync(depth, m->dDepth.p, (size_t)NL * 4, hipMemcpyDeviceToHost, s));
-  HIP_TRY(stream_wait(s));
-  return ORB_OK;
+  return call.finish();
 }
 
 orb_status_t orb_stereo_match_batch(orb_matcher_t* m, int n_pairs, orb_extractor_t* left_ext,
@@ -2036,11 +1625,9 @@ orb_status_t orb_stereo_match_batch(orb_matcher_t* m, int n_pairs, orb_extractor
   if (n_pairs == 0) return ORB_OK;
   const int L = orb_extractor_get_levels(left_ext);
   if (L != orb_extractor_get_levels(right_ext)) return ORB_EINVAL;
-  std::lock_guard<std::mutex> g(m->mu);
-  hipSetDevice(m->device);
-  hipStream_t s = stream ? (hipStream_t)stream : m->stream;
-  CallOrder order(m->evLast, &m->lastStream, s);
-  if (order.status) return order.status;
+  MatcherCall call(m, stream);
+  if (call.status) return call.status;
+  const hipStream_t s = call.s;
   StereoParams P;
   memset(&P, 0, sizeof(P));
   P.nLevels = L;
@@ -2074,8 +1661,7 @@ orb_status_t orb_stereo_match_batch(orb_matcher_t* m, int n_pairs, orb_extractor
                        kp_stride, kp_stride, m->dPairLv.as<StereoPairLevels>(), &P, d_u_right, d_depth, d_sad,
                        n_pairs, m->dStRowStart.as<int32_t>(), m->dStRowIdx.as<int32_t>(), s));
   // the pair-level pointer table must outlive the asynchronous launch
-  HIP_TRY(stream_wait(s));
-  return ORB_OK;
+  return call.finish();
 }
 
 // Frame::ComputeStereoMatches for the pair the two handles extracted last with
@@ -2108,11 +1694,9 @@ orb_status_t orb_stereo_match_extracted(orb_matcher_t* m, orb_extractor_t* left_
   if (nL > capacity) return ORB_ECAPACITY;
   if (nL == 0) return ORB_OK;
   if (!u_right || !depth) return ORB_EINVAL;
-  std::lock_guard<std::mutex> g(m->mu);
-  hipSetDevice(m->device);
-  hipStream_t s = m->stream;
-  CallOrder order(m->evLast, &m->lastStream, s);
-  if (order.status) return order.status;
+  MatcherCall call(m);
+  if (call.status) return call.status;
+  const hipStream_t s = call.s;
   HIP_TRY(hipStreamWaitEvent(s, left_ext->evBatch, 0));
   HIP_TRY(hipStreamWaitEvent(s, right_ext->evBatch, 0));
   StereoParams P;
@@ -2168,7 +1752,7 @@ orb_status_t orb_stereo_match_extracted(orb_matcher_t* m, orb_extractor_t* left_
   HIP_TRY(hipMemcpyAsync(m->hPyr.p, m->dUr.p, (size_t)nL * 4, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipMemcpyAsync(m->hPyr.as<uint8_t>() + (size_t)nL * 4, m->dDepth.p, (size_t)nL * 4,
                          hipMemcpyDeviceToHost, s));
-  HIP_TRY(stream_wait(s));
+  if ((st = call.finish())) return st;
   memcpy(u_right, m->hPyr.p, (size_t)nL * 4);
   memcpy(depth, m->hPyr.as<uint8_t>() + (size_t)nL * 4, (size_t)nL * 4);
   return ORB_OK;
@@ -2191,11 +1775,9 @@ orb_status_t orb_match_projection_frame(orb_matcher_t* m, const orb_frame_t* C,
   if (C->n == 0) return ORB_OK;
   // k_frame_resolve is one block: its LDS must fit one CU (checked before any launch)
   if (orb_k_frame_resolve_lds(C->n, n_last) > ORB_LDS_PER_CU) return ORB_ECAPACITY;
-  std::lock_guard<std::mutex> g(m->mu);
-  hipSetDevice(m->device);
-  hipStream_t s = m->stream;
-  CallOrder order(m->evLast, &m->lastStream, s);
-  if (order.status) return order.status;
+  MatcherCall call(m);
+  if (call.status) return call.status;
+  const hipStream_t s = call.s;
   const int N = C->n, M = n_last;
   orb_status_t st;
   if ((st = upload(m->dKeys, C->keys, (size_t)N * sizeof(orb_keypoint_t), s))) return st;
@@ -2235,8 +1817,7 @@ orb_status_t orb_match_projection_frame(orb_matcher_t* m, const orb_frame_t* C,
                            m->dKpMatch.as<int32_t>(), m->dNMatch.as<int32_t>(), s));
   HIP_TRY(hipMemcpyAsync(kp_match, m->dKpMatch.p, (size_t)N * 4, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipMemcpyAsync(nmatches, m->dNMatch.p, 4, hipMemcpyDeviceToHost, s));
-  HIP_TRY(stream_wait(s));
-  return ORB_OK;
+  return call.finish();
 }
 
 // ------------------------------------------------------------- SearchByBoW
@@ -2255,11 +1836,9 @@ orb_status_t orb_match_bow(orb_matcher_t* m, int n_kf, const uint8_t* kf_desc,
   for (int j = 0; j < n_f; ++j) f_match[j] = -1;
   if (n_kf == 0 || n_f == 0 || kf_nodes == 0 || f_nodes == 0) return ORB_OK;
   const int nKfFeats = kf_offs[kf_nodes], nFFeats = f_offs[f_nodes];
-  std::lock_guard<std::mutex> g(m->mu);
-  hipSetDevice(m->device);
-  hipStream_t s = m->stream;
-  CallOrder order(m->evLast, &m->lastStream, s);
-  if (order.status) return order.status;
+  MatcherCall call(m);
+  if (call.status) return call.status;
+  const hipStream_t s = call.s;
   orb_status_t st;
   if ((st = upload(m->dBowA, kf_desc, (size_t)n_kf * 32, s))) return st;
   if ((st = upload(m->dBowB, kf_angle, (size_t)n_kf * 4, s))) return st;
@@ -2286,8 +1865,7 @@ orb_status_t orb_match_bow(orb_matcher_t* m, int n_kf, const uint8_t* kf_desc,
                     m->dTopk.as<int32_t>(), m->dNMatch.as<int32_t>(), s));
   HIP_TRY(hipMemcpyAsync(f_match, m->dKpMatch.p, (size_t)n_f * 4, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipMemcpyAsync(nmatches, m->dNMatch.p, 4, hipMemcpyDeviceToHost, s));
-  HIP_TRY(stream_wait(s));
-  return ORB_OK;
+  return call.finish();
 }
 
 // ------------------------------------------------- SearchForInitialization
@@ -2349,11 +1927,9 @@ orb_status_t orb_search_for_initialization(orb_matcher_t* m, const orb_frame_t* 
   if (N1 == 0 || N2 == 0) return ORB_OK;
   const int stride = std::max(N1, N2);
   if (!init_stride_ok(stride)) return ORB_ECAPACITY;
-  std::lock_guard<std::mutex> g(m->mu);
-  hipSetDevice(m->device);
-  hipStream_t s = m->stream;
-  CallOrder order(m->evLast, &m->lastStream, s);
-  if (order.status) return order.status;
+  MatcherCall call(m);
+  if (call.status) return call.status;
+  const hipStream_t s = call.s;
   orb_status_t st;
   if ((st = upload(m->dK1, f1->keys, (size_t)N1 * sizeof(orb_keypoint_t), s))) return st;
   if ((st = upload(m->dD1, f1->descriptors, (size_t)N1 * 32, s))) return st;
@@ -2374,8 +1950,7 @@ orb_status_t orb_search_for_initialization(orb_matcher_t* m, const orb_frame_t* 
   HIP_TRY(hipMemcpyAsync(matches12, m->dM12.p, (size_t)N1 * 4, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipMemcpyAsync(prev_matched, m->dPrev.p, (size_t)N1 * 8, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipMemcpyAsync(nmatches, m->dNMatch.p, 4, hipMemcpyDeviceToHost, s));
-  HIP_TRY(stream_wait(s));
-  return ORB_OK;
+  return call.finish();
 }
 
 orb_status_t orb_search_for_initialization_batch(
@@ -2390,11 +1965,9 @@ orb_status_t orb_search_for_initialization_batch(
       !d_matches12 || !d_nmatches || n_problems > 65535)
     return ORB_EINVAL;
   if (!init_stride_ok(kp_stride)) return kp_stride <= 0 ? ORB_EINVAL : ORB_ECAPACITY;
-  std::lock_guard<std::mutex> g(m->mu);
-  hipSetDevice(m->device);
-  hipStream_t s = stream ? (hipStream_t)stream : m->stream;
-  CallOrder order(m->evLast, &m->lastStream, s);
-  if (order.status) return order.status;
+  MatcherCall call(m, stream);
+  if (call.status) return call.status;
+  const hipStream_t s = call.s;
   return search_init_device(m, n_problems, d_keys1, d_desc1, d_n1, d_keys2, d_desc2, d_n2,
                             kp_stride, min_x, max_x, min_y, max_y, window_size, nnratio,
                             check_orientation, d_prev_matched, d_matches12, d_nmatches, s);
@@ -2411,11 +1984,9 @@ orb_status_t orb_distinctive_descriptors(orb_matcher_t* m, int n_mp, const int32
     if (obs_offs[i + 1] < obs_offs[i]) return ORB_EINVAL;
   const size_t nobs = (size_t)obs_offs[n_mp];
   if (nobs > 0 && !obs_desc) return ORB_EINVAL;
-  std::lock_guard<std::mutex> g(m->mu);
-  hipSetDevice(m->device);
-  hipStream_t s = m->stream;
-  CallOrder order(m->evLast, &m->lastStream, s);
-  if (order.status) return order.status;
+  MatcherCall call(m);
+  if (call.status) return call.status;
+  const hipStream_t s = call.s;
   orb_status_t st;
   if ((st = upload(m->dOffs, obs_offs, (size_t)(n_mp + 1) * 4, s))) return st;
   if ((st = upload(m->dObsDesc, obs_desc, nobs * 32, s))) return st;
@@ -2428,8 +1999,7 @@ orb_status_t orb_distinctive_descriptors(orb_matcher_t* m, int n_mp, const int32
   if (descriptors)
     HIP_TRY(hipMemcpyAsync(descriptors, m->dBestDesc.p, (size_t)n_mp * 32, hipMemcpyDeviceToHost,
                            s));
-  HIP_TRY(stream_wait(s));
-  return ORB_OK;
+  return call.finish();
 }
 
 orb_status_t orb_distinctive_descriptors_batch(orb_matcher_t* m, int n_mp,
@@ -2595,11 +2165,9 @@ orb_status_t orb_search_by_projection_reloc(orb_matcher_t* m, const orb_frame_t*
   if (frame->n == 0 || n_mp == 0) return ORB_OK;
   // k_pp_resolve is one block: its LDS must fit one CU (checked before any launch)
   if (orb_k_pp_resolve_lds(frame->n, n_mp) > ORB_LDS_PER_CU) return ORB_ECAPACITY;
-  std::lock_guard<std::mutex> g(m->mu);
-  hipSetDevice(m->device);
-  hipStream_t s = m->stream;
-  CallOrder order(m->evLast, &m->lastStream, s);
-  if (order.status) return order.status;
+  MatcherCall call(m);
+  if (call.status) return call.status;
+  const hipStream_t s = call.s;
   if ((st = pp_frame(m, frame, P, PP_FRAME0, s))) return st;
   return pp_run(m, 0, P, PP_FRAME0, frame, kp_locked, n_mp, mps, nullptr, nullptr, mp_desc,
                 check_orientation ? kf_angle : nullptr, nullptr, kp_match, nmatches, s);
@@ -2619,11 +2187,9 @@ orb_status_t orb_search_by_projection_sim3(orb_matcher_t* m, const orb_frame_t* 
   *nmatches = 0;
   if (kf->n == 0 || n_mp == 0) return ORB_OK;
   if (orb_k_pp_resolve_lds(kf->n, n_mp) > ORB_LDS_PER_CU) return ORB_ECAPACITY;
-  std::lock_guard<std::mutex> g(m->mu);
-  hipSetDevice(m->device);
-  hipStream_t s = m->stream;
-  CallOrder order(m->evLast, &m->lastStream, s);
-  if (order.status) return order.status;
+  MatcherCall call(m);
+  if (call.status) return call.status;
+  const hipStream_t s = call.s;
   if ((st = pp_frame(m, kf, P, PP_FRAME0, s))) return st;
   return pp_run(m, 1, P, PP_FRAME0, kf, nullptr, n_mp, mps, nullptr, nullptr, mp_desc, nullptr,
                 nullptr, kp_matched, nmatches, s);
@@ -2646,11 +2212,9 @@ orb_status_t orb_fuse(orb_matcher_t* m, const orb_frame_t* kf, const float* inv_
   *n_fuse = 0;
   for (int i = 0; i < n_mp; ++i) fuse_idx[i] = -1;
   if (kf->n == 0 || n_mp == 0) return ORB_OK;
-  std::lock_guard<std::mutex> g(m->mu);
-  hipSetDevice(m->device);
-  hipStream_t s = m->stream;
-  CallOrder order(m->evLast, &m->lastStream, s);
-  if (order.status) return order.status;
+  MatcherCall call(m);
+  if (call.status) return call.status;
+  const hipStream_t s = call.s;
   if ((st = pp_frame(m, kf, P, PP_FRAME0, s))) return st;
   return pp_run(m, 2, P, PP_FRAME0, kf, nullptr, n_mp, mps, nullptr, nullptr, mp_desc, nullptr,
                 fuse_idx, nullptr, n_fuse, s);
@@ -2669,11 +2233,9 @@ orb_status_t orb_fuse_sim3(orb_matcher_t* m, const orb_frame_t* kf, const float*
   *n_fuse = 0;
   for (int i = 0; i < n_mp; ++i) fuse_idx[i] = -1;
   if (kf->n == 0 || n_mp == 0) return ORB_OK;
-  std::lock_guard<std::mutex> g(m->mu);
-  hipSetDevice(m->device);
-  hipStream_t s = m->stream;
-  CallOrder order(m->evLast, &m->lastStream, s);
-  if (order.status) return order.status;
+  MatcherCall call(m);
+  if (call.status) return call.status;
+  const hipStream_t s = call.s;
   if ((st = pp_frame(m, kf, P, PP_FRAME0, s))) return st;
   return pp_run(m, 3, P, PP_FRAME0, kf, nullptr, n_mp, mps, nullptr, nullptr, mp_desc, nullptr,
                 fuse_idx, nullptr, n_fuse, s);
@@ -2710,11 +2272,9 @@ orb_status_t orb_search_by_sim3(orb_matcher_t* m, const orb_frame_t* kf1, const 
   *nfound = 0;
   for (int i = 0; i < kf1->n; ++i) match12[i] = -1;
   if (kf1->n == 0 || kf2->n == 0) return ORB_OK;
-  std::lock_guard<std::mutex> g(m->mu);
-  hipSetDevice(m->device);
-  hipStream_t s = m->stream;
-  CallOrder order(m->evLast, &m->lastStream, s);
-  if (order.status) return order.status;
+  MatcherCall call(m);
+  if (call.status) return call.status;
+  const hipStream_t s = call.s;
   if ((st = pp_frame(m, kf2, P1, PP_FRAME0, s))) return st;
   if ((st = pp_frame(m, kf1, P2, PP_FRAME1, s))) return st;
   if ((st = m->sx[PP_BEST12].ensure((size_t)kf1->n * 4))) return st;
@@ -2733,8 +2293,7 @@ orb_status_t orb_search_by_sim3(orb_matcher_t* m, const orb_frame_t* kf1, const 
                             m->sx[PP_BEST21].as<int32_t>(), out, out + kf1->n, s));
   HIP_TRY(hipMemcpyAsync(match12, out, (size_t)kf1->n * 4, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipMemcpyAsync(nfound, out + kf1->n, 4, hipMemcpyDeviceToHost, s));
-  HIP_TRY(stream_wait(s));
-  return ORB_OK;
+  return call.finish();
 }
 
 orb_status_t orb_match_bow_kf(orb_matcher_t* m, int n1, const uint8_t* desc1,
@@ -2755,11 +2314,9 @@ orb_status_t orb_match_bow_kf(orb_matcher_t* m, int n1, const uint8_t* desc1,
   if (n1 == 0 || n2 == 0 || nodes1 == 0 || nodes2 == 0) return ORB_OK;
   if ((size_t)4 * ((n2 + 31) / 32) * 4 > 65536) return ORB_ECAPACITY;
   const int nF1 = offs1[nodes1], nF2 = offs2[nodes2];
-  std::lock_guard<std::mutex> g(m->mu);
-  hipSetDevice(m->device);
-  hipStream_t s = m->stream;
-  CallOrder order(m->evLast, &m->lastStream, s);
-  if (order.status) return order.status;
+  MatcherCall call(m);
+  if (call.status) return call.status;
+  const hipStream_t s = call.s;
   orb_status_t st;
   DevBuf* b = m->sx;
   if ((st = upload(b[BW_DESC1], desc1, (size_t)n1 * 32, s))) return st;
@@ -2791,8 +2348,7 @@ orb_status_t orb_match_bow_kf(orb_matcher_t* m, int n1, const uint8_t* desc1,
                     b[BW_ACC].as<int32_t>(), b[BW_COUNT].as<int32_t>(), s));
   HIP_TRY(hipMemcpyAsync(match12, b[BW_MATCH].p, (size_t)n1 * 4, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipMemcpyAsync(nmatches, b[BW_COUNT].p, 4, hipMemcpyDeviceToHost, s));
-  HIP_TRY(stream_wait(s));
-  return ORB_OK;
+  return call.finish();
 }
 
 orb_status_t orb_search_for_triangulation(
@@ -2827,11 +2383,9 @@ orb_status_t orb_search_for_triangulation(
   for (int i = 0; i < kf1->n; ++i) match12[i] = -1;
   if (kf1->n == 0 || kf2->n == 0 || nodes1 == 0 || nodes2 == 0) return ORB_OK;
   const int nF1 = offs1[nodes1], nF2 = offs2[nodes2];
-  std::lock_guard<std::mutex> g(m->mu);
-  hipSetDevice(m->device);
-  hipStream_t s = m->stream;
-  CallOrder order(m->evLast, &m->lastStream, s);
-  if (order.status) return order.status;
+  MatcherCall call(m);
+  if (call.status) return call.status;
+  const hipStream_t s = call.s;
   orb_status_t st;
   DevBuf* b = m->sx;
   const int n1 = kf1->n, n2 = kf2->n;
@@ -2863,734 +2417,7 @@ orb_status_t orb_search_for_triangulation(
       b[TR_MATCH].as<int32_t>(), b[TR_ACC].as<int32_t>(), b[TR_COUNT].as<int32_t>(), s));
   HIP_TRY(hipMemcpyAsync(match12, b[TR_MATCH].p, (size_t)n1 * 4, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipMemcpyAsync(nmatches, b[TR_COUNT].p, 4, hipMemcpyDeviceToHost, s));
-  HIP_TRY(stream_wait(s));
-  return ORB_OK;
-}
-
-// ------------------------------------------------------- DBoW2 vocabulary
-// TemplatedVocabulary<FORB::TDescriptor, FORB> as loaded by loadFromTextFile
-// (Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:1362-1448) and its transform
-// (:1128-1283), the producer of Frame/KeyFrame::mBowVec and mFeatVec
-// (src/Frame.cc:439-449, src/KeyFrame.cc:60-71).  The tree lives on the
-// device, renumbered breadth-first (vocab_kernels.hip).  (Hidden: its implicit
-// destructor, which frees the buffers, is no export of the library.)
-struct __attribute__((visibility("hidden"))) orb_vocabulary {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  std::mutex mu;
-  int k = 0, L = 0, scoring = 0, weighting = 0, nNodes = 0, nWords = 0;
-  DevBuf dInfo, dDesc, dWord, dWeight, dOrig;
-  DevBuf dIn, dCounts, dFWord, dFWeight, dFNode, dBowW, dBowV, dNW, dFvN, dFvO, dFvF, dNFv;
-  DevBuf dScore[7];  // orb_vocabulary_score: a offs / words / values, b likewise, out
-};
-
-static orb_status_t vocab_build(orb_vocabulary* V, int n_nodes, const int32_t* parent,
-                                const uint8_t* leaf, const uint8_t* desc, const double* weight) {
-  // children in creation order (m_nodes[pid].children.push_back(nid), :1416)
-  std::vector<int32_t> ccount(n_nodes, 0), cstart(n_nodes + 1, 0), clist(std::max(n_nodes - 1, 1));
-  for (int i = 1; i < n_nodes; ++i) {
-    if (parent[i] < 0 || parent[i] >= i) return ORB_EINVAL;
-    ++ccount[parent[i]];
-  }
-  for (int i = 0; i < n_nodes; ++i) cstart[i + 1] = cstart[i] + ccount[i];
-  {
-    std::vector<int32_t> fill(cstart.begin(), cstart.end() - 1);
-    for (int i = 1; i < n_nodes; ++i) clist[fill[parent[i]]++] = i;
-  }
-  // word ids: leaf-flagged nodes in file order (:1432-1439); others keep 0 (Node())
-  std::vector<uint32_t> wordOf(n_nodes, 0);
-  int nw = 0;
-  for (int i = 1; i < n_nodes; ++i)
-    if (leaf[i]) wordOf[i] = (uint32_t)nw++;
-  // breadth-first renumbering: children of the node at position p occupy
-  // consecutive positions, in child order
-  std::vector<VocNodeInfo> info(n_nodes);
-  std::vector<int32_t> orig(n_nodes);
-  std::vector<uint8_t> ddesc((size_t)n_nodes * 32);
-  std::vector<uint32_t> dword(n_nodes);
-  std::vector<double> dweight(n_nodes);
-  orig[0] = 0;
-  int next = 1;
-  for (int p = 0; p < n_nodes; ++p) {
-    const int id = orig[p];
-    info[p].first = next;
-    info[p].count = ccount[id];
-    for (int c = cstart[id]; c < cstart[id + 1]; ++c) orig[next++] = clist[c];
-    memcpy(&ddesc[(size_t)p * 32], desc + (size_t)id * 32, 32);
-    dword[p] = wordOf[id];
-    dweight[p] = id == 0 ? 0.0 : weight[id];
-  }
-  if (next != n_nodes) return ORB_EINVAL;
-  V->nNodes = n_nodes;
-  V->nWords = nw;
-  hipStream_t s = V->stream;
-  orb_status_t st;
-  if ((st = upload(V->dInfo, info.data(), info.size() * sizeof(VocNodeInfo), s))) return st;
-  if ((st = upload(V->dDesc, ddesc.data(), ddesc.size(), s))) return st;
-  if ((st = upload(V->dWord, dword.data(), dword.size() * 4, s))) return st;
-  if ((st = upload(V->dWeight, dweight.data(), dweight.size() * 8, s))) return st;
-  if ((st = upload(V->dOrig, orig.data(), orig.size() * 4, s))) return st;
-  HIP_TRY(stream_wait(s));
-  return ORB_OK;
-}
-
-static orb_status_t vocab_new(int device, int k, int L, int scoring, int weighting,
-                              orb_vocabulary** out) {
-  orb_status_t st = check_device(device);
-  if (st) return st;
-  orb_vocabulary* V = new orb_vocabulary();
-  V->device = device;
-  V->k = k; V->L = L; V->scoring = scoring; V->weighting = weighting;
-  hipSetDevice(device);
-  if (create_own_stream(&V->stream) != hipSuccess) {
-    delete V;
-    return ORB_EDEVICE;
-  }
-  *out = V;
-  return ORB_OK;
-}
-
-orb_status_t orb_vocabulary_create(int device, int k, int L, int scoring, int weighting,
-                                   int n_nodes, const int32_t* parent, const uint8_t* leaf_flag,
-                                   const uint8_t* descriptors, const double* weights,
-                                   orb_vocabulary_t** out) {
-  if (!out) return ORB_EINVAL;
-  *out = nullptr;
-  // loadFromTextFile's header check (:1383)
-  if (k < 0 || k > 20 || L < 1 || L > 10 || scoring < 0 || scoring > 5 || weighting < 0 ||
-      weighting > 3 || n_nodes < 1 ||
-      (n_nodes > 1 && (!parent || !leaf_flag || !descriptors || !weights)))
-    return ORB_EINVAL;
-  orb_vocabulary* V = nullptr;
-  orb_status_t st = vocab_new(device, k, L, scoring, weighting, &V);
-  if (st) return st;
-  std::vector<int32_t> p0(1, 0);
-  std::vector<uint8_t> l0(1, 0), d0(32, 0);
-  std::vector<double> w0(1, 0.0);
-  st = n_nodes > 1 ? vocab_build(V, n_nodes, parent, leaf_flag, descriptors, weights)
-                   : vocab_build(V, 1, p0.data(), l0.data(), d0.data(), w0.data());
-  if (st) {
-    orb_vocabulary_destroy(V);
-    return st;
-  }
-  *out = V;
-  return ORB_OK;
-}
-
-// Text format of loadFromTextFile: "k L scoring weighting", then one line per
-// node "parent isLeaf d0 .. d31 weight" (descriptor bytes as integers,
-// FORB::fromString FORB.cpp:120-135).  Lines without a parent field are
-// skipped (the reference's eof loop turns a trailing empty line into a root
-// child with an uninitialised descriptor).
-orb_status_t orb_vocabulary_load_text(int device, const char* path, orb_vocabulary_t** out) {
-  if (!out || !path) return ORB_EINVAL;
-  *out = nullptr;
-  FILE* fp = fopen(path, "rb");
-  if (!fp) return ORB_EINVAL;
-  std::vector<char> text;
-  {
-    char buf[1 << 16];
-    size_t r;
-    while ((r = fread(buf, 1, sizeof(buf), fp)) > 0) text.insert(text.end(), buf, buf + r);
-    fclose(fp);
-  }
-  text.push_back('\0');
-  char* c = text.data();
-  char* eol = strchr(c, '\n');
-  int hdr[4];
-  for (int i = 0; i < 4; ++i) {
-    char* e;
-    const long v = strtol(c, &e, 10);
-    if (e == c || (eol && e > eol)) return ORB_EINVAL;
-    hdr[i] = (int)v;
-    c = e;
-  }
-  c = eol ? eol + 1 : c + strlen(c);
-  std::vector<int32_t> parent(1, 0);
-  std::vector<uint8_t> leaf(1, 0), desc(32, 0);
-  std::vector<double> weight(1, 0.0);
-  while (*c) {
-    char* le = strchr(c, '\n');
-    if (le) *le = '\0';
-    char* e;
-    const long pid = strtol(c, &e, 10);
-    if (e != c) {
-      c = e;
-      const long isLeaf = strtol(c, &e, 10);
-      c = e;
-      uint8_t d[32] = {0};
-      for (int i = 0; i < 32; ++i) {
-        const long v = strtol(c, &e, 10);
-        if (e == c) break;
-        d[i] = (uint8_t)v;
-        c = e;
-      }
-      const double w = strtod(c, &e);
-      parent.push_back((int32_t)pid);
-      leaf.push_back(isLeaf > 0);
-      desc.insert(desc.end(), d, d + 32);
-      weight.push_back(e == c ? 0.0 : w);
-    }
-    if (!le) break;
-    c = le + 1;
-  }
-  return orb_vocabulary_create(device, hdr[0], hdr[1], hdr[2], hdr[3], (int)parent.size(),
-                               parent.data(), leaf.data(), desc.data(), weight.data(), out);
-}
-
-void orb_vocabulary_destroy(orb_vocabulary_t* V) {
-  if (!V) return;
-  hipSetDevice(V->device);
-  hipStreamSynchronize(V->stream);
-  const hipStream_t stream = V->stream;
-  delete V;  // frees every buffer (DevBuf)
-  hipStreamDestroy(stream);
-}
-
-orb_status_t orb_vocabulary_info(const orb_vocabulary_t* V, int32_t* info6) {
-  if (!V || !info6) return ORB_EINVAL;
-  info6[0] = V->k; info6[1] = V->L; info6[2] = V->scoring; info6[3] = V->weighting;
-  info6[4] = V->nNodes; info6[5] = V->nWords;
-  return ORB_OK;
-}
-
-void* orb_vocabulary_stream(orb_vocabulary_t* V) { return V ? (void*)V->stream : nullptr; }
-
-static orb_status_t vocab_launch(orb_vocabulary* V, int n_frames, const int32_t* d_counts,
-                                 int n_single, const uint8_t* d_desc, int stride, int levelsup,
-                                 uint32_t* fword, double* fweight, uint32_t* fnode,
-                                 uint32_t* bw, double* bv, int32_t* nw, uint32_t* fvn,
-                                 int32_t* fvo, uint32_t* fvf, int32_t* nfv, hipStream_t s) {
-  int l2 = V->scoring == 1;
-  const int must = V->scoring != 5;  // ScoringObject.h:74-89
-  const int tf = V->weighting == 0 || V->weighting == 1;
-  if (V->nWords == 0) {  // empty(): v, fv cleared (:1136-1140)
-    HIP_TRY(hipMemsetAsync(nw, 0, (size_t)n_frames * 4, s));
-    HIP_TRY(hipMemsetAsync(nfv, 0, (size_t)n_frames * 4, s));
-    for (int f = 0; f < n_frames; ++f)
-      HIP_TRY(hipMemsetAsync(fvo + (size_t)f * (stride + 1), 0, 4, s));
-    return ORB_OK;
-  }
-  HIP_TRY(orb_k_voc_descend(V->dInfo.as<VocNodeInfo>(), V->dDesc.p, V->dWord.as<uint32_t>(),
-                            V->dWeight.as<double>(), V->dOrig.as<uint32_t>(), V->L - levelsup,
-                            d_desc, d_counts, n_single, stride, n_frames, fword, fweight, fnode,
-                            s));
-  HIP_TRY(orb_k_voc_vectors(fword, fweight, fnode, d_counts, n_single, stride, tf, must, l2,
-                            n_frames, bw, bv, nw, fvn, fvo, fvf, nfv, s));
-  return ORB_OK;
-}
-
-orb_status_t orb_vocabulary_transform(orb_vocabulary_t* V, int n, const uint8_t* desc,
-                                      int levelsup, uint32_t* bow_words, double* bow_values,
-                                      int32_t* n_words, uint32_t* fv_nodes, int32_t* fv_offs,
-                                      uint32_t* fv_feats, int32_t* n_fv_nodes,
-                                      uint32_t* feat_word, uint32_t* feat_node) {
-  if (!V || n < 0 || n > orb_k_voc_max_features() || (n > 0 && !desc) || !bow_words ||
-      !bow_values || !n_words || !fv_nodes || !fv_offs || !fv_feats || !n_fv_nodes)
-    return ORB_EINVAL;
-  if (n == 0 || V->nWords == 0) {
-    *n_words = 0;
-    *n_fv_nodes = 0;
-    fv_offs[0] = 0;
-    return ORB_OK;
-  }
-  std::lock_guard<std::mutex> g(V->mu);
-  hipSetDevice(V->device);
-  hipStream_t s = V->stream;
-  orb_status_t st;
-  const size_t N = (size_t)n;
-  if ((st = upload(V->dIn, desc, N * 32, s))) return st;
-  if ((st = V->dFWord.ensure(N * 4)) || (st = V->dFWeight.ensure(N * 8)) ||
-      (st = V->dFNode.ensure(N * 4)) || (st = V->dBowW.ensure(N * 4)) ||
-      (st = V->dBowV.ensure(N * 8)) || (st = V->dNW.ensure(16)) || (st = V->dFvN.ensure(N * 4)) ||
-      (st = V->dFvO.ensure((N + 1) * 4)) || (st = V->dFvF.ensure(N * 4)) ||
-      (st = V->dNFv.ensure(16)))
-    return st;
-  if ((st = vocab_launch(V, 1, nullptr, n, V->dIn.as<uint8_t>(), n, levelsup,
-                         V->dFWord.as<uint32_t>(), V->dFWeight.as<double>(),
-                         V->dFNode.as<uint32_t>(), V->dBowW.as<uint32_t>(),
-                         V->dBowV.as<double>(), V->dNW.as<int32_t>(), V->dFvN.as<uint32_t>(),
-                         V->dFvO.as<int32_t>(), V->dFvF.as<uint32_t>(), V->dNFv.as<int32_t>(), s)))
-    return st;
-  int32_t counts[2];
-  HIP_TRY(hipMemcpyAsync(&counts[0], V->dNW.p, 4, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipMemcpyAsync(&counts[1], V->dNFv.p, 4, hipMemcpyDeviceToHost, s));
-  HIP_TRY(stream_wait(s));
-  *n_words = counts[0];
-  *n_fv_nodes = counts[1];
-  HIP_TRY(hipMemcpyAsync(bow_words, V->dBowW.p, (size_t)counts[0] * 4, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipMemcpyAsync(bow_values, V->dBowV.p, (size_t)counts[0] * 8, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipMemcpyAsync(fv_nodes, V->dFvN.p, (size_t)counts[1] * 4, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipMemcpyAsync(fv_offs, V->dFvO.p, (size_t)(counts[1] + 1) * 4, hipMemcpyDeviceToHost,
-                         s));
-  HIP_TRY(stream_wait(s));
-  const int nfeat = fv_offs[counts[1]];
-  if (nfeat > 0)
-    HIP_TRY(hipMemcpyAsync(fv_feats, V->dFvF.p, (size_t)nfeat * 4, hipMemcpyDeviceToHost, s));
-  if (feat_word) HIP_TRY(hipMemcpyAsync(feat_word, V->dFWord.p, N * 4, hipMemcpyDeviceToHost, s));
-  if (feat_node) HIP_TRY(hipMemcpyAsync(feat_node, V->dFNode.p, N * 4, hipMemcpyDeviceToHost, s));
-  HIP_TRY(stream_wait(s));
-  return ORB_OK;
-}
-
-orb_status_t orb_vocabulary_transform_batch(orb_vocabulary_t* V, int n_frames,
-                                            const int32_t* d_counts, const uint8_t* d_desc,
-                                            int stride, int levelsup, uint32_t* d_feat_word,
-                                            double* d_feat_weight, uint32_t* d_feat_node,
-                                            uint32_t* d_bow_words, double* d_bow_values,
-                                            int32_t* d_n_words, uint32_t* d_fv_nodes,
-                                            int32_t* d_fv_offs, uint32_t* d_fv_feats,
-                                            int32_t* d_n_fv_nodes, void* stream) {
-  if (!V || n_frames < 0 || stride <= 0 || stride > orb_k_voc_max_features()) return ORB_EINVAL;
-  if (n_frames == 0) return ORB_OK;
-  if (!d_counts || !d_desc || !d_feat_word || !d_feat_weight || !d_feat_node || !d_bow_words ||
-      !d_bow_values || !d_n_words || !d_fv_nodes || !d_fv_offs || !d_fv_feats || !d_n_fv_nodes)
-    return ORB_EINVAL;
-  hipSetDevice(V->device);
-  return vocab_launch(V, n_frames, d_counts, 0, d_desc, stride, levelsup, d_feat_word,
-                      d_feat_weight, d_feat_node, d_bow_words, d_bow_values, d_n_words,
-                      d_fv_nodes, d_fv_offs, d_fv_feats, d_n_fv_nodes,
-                      stream ? (hipStream_t)stream : V->stream);
-}
-
-// ------------------------------------------------- place recognition: score
-// TemplatedVocabulary::score -> ScoringObject.cpp:23-311 (placerec_kernels.hip).
-static bool bow_vectors_valid(int n, const int32_t* offs, const uint32_t* words) {
-  if (offs[0] < 0) return false;
-  for (int p = 0; p < n; ++p) {
-    if (offs[p + 1] < offs[p]) return false;
-    for (int i = offs[p] + 1; i < offs[p + 1]; ++i)
-      if (words[i] <= words[i - 1]) return false;  // std::map keys: strictly ascending
-  }
-  return true;
-}
-
-orb_status_t orb_vocabulary_score(orb_vocabulary_t* V, int n_pairs, const int32_t* a_offs,
-                                  const uint32_t* a_words, const double* a_values,
-                                  const int32_t* b_offs, const uint32_t* b_words,
-                                  const double* b_values, double* out) {
-  if (!V || n_pairs < 0 || V->scoring == ORB_VOC_KL) return ORB_EINVAL;
-  if (n_pairs == 0) return ORB_OK;
-  if (!a_offs || !b_offs || !out) return ORB_EINVAL;
-  const size_t na = (size_t)std::max(a_offs[n_pairs], 0), nb = (size_t)std::max(b_offs[n_pairs], 0);
-  if ((na && (!a_words || !a_values)) || (nb && (!b_words || !b_values))) return ORB_EINVAL;
-  if (!bow_vectors_valid(n_pairs, a_offs, a_words) || !bow_vectors_valid(n_pairs, b_offs, b_words))
-    return ORB_EINVAL;
-  std::lock_guard<std::mutex> g(V->mu);
-  hipSetDevice(V->device);
-  hipStream_t s = V->stream;
-  orb_status_t st;
-  DevBuf* B = V->dScore;
-  const size_t no = (size_t)(n_pairs + 1) * 4;
-  if ((st = upload(B[0], a_offs, no, s)) || (st = upload(B[1], a_words, na * 4, s)) ||
-      (st = upload(B[2], a_values, na * 8, s)) || (st = upload(B[3], b_offs, no, s)) ||
-      (st = upload(B[4], b_words, nb * 4, s)) || (st = upload(B[5], b_values, nb * 8, s)) ||
-      (st = B[6].ensure((size_t)n_pairs * 8)))
-    return st;
-  HIP_TRY(orb_k_bow_score(V->scoring, n_pairs, B[0].as<int32_t>(), B[1].as<uint32_t>(),
-                          B[2].as<double>(), B[3].as<int32_t>(), B[4].as<uint32_t>(),
-                          B[5].as<double>(), B[6].as<double>(), s));
-  HIP_TRY(hipMemcpyAsync(out, B[6].p, (size_t)n_pairs * 8, hipMemcpyDeviceToHost, s));
-  HIP_TRY(stream_wait(s));
-  return ORB_OK;
-}
-
-orb_status_t orb_vocabulary_score_batch(orb_vocabulary_t* V, int n_pairs, const int32_t* d_a_offs,
-                                        const uint32_t* d_a_words, const double* d_a_values,
-                                        const int32_t* d_b_offs, const uint32_t* d_b_words,
-                                        const double* d_b_values, double* d_out, void* stream) {
-  if (!V || n_pairs < 0 || V->scoring == ORB_VOC_KL) return ORB_EINVAL;
-  if (n_pairs == 0) return ORB_OK;
-  if (!d_a_offs || !d_a_words || !d_a_values || !d_b_offs || !d_b_words || !d_b_values || !d_out)
-    return ORB_EINVAL;
-  hipSetDevice(V->device);
-  HIP_TRY(orb_k_bow_score(V->scoring, n_pairs, d_a_offs, d_a_words, d_a_values, d_b_offs,
-                          d_b_words, d_b_values, d_out, stream ? (hipStream_t)stream : V->stream));
-  return ORB_OK;
-}
-
-// -------------------------------------- place recognition: KeyFrameDatabase
-// src/KeyFrameDatabase.cc over keyframe ids.  A keyframe takes the next slot
-// when it is added; slots are never reused before clear(), so the slot index
-// is the add sequence number the list order needs (placerec_kernels.hip).
-// The host keeps what resolves ids (id -> slot, who names whom as a
-// neighbour); BowVectors, covisibility slots and scores stay on the device.
-struct orb_kf_database {
-  orb_vocabulary* voc = nullptr;
-  int device = 0;
-  hipStream_t stream = nullptr;
-  std::mutex mu;
-  // host side of the slot table
-  std::vector<int64_t> slotId;
-  std::vector<uint8_t> slotLive;
-  std::vector<std::array<int64_t, PR_NEIGH>> neighIds;
-  std::vector<int> neighN;
-  std::unordered_map<int64_t, int> slotOf;  // live keyframes
-  // neighbour id -> (slot, position) of every live keyframe that names it
-  std::unordered_multimap<int64_t, std::pair<int, int>> namedBy;
-  size_t entries = 0;  // BowVector entries stored (erased ones included)
-  int nLive = 0;
-  // device: the database (grown with their contents kept)
-  DevBuf dWords, dValues, dSlots, dNeigh, dIds, dStored[2];  // [0] mRelocScore, [1] mLoopScore
-  // device: per-query scratch
-  DevBuf dQW, dQV, dConnSlots, dConn, dCommon, dFirst, dFirstPos, dKeys, dList, dHdr, dScored,
-      dAcc, dBest, dValid, dOut;
-  uint64_t lastId[2] = {0, 0};
-  int lastKind = -1, lastSlots = 0, lastN = 0;
-  bool argsValid = false;
-  PrQueryArgs args;
-};
-
-// Grows b to hold `need` bytes, keeping its first `used` bytes.
-static orb_status_t grow_keep(DevBuf& b, size_t used, size_t need, hipStream_t s) {
-  if (need <= b.bytes) return ORB_OK;
-  const size_t cap = std::max<size_t>(std::max(need, b.bytes * 2), 4096);
-  void* p = nullptr;
-  if (hipMalloc(&p, cap) != hipSuccess) return ORB_ENOMEM;
-  if (used && b.p) {
-    hipError_t e = hipMemcpyAsync(p, b.p, used, hipMemcpyDeviceToDevice, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) {
-      hipFree(p);
-      return ORB_EDEVICE;
-    }
-  }
-  if (b.p) hipFree(b.p);
-  b.p = p;
-  b.bytes = cap;
-  return ORB_OK;
-}
-
-static void kfdb_unname(orb_kf_database* D, int slot) {
-  for (int j = 0; j < D->neighN[slot]; ++j) {
-    auto range = D->namedBy.equal_range(D->neighIds[slot][j]);
-    for (auto it = range.first; it != range.second; ++it)
-      if (it->second.first == slot && it->second.second == j) {
-        D->namedBy.erase(it);
-        break;
-      }
-  }
-  D->neighN[slot] = 0;
-}
-
-// Every live keyframe that names `id` as a neighbour now points at `slot` (-1: absent).
-static orb_status_t kfdb_patch_neighbours(orb_kf_database* D, int64_t id, const int32_t* slot,
-                                          hipStream_t s) {
-  auto range = D->namedBy.equal_range(id);
-  for (auto it = range.first; it != range.second; ++it) {
-    const size_t at = (size_t)it->second.first * PR_NEIGH + it->second.second;
-    HIP_TRY(hipMemcpyAsync(D->dNeigh.as<int32_t>() + at, slot, 4, hipMemcpyHostToDevice, s));
-  }
-  return ORB_OK;
-}
-
-orb_status_t orb_kf_database_create(orb_vocabulary_t* V, orb_kf_database_t** out) {
-  if (!out) return ORB_EINVAL;
-  *out = nullptr;
-  if (!V || V->scoring == ORB_VOC_KL) return ORB_EINVAL;
-  orb_kf_database* D = new orb_kf_database();
-  D->voc = V;
-  D->device = V->device;
-  hipSetDevice(D->device);
-  if (create_own_stream(&D->stream) != hipSuccess) {
-    delete D;
-    return ORB_EDEVICE;
-  }
-  *out = D;
-  return ORB_OK;
-}
-
-void orb_kf_database_destroy(orb_kf_database_t* D) {
-  if (!D) return;
-  hipSetDevice(D->device);
-  hipStreamSynchronize(D->stream);
-  const hipStream_t stream = D->stream;
-  delete D;  // frees every buffer (DevBuf)
-  hipStreamDestroy(stream);
-}
-
-orb_status_t orb_kf_database_clear(orb_kf_database_t* D) {
-  if (!D) return ORB_EINVAL;
-  std::lock_guard<std::mutex> g(D->mu);
-  D->slotId.clear();
-  D->slotLive.clear();
-  D->neighIds.clear();
-  D->neighN.clear();
-  D->slotOf.clear();
-  D->namedBy.clear();
-  D->entries = 0;
-  D->nLive = 0;
-  D->lastKind = -1;
-  D->lastN = D->lastSlots = 0;
-  D->argsValid = false;
-  return ORB_OK;
-}
-
-int orb_kf_database_size(orb_kf_database_t* D) {
-  if (!D) return ORB_EINVAL;
-  std::lock_guard<std::mutex> g(D->mu);
-  return D->nLive;
-}
-
-orb_status_t orb_kf_database_add(orb_kf_database_t* D, int64_t kf_id, int n_words,
-                                 const uint32_t* words, const double* values) {
-  if (!D || n_words < 0 || (n_words > 0 && (!words || !values))) return ORB_EINVAL;
-  for (int i = 0; i < n_words; ++i)
-    if (words[i] >= (uint32_t)D->voc->nWords || (i > 0 && words[i] <= words[i - 1]))
-      return ORB_EINVAL;
-  std::lock_guard<std::mutex> g(D->mu);
-  if (D->slotOf.count(kf_id) || D->slotId.size() >= (size_t)0x7FFFFFFF) return ORB_EINVAL;
-  hipSetDevice(D->device);
-  hipStream_t s = D->stream;
-  const size_t slot = D->slotId.size(), e0 = D->entries, e1 = e0 + (size_t)n_words;
-  orb_status_t st;
-  if ((st = grow_keep(D->dWords, e0 * 4, e1 * 4, s)) ||
-      (st = grow_keep(D->dValues, e0 * 8, e1 * 8, s)) ||
-      (st = grow_keep(D->dSlots, slot * sizeof(PrSlot), (slot + 1) * sizeof(PrSlot), s)) ||
-      (st = grow_keep(D->dNeigh, slot * PR_NEIGH * 4, (slot + 1) * PR_NEIGH * 4, s)) ||
-      (st = grow_keep(D->dIds, slot * 8, (slot + 1) * 8, s)) ||
-      (st = grow_keep(D->dStored[0], slot * 4, (slot + 1) * 4, s)) ||
-      (st = grow_keep(D->dStored[1], slot * 4, (slot + 1) * 4, s)))
-    return st;
-  const PrSlot rec{(long long)e0, n_words, 1};
-  int32_t none[PR_NEIGH];
-  for (int32_t& v : none) v = -1;
-  const long long id = kf_id;
-  const int32_t self = (int32_t)slot;
-  if (n_words) {
-    HIP_TRY(hipMemcpyAsync(D->dWords.as<uint32_t>() + e0, words, (size_t)n_words * 4,
-                           hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(D->dValues.as<double>() + e0, values, (size_t)n_words * 8,
-                           hipMemcpyHostToDevice, s));
-  }
-  HIP_TRY(hipMemcpyAsync(D->dSlots.as<PrSlot>() + slot, &rec, sizeof(rec),
-                         hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(D->dNeigh.as<int32_t>() + slot * PR_NEIGH, none, sizeof(none),
-                         hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemcpyAsync(D->dIds.as<long long>() + slot, &id, 8, hipMemcpyHostToDevice, s));
-  HIP_TRY(hipMemsetAsync(D->dStored[0].as<float>() + slot, 0, 4, s));  // never scored: 0.0f
-  HIP_TRY(hipMemsetAsync(D->dStored[1].as<float>() + slot, 0, 4, s));
-  if ((st = kfdb_patch_neighbours(D, kf_id, &self, s))) return st;
-  HIP_TRY(hipStreamSynchronize(s));
-  D->slotId.push_back(kf_id);
-  D->slotLive.push_back(1);
-  D->neighIds.emplace_back();
-  D->neighN.push_back(0);
-  D->slotOf[kf_id] = (int)slot;
-  D->entries = e1;
-  ++D->nLive;
-  D->argsValid = false;
-  return ORB_OK;
-}
-
-orb_status_t orb_kf_database_erase(orb_kf_database_t* D, int64_t kf_id) {
-  if (!D) return ORB_EINVAL;
-  std::lock_guard<std::mutex> g(D->mu);
-  auto it = D->slotOf.find(kf_id);
-  if (it == D->slotOf.end()) return ORB_OK;
-  hipSetDevice(D->device);
-  hipStream_t s = D->stream;
-  const int slot = it->second;
-  const int32_t dead = 0, none = -1;
-  HIP_TRY(hipMemcpyAsync(&D->dSlots.as<PrSlot>()[slot].live, &dead, 4, hipMemcpyHostToDevice,
-                         s));
-  orb_status_t st = kfdb_patch_neighbours(D, kf_id, &none, s);
-  if (st) return st;
-  HIP_TRY(hipStreamSynchronize(s));
-  kfdb_unname(D, slot);
-  D->slotLive[slot] = 0;
-  D->slotOf.erase(it);
-  --D->nLive;
-  D->argsValid = false;
-  return ORB_OK;
-}
-
-orb_status_t orb_kf_database_set_covisibility(orb_kf_database_t* D, int64_t kf_id, int n,
-                                              const int64_t* neighbour_ids) {
-  if (!D || n < 0 || n > PR_NEIGH || (n > 0 && !neighbour_ids)) return ORB_EINVAL;
-  std::lock_guard<std::mutex> g(D->mu);
-  auto it = D->slotOf.find(kf_id);
-  if (it == D->slotOf.end()) return ORB_EINVAL;
-  hipSetDevice(D->device);
-  hipStream_t s = D->stream;
-  const int slot = it->second;
-  int32_t resolved[PR_NEIGH];
-  for (int j = 0; j < PR_NEIGH; ++j) {
-    resolved[j] = -1;
-    if (j < n) {
-      auto f = D->slotOf.find(neighbour_ids[j]);
-      if (f != D->slotOf.end()) resolved[j] = f->second;
-    }
-  }
-  HIP_TRY(hipMemcpyAsync(D->dNeigh.as<int32_t>() + (size_t)slot * PR_NEIGH, resolved,
-                         sizeof(resolved), hipMemcpyHostToDevice, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  kfdb_unname(D, slot);
-  for (int j = 0; j < n; ++j) {
-    D->neighIds[slot][j] = neighbour_ids[j];
-    D->namedBy.emplace(neighbour_ids[j], std::make_pair(slot, j));
-  }
-  D->neighN[slot] = n;
-  D->argsValid = false;
-  return ORB_OK;
-}
-
-static orb_status_t kfdb_query(orb_kf_database* D, int kind, uint64_t query_id, int n_words,
-                               const uint32_t* words, const double* values, int n_connected,
-                               const int64_t* connected_ids, float min_score, int64_t* out_ids,
-                               int capacity, int* n_out) {
-  if (!D || !n_out || n_words < 0 || (n_words > 0 && (!words || !values)) || capacity < 0 ||
-      (capacity > 0 && !out_ids) || n_connected < 0 || (n_connected > 0 && !connected_ids))
-    return ORB_EINVAL;
-  for (int i = 0; i < n_words; ++i)
-    if (words[i] >= (uint32_t)D->voc->nWords || (i > 0 && words[i] <= words[i - 1]))
-      return ORB_EINVAL;
-  std::lock_guard<std::mutex> g(D->mu);
-  // mnRelocQuery / mnLoopQuery start at 0 and ids are unique in the reference
-  if (query_id == 0 || query_id == D->lastId[kind]) return ORB_EINVAL;
-  D->lastId[kind] = query_id;
-  D->lastKind = kind;
-  D->lastN = 0;
-  D->argsValid = false;
-  *n_out = 0;
-  const int nSlots = (int)D->slotId.size();
-  D->lastSlots = nSlots;
-  if (nSlots == 0 || n_words == 0) return ORB_OK;  // nothing shares a word (:111, :238)
-  hipSetDevice(D->device);
-  hipStream_t s = D->stream;
-  std::vector<int32_t> conn;
-  for (int i = 0; i < n_connected; ++i) {
-    auto f = D->slotOf.find(connected_ids[i]);
-    if (f != D->slotOf.end()) conn.push_back(f->second);
-  }
-  const size_t N = (size_t)nSlots;
-  orb_status_t st;
-  if ((st = upload(D->dQW, words, (size_t)n_words * 4, s)) ||
-      (st = upload(D->dQV, values, (size_t)n_words * 8, s)) ||
-      (st = upload(D->dConnSlots, conn.data(), conn.size() * 4, s)) ||
-      (st = D->dConn.ensure(N)) || (st = D->dCommon.ensure(N * 4)) ||
-      (st = D->dFirst.ensure(N * 4)) || (st = D->dFirstPos.ensure(N * 4)) ||
-      (st = D->dKeys.ensure(std::max<size_t>(orb_k_db_key_scratch(nSlots), 1) * 8)) ||
-      (st = D->dList.ensure(N * 4)) || (st = D->dHdr.ensure(16)) || (st = D->dScored.ensure(N)) ||
-      (st = D->dAcc.ensure(N * 4)) || (st = D->dBest.ensure(N * 4)) ||
-      (st = D->dValid.ensure(N)) || (st = D->dOut.ensure(N * 8)))
-    return st;
-  PrQueryArgs& A = D->args;
-  A.type = D->voc->scoring;
-  A.loop = kind;
-  A.minScore = min_score;
-  A.nSlots = nSlots;
-  A.nq = n_words;
-  A.nConnected = (int)conn.size();
-  A.slots = D->dSlots.as<PrSlot>();
-  A.words = D->dWords.as<uint32_t>();
-  A.values = D->dValues.as<double>();
-  A.neigh = D->dNeigh.as<int32_t>();
-  A.ids = D->dIds.as<long long>();
-  A.stored = D->dStored[kind].as<float>();
-  A.qWords = D->dQW.as<uint32_t>();
-  A.qValues = D->dQV.as<double>();
-  A.connSlots = D->dConnSlots.as<int32_t>();
-  A.connected = D->dConn.as<uint8_t>();
-  A.common = D->dCommon.as<int32_t>();
-  A.first = D->dFirst.as<uint32_t>();
-  A.firstPos = D->dFirstPos.as<int32_t>();
-  A.keys = D->dKeys.as<unsigned long long>();
-  A.list = D->dList.as<uint32_t>();
-  A.hdr = D->dHdr.as<int32_t>();
-  A.scored = D->dScored.as<uint8_t>();
-  A.acc = D->dAcc.as<float>();
-  A.best = D->dBest.as<uint32_t>();
-  A.valid = D->dValid.as<uint8_t>();
-  A.out = D->dOut.as<long long>();
-  A.stage = -1;
-  HIP_TRY(orb_k_db_query(&A, s));
-  int32_t hdr[4];
-  HIP_TRY(hipMemcpyAsync(hdr, D->dHdr.p, sizeof(hdr), hipMemcpyDeviceToHost, s));
-  HIP_TRY(stream_wait(s));
-  D->lastN = hdr[0];
-  D->argsValid = true;
-  *n_out = hdr[3];
-  if (hdr[3] > capacity) return ORB_ECAPACITY;
-  if (hdr[3] > 0) {
-    HIP_TRY(hipMemcpyAsync(out_ids, D->dOut.p, (size_t)hdr[3] * 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(stream_wait(s));
-  }
-  return ORB_OK;
-}
-
-orb_status_t orb_kf_database_detect_relocalization(orb_kf_database_t* D, uint64_t query_id,
-                                                   int n_words, const uint32_t* words,
-                                                   const double* values, int64_t* out_ids,
-                                                   int capacity, int* n_out) {
-  return kfdb_query(D, 0, query_id, n_words, words, values, 0, nullptr, 0.0f, out_ids, capacity,
-                    n_out);
-}
-
-orb_status_t orb_kf_database_detect_loop(orb_kf_database_t* D, uint64_t query_id, int n_words,
-                                         const uint32_t* words, const double* values,
-                                         int n_connected, const int64_t* connected_ids,
-                                         float min_score, int64_t* out_ids, int capacity,
-                                         int* n_out) {
-  return kfdb_query(D, 1, query_id, n_words, words, values, n_connected, connected_ids, min_score,
-                    out_ids, capacity, n_out);
-}
-
-orb_status_t orb_kf_database_last_query(orb_kf_database_t* D, int64_t* ids, int32_t* common,
-                                        float* scores, uint8_t* scored, int capacity, int* n) {
-  if (!D || !n || capacity < 0) return ORB_EINVAL;
-  std::lock_guard<std::mutex> g(D->mu);
-  const int L = D->lastKind < 0 ? 0 : D->lastN;
-  *n = L;
-  if (L > capacity) return ORB_ECAPACITY;
-  if (L == 0) return ORB_OK;
-  hipSetDevice(D->device);
-  hipStream_t s = D->stream;
-  const size_t N = (size_t)D->lastSlots;
-  std::vector<uint32_t> list(L);
-  std::vector<int32_t> cm(N);
-  std::vector<float> sc(N);
-  HIP_TRY(hipMemcpyAsync(list.data(), D->dList.p, (size_t)L * 4, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipMemcpyAsync(cm.data(), D->dCommon.p, N * 4, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipMemcpyAsync(sc.data(), D->dStored[D->lastKind].p, N * 4, hipMemcpyDeviceToHost, s));
-  if (scored) HIP_TRY(hipMemcpyAsync(scored, D->dScored.p, (size_t)L, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  for (int i = 0; i < L; ++i) {
-    const uint32_t slot = list[i];
-    if (slot >= N) return ORB_EDEVICE;
-    if (ids) ids[i] = D->slotId[slot];
-    if (common) common[i] = cm[slot];
-    if (scores) scores[i] = sc[slot];
-  }
-  return ORB_OK;
-}
-
-orb_status_t orb_kf_database_profile(orb_kf_database_t* D, int stage, int reps, double* total_ms,
-                                     const char** name) {
-  static const char* const names[] = {"k_db_common", "k_db_list", "k_db_score", "k_db_accumulate",
-                                      "k_db_select"};
-  if (!D || stage < 0 || stage > 4 || reps < 1 || !total_ms) return ORB_EINVAL;
-  std::lock_guard<std::mutex> g(D->mu);
-  if (!D->argsValid) return ORB_EINVAL;
-  hipSetDevice(D->device);
-  hipStream_t s = D->stream;
-  hipEvent_t e0, e1;
-  HIP_TRY(hipEventCreate(&e0));
-  HIP_TRY(hipEventCreate(&e1));
-  PrQueryArgs A = D->args;
-  A.stage = stage;
-  hipError_t e = hipEventRecord(e0, s);
-  for (int i = 0; i < reps && e == hipSuccess; ++i) e = orb_k_db_query(&A, s);
-  if (e == hipSuccess) e = hipEventRecord(e1, s);
-  if (e == hipSuccess) e = hipEventSynchronize(e1);
-  float ms = 0.f;
-  if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
-  hipEventDestroy(e0);
-  hipEventDestroy(e1);
-  HIP_TRY(e);
-  *total_ms = ms;
-  if (name) *name = names[stage];
-  return ORB_OK;
+  return call.finish();
 }
 
 // ------------------------------------------------------------ undistortion
@@ -3618,16 +2445,13 @@ orb_status_t orb_undistort_points(orb_matcher_t* m, int n, const float* xy, cons
   orb_status_t st = undistort_params(K, dist, n_dist, P);
   if (st) return st;
   if (n == 0) return ORB_OK;
-  std::lock_guard<std::mutex> g(m->mu);
-  hipSetDevice(m->device);
-  hipStream_t s = m->stream;
-  CallOrder order(m->evLast, &m->lastStream, s);
-  if (order.status) return order.status;
+  MatcherCall call(m);
+  if (call.status) return call.status;
+  const hipStream_t s = call.s;
   if ((st = upload(m->dA, xy, (size_t)n * 8, s)) || (st = m->dB.ensure((size_t)n * 8))) return st;
   HIP_TRY(orb_k_undistort_points(&P, n, m->dA.as<float>(), m->dB.as<float>(), s));
   HIP_TRY(hipMemcpyAsync(out_xy, m->dB.p, (size_t)n * 8, hipMemcpyDeviceToHost, s));
-  HIP_TRY(stream_wait(s));
-  return ORB_OK;
+  return call.finish();
 }
 
 orb_status_t orb_undistort_keypoints(orb_matcher_t* m, int n, const orb_keypoint_t* keys,
@@ -3642,17 +2466,14 @@ orb_status_t orb_undistort_keypoints(orb_matcher_t* m, int n, const orb_keypoint
     if (keys_un != keys) memmove(keys_un, keys, (size_t)n * sizeof(orb_keypoint_t));
     return ORB_OK;
   }
-  std::lock_guard<std::mutex> g(m->mu);
-  hipSetDevice(m->device);
-  hipStream_t s = m->stream;
-  CallOrder order(m->evLast, &m->lastStream, s);
-  if (order.status) return order.status;
+  MatcherCall call(m);
+  if (call.status) return call.status;
+  const hipStream_t s = call.s;
   const size_t bytes = (size_t)n * sizeof(orb_keypoint_t);
   if ((st = upload(m->dA, keys, bytes, s)) || (st = m->dB.ensure(bytes))) return st;
   HIP_TRY(orb_k_undistort_keys(&P, 1, nullptr, n, n, m->dA.p, m->dB.p, 0, s));
   HIP_TRY(hipMemcpyAsync(keys_un, m->dB.p, bytes, hipMemcpyDeviceToHost, s));
-  HIP_TRY(stream_wait(s));
-  return ORB_OK;
+  return call.finish();
 }
 
 orb_status_t orb_compute_image_bounds(orb_matcher_t* m, int cols, int rows, const float* K,
@@ -3733,11 +2554,9 @@ orb_status_t orb_stereo_from_rgbd(orb_matcher_t* m, int n, const orb_keypoint_t*
                                 depth, P);
   if (st) return st;
   if (n == 0) return ORB_OK;
-  std::lock_guard<std::mutex> g(m->mu);
-  hipSetDevice(m->device);
-  hipStream_t s = m->stream;
-  CallOrder order(m->evLast, &m->lastStream, s);
-  if (order.status) return order.status;
+  MatcherCall call(m);
+  if (call.status) return call.status;
+  const hipStream_t s = call.s;
   const size_t kb = (size_t)n * sizeof(orb_keypoint_t);
   if ((st = upload(m->dA, keys, kb, s)) || (st = upload(m->dB, keys_un, kb, s)) ||
       (st = upload(m->dIn, depth, (size_t)rows * row_bytes, s)) ||
@@ -3748,9 +2567,7 @@ orb_status_t orb_stereo_from_rgbd(orb_matcher_t* m, int n, const orb_keypoint_t*
                                  m->dB.as<orb_keypoint_t>(), m->dIn.p, out, out + n, s));
   HIP_TRY(hipMemcpyAsync(u_right, out, (size_t)n * 4, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipMemcpyAsync(depth_out, out + n, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-  HIP_TRY(stream_wait(s));
-  order.settled();
-  return ORB_OK;
+  return call.finish();
 }
 
 orb_status_t orb_stereo_from_rgbd_batch(orb_matcher_t* m, int n_frames, const int32_t* d_n,
@@ -3792,11 +2609,9 @@ orb_status_t orb_unproject_stereo(orb_matcher_t* m, int n, const orb_keypoint_t*
     return ORB_EINVAL;
   if (n == 0) return ORB_OK;
   const UnprojectParams P = unproject_params(1, n, cam);
-  std::lock_guard<std::mutex> g(m->mu);
-  hipSetDevice(m->device);
-  hipStream_t s = m->stream;
-  CallOrder order(m->evLast, &m->lastStream, s);
-  if (order.status) return order.status;
+  MatcherCall call(m);
+  if (call.status) return call.status;
+  const hipStream_t s = call.s;
   orb_status_t st;
   if ((st = upload(m->dA, keys_un, (size_t)n * sizeof(orb_keypoint_t), s)) ||
       (st = upload(m->dB, depth, (size_t)n * 4, s)) ||
@@ -3809,9 +2624,7 @@ orb_status_t orb_unproject_stereo(orb_matcher_t* m, int n, const orb_keypoint_t*
                                  m->dPose.as<orb_pose_t>(), out, dv, s));
   HIP_TRY(hipMemcpyAsync(x3d, out, (size_t)n * 12, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipMemcpyAsync(valid, dv, (size_t)n, hipMemcpyDeviceToHost, s));
-  HIP_TRY(stream_wait(s));
-  order.settled();
-  return ORB_OK;
+  return call.finish();
 }
 
 orb_status_t orb_unproject_stereo_batch(orb_matcher_t* m, int n_frames, const int32_t* d_n,
@@ -3840,11 +2653,9 @@ orb_status_t orb_close_points(orb_matcher_t* m, int n, const float* depth,
     return ORB_EINVAL;
   memset(counts, 0, sizeof(*counts));
   if (n == 0) return ORB_OK;
-  std::lock_guard<std::mutex> g(m->mu);
-  hipSetDevice(m->device);
-  hipStream_t s = m->stream;
-  CallOrder co(m->evLast, &m->lastStream, s);
-  if (co.status) return co.status;
+  MatcherCall call(m);
+  if (call.status) return call.status;
+  const hipStream_t s = call.s;
   orb_status_t st;
   // dOut: order (n x 4), counts (16), create (n)
   if ((st = upload(m->dA, depth, (size_t)n * 4, s)) ||
@@ -3864,9 +2675,7 @@ orb_status_t orb_close_points(orb_matcher_t* m, int n, const float* depth,
   HIP_TRY(hipMemcpyAsync(order, dOrder, (size_t)n * 4, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipMemcpyAsync(create, dCreate, (size_t)n, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipMemcpyAsync(counts, dCounts, sizeof(*counts), hipMemcpyDeviceToHost, s));
-  HIP_TRY(stream_wait(s));
-  co.settled();
-  return ORB_OK;
+  return call.finish();
 }
 
 orb_status_t orb_close_points_batch(orb_matcher_t* m, int n_frames, const int32_t* d_n,
@@ -3947,11 +2756,9 @@ orb_status_t orb_pose_optimization(orb_matcher_t* m, int n, const orb_keypoint_t
              (const uint8_t*)points + (size_t)point_index[i] * point_stride_bytes, 12);
       idx[i] = i;
     }
-  std::lock_guard<std::mutex> g(m->mu);
-  hipSetDevice(m->device);
-  hipStream_t s = m->stream;
-  CallOrder co(m->evLast, &m->lastStream, s);
-  if (co.status) return co.status;
+  MatcherCall call(m);
+  if (call.status) return call.status;
+  const hipStream_t s = call.s;
   orb_status_t st;
   // dPoOut: pose in (64), pose out (64), info (16), outlier (n)
   if ((st = upload(m->dPoKeys, keys_un, (size_t)n * sizeof(orb_keypoint_t), s)) ||
@@ -3976,9 +2783,7 @@ orb_status_t orb_pose_optimization(orb_matcher_t* m, int n, const orb_keypoint_t
   HIP_TRY(hipMemcpyAsync(pose_out, dOutPose, sizeof(orb_pose_t), hipMemcpyDeviceToHost, s));
   HIP_TRY(hipMemcpyAsync(outlier, dOutlier, (size_t)n, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipMemcpyAsync(info, dInfo, sizeof(*info), hipMemcpyDeviceToHost, s));
-  HIP_TRY(stream_wait(s));
-  co.settled();
-  return ORB_OK;
+  return call.finish();
 }
 
 orb_status_t orb_pose_optimization_batch(orb_matcher_t* m, int n_problems,
@@ -4000,11 +2805,9 @@ orb_status_t orb_pose_optimization_batch(orb_matcher_t* m, int n_problems,
   if (!d_nkeys || !d_keys_un || !d_point_index || !d_points || !d_pose_in || !d_pose_out ||
       !d_outlier || !d_info)
     return ORB_EINVAL;
-  std::lock_guard<std::mutex> g(m->mu);
-  hipSetDevice(m->device);
-  hipStream_t s = stream ? (hipStream_t)stream : m->stream;
-  CallOrder co(m->evLast, &m->lastStream, s);
-  if (co.status) return co.status;
+  MatcherCall call(m, stream);
+  if (call.status) return call.status;
+  const hipStream_t s = call.s;
   const size_t sb = orb_k_pose_optimization_scratch(n_problems, kp_stride);
   orb_status_t st;
   if (sb && (st = m->dPoRecs.ensure(sb))) return st;
@@ -4038,11 +2841,9 @@ orb_status_t orb_match_projection_frame_batch(
       !d_last_nkeys || !d_last_point_index || !d_points || !d_mp_desc || !d_kp_match || !d_info ||
       n_problems > 65535)
     return ORB_EINVAL;
-  std::lock_guard<std::mutex> g(m->mu);
-  hipSetDevice(m->device);
-  hipStream_t s = stream ? (hipStream_t)stream : m->stream;
-  CallOrder order(m->evLast, &m->lastStream, s);
-  if (order.status) return order.status;
+  MatcherCall call(m, stream);
+  if (call.status) return call.status;
+  const hipStream_t s = call.s;
   orb_status_t st;
   if ((st = m->dCellStart.ensure((size_t)n_problems * (ORB_GRID_COLS * ORB_GRID_ROWS + 1) * 4)))
     return st;
@@ -4181,11 +2982,9 @@ orb_status_t orb_update_local_map_batch(
       !d_n_local_kf || !d_local_index || !d_mps || !d_mp_desc || !d_nmps || !d_locked ||
       !d_info)
     return ORB_EINVAL;
-  std::lock_guard<std::mutex> g(m->mu);
-  hipSetDevice(m->device);
-  hipStream_t s = stream ? (hipStream_t)stream : m->stream;
-  CallOrder order(m->evLast, &m->lastStream, s);
-  if (order.status) return order.status;
+  MatcherCall call(m, stream);
+  if (call.status) return call.status;
+  const hipStream_t s = call.s;
   orb_status_t st;
   const bool scratch = view->n_mp > orb_k_local_map_hash_cap();
   if (scratch && (st = m->dLmTable.ensure((size_t)n_problems * (size_t)view->n_mp * 4)))

@@ -3,7 +3,7 @@
 // src/KeyFrame.cc:60-71 -> TemplatedVocabulary::transform,
 // Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:1128-1283).
 //
-// Device tree layout (built by runtime.cpp from the loadFromTextFile node
+// Device tree layout (built by runtime_vocab.cpp from the loadFromTextFile node
 // table): nodes renumbered breadth-first so that every node's children sit at
 // consecutive device positions in the reference's child order.  Position p
 // holds {first child position, child count}, the 32-byte descriptor, the word

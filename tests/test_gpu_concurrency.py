@@ -234,7 +234,7 @@ def test_batch_rate_with_extra_caller_streams(gpu):
     submission order.  The batch path forks level 0's FAST (then levels 1-2)
     onto the device's shared side stream, and every handle's own stream is
     created at the least priority too, so no library stream takes a queue from
-    the caller's normal- or high-priority pools (runtime.cpp create_own_stream:
+    the caller's normal- or high-priority pools (runtime_common.h create_own_stream:
     three normal-priority streams created at start-up, by any code, halved a
     later high-priority stream's rate beside busy normal streams,
     profiles/r05_contention.txt).  In a fresh process (the queue mapping

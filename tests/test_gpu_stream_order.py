@@ -5,7 +5,7 @@ keys, octree tables) and a frame-size change rewrites the handle's plan tables;
 every matcher call reuses the grid, candidate lists and claim buffers.  The
 batch entry points run asynchronously on whatever stream the caller passes, so
 the library orders a call after the previous call on the same handle whenever
-the stream changes (runtime.cpp CallOrder; include/orb_abi.h "Streams").  The
+the stream changes (runtime_common.h CallOrder; include/orb_abi.h "Streams").  The
 reference states the rule in host form: an ORBextractor is not reentrant
 (include/ORBextractor.h:85; it rebuilds mvImagePyramid on every call), and
 Frame runs two instances at once (src/Frame.cc:81-84).
