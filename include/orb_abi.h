@@ -86,6 +86,11 @@
  *                                  local matcher, as global point indices
  *   orb_track_local_map_finish_batch  mnMatchesInliers and the stereo outlier reset of
  *                                  Tracking::TrackLocalMap src/Tracking.cc:1109-1135
+ *   orb_sim3_solver_setup_batch    Sim3Solver's constructor and SetRansacParameters
+ *                                  src/Sim3Solver.cc:37-141 (LoopClosing::ComputeSim3
+ *                                  src/LoopClosing.cc)
+ *   orb_sim3_solver_iterate_batch  Sim3Solver::iterate / find :144-220 with ComputeSim3
+ *                                  :237-351, CheckInliers :354-378 and Project :396-417
  *   orb_vocabulary_create / _load_text / _destroy
  *                                  DBoW2 TemplatedVocabulary ctor + loadFromTextFile
  *                                  Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:1362-1448
@@ -1208,6 +1213,199 @@ orb_status_t orb_track_local_map_finish_batch(orb_matcher_t* m, int n_problems,
                                               long long pt_stride, int only_tracking,
                                               int null_outliers, int32_t* d_n_inliers,
                                               void* stream);
+
+/* ------------------------------------------------- Sim3Solver on the device */
+
+/* Sim3Solver (src/Sim3Solver.cc, include/Sim3Solver.h) for n_problems
+ * independent (pKF1, pKF2, vpMatched12) problems as LoopClosing::ComputeSim3
+ * runs them: one call builds the solvers (the constructor and
+ * SetRansacParameters), one runs iterate(n) on every solver that is still
+ * active.  Every per-problem array is a device pointer, both calls are
+ * asynchronous on `stream`, neither synchronises with the host, and neither
+ * uses the handle's scratch, so both are ordered by `stream` alone.  The
+ * caller owns the state and correspondence arrays; they are the solver's
+ * members between calls.
+ *
+ * One correspondence the constructor's loop (:62-105) keeps, in ascending i1. */
+typedef struct orb_sim3_corr {
+  int32_t index1;      /* mvnIndices1: i1 */
+  float x1[3];         /* mvX3Dc1 = Rcw1 * pos(pMP1) + tcw1 */
+  float x2[3];         /* mvX3Dc2 = Rcw2 * pos(pMP2) + tcw2 */
+  float p1[2];         /* mvP1im1 (FromCameraToImage, mK1) */
+  float p2[2];         /* mvP2im2 (mK2) */
+  float max_err1;      /* mvnMaxError1: the size_t (9.210 * sigma2, truncated) as the float */
+  float max_err2;      /*   the comparison err < maxError converts it to; mvnMaxError2 */
+  uint8_t best_inlier; /* mvbBestInliers */
+  uint8_t _pad[3];     /* written as 0 */
+} orb_sim3_corr_t;     /* 56 bytes */
+
+typedef struct orb_sim3_state {
+  int32_t status;         /* 0; -1: malformed slot or draw, every later iterate returns "no more" */
+  int32_t n1;             /* mN1 = vpMatched12.size() (keyframe 1's clamped count) */
+  int32_t n;              /* N = mvpMapPoints1.size() */
+  int32_t max_its;        /* mRansacMaxIts after SetRansacParameters (0 when N < min_inliers) */
+  int32_t iterations;     /* mnIterations */
+  int32_t best_inliers;   /* mnBestInliers */
+  int32_t best_iteration; /* the 1-based lifetime iteration that produced the best (0: none) */
+  int32_t min_inliers;    /* mRansacMinInliers */
+  int32_t fix_scale;      /* mbFixScale */
+  float best_scale;       /* mBestScale (0 until an iteration is taken) */
+  float best_R[9];        /* mBestRotation, row-major */
+  float best_t[3];        /* mBestTranslation */
+  float best_T12[16];     /* mBestT12, row-major */
+  float k1[4], k2[4];     /* fx, fy, cx, cy of mK1 and mK2 */
+} orb_sim3_state_t;       /* 184 bytes */
+
+typedef struct orb_sim3_result {
+  int32_t has_sim3;       /* iterate returned a non-empty Mat */
+  int32_t no_more;        /* bNoMore */
+  int32_t n_inliers;      /* nInliers (0 unless has_sim3) */
+  int32_t iterations_run; /* nCurrentIterations of this call */
+  float T12[16];          /* the returned mBestT12; the four below: zeros unless has_sim3 */
+  float R[9];             /* GetEstimatedRotation() */
+  float t[3];             /* GetEstimatedTranslation() */
+  float scale;            /* GetEstimatedScale() */
+} orb_sim3_result_t;      /* 132 bytes */
+
+/* The constructor and SetRansacParameters (:37-141).
+ * Slots, as orb_match_bow_batch lays keyframes out: slot k has mvKeysUn at
+ * d_kf_keys + k * kp_stride, GetMapPointMatches() as indices into d_points at
+ * d_kf_point_index + k * kp_stride (any negative value is NULL), its count
+ * d_kf_nkeys[k] (clamped to [0, kp_stride]) and its pose d_kf_pose[k] (rcw and
+ * tcw are read).  Problem p uses slots d_kf1_slot[p] and d_kf2_slot[p] (either
+ * NULL: slot p; a slot may serve many problems).  d_points is one array shared
+ * by all problems (pos and bad are read); the caller keeps every non-negative
+ * point index inside it and every slot number inside the slot arrays (NOT
+ * checked).
+ * Matches: d_match12 + p * kp_stride holds, per i1 < mN1, the global point
+ * index of vpMatched12[i1] (negative: NULL); d_index2 + p * kp_stride holds
+ * pMP2->GetIndexInKeyFrame(pKF2) (the matchers' bestIdx2); d_index1 is optional
+ * (NULL: i1), else pMP1->GetIndexInKeyFrame(pKF1).
+ * Skips, in the reference's order: NULL match, NULL pMP1, either point bad,
+ * either index negative.  A kept correspondence whose index is at or above its
+ * keyframe's clamped count, or whose keypoint's octave is outside
+ * [0, n_levels), makes the problem malformed: status = -1, n1 as usual, every
+ * other state field 0, no correspondence written, and nothing is indexed with
+ * the bad value.
+ * Host values: level_sigma2[n_levels] (mvLevelSigma2; 1 <= n_levels <= 16, each
+ * finite and in [0, 1e15]), cam1 / cam2 (fx, fy, cx, cy are read), fix_scale,
+ * probability (strictly between 0 and 1), min_inliers (>= 3: below it the
+ * reference would call RandomInt(0, -1)), max_iterations (>= 1).
+ * Out: d_state[p]; d_corr + p * kp_stride, the first `n` records (the rest is
+ * not written), best_inlier 0.  max_its: N < min_inliers stores 0 (iterate
+ * never reads it); N == min_inliers gives 1; otherwise epsilon =
+ * (float)min_inliers / N and ceil(log(1 - p) / log(1 - pow(epsilon, 3))),
+ * clamped to [1, max_iterations].
+ * Capacity: iterate keeps 48 bytes per correspondence slot and (SIM3_CHUNK +
+ * 1) bits per slot in LDS over kp_stride rounded up to 64, beside 8 KiB of
+ * static state; orb_sim3_solver_max_stride() is the largest kp_stride that
+ * fits the 160 KiB of one CU (a pure function, callable without a device).
+ * Above it both calls return ORB_ECAPACITY before anything is launched, and
+ * nothing is written.
+ * ORB_EINVAL: a null required pointer, n_problems < 0, kp_stride <= 0, a host
+ * value outside the ranges above.  n_problems == 0: ORB_OK, no launch. */
+orb_status_t orb_sim3_solver_setup_batch(
+    orb_matcher_t* m, int n_problems, const int32_t* d_kf1_slot, const int32_t* d_kf2_slot,
+    const orb_keypoint_t* d_kf_keys, const int32_t* d_kf_nkeys, const int32_t* d_kf_point_index,
+    const orb_pose_t* d_kf_pose, int kp_stride, const orb_map_point_t* d_points,
+    const int32_t* d_match12, const int32_t* d_index1, const int32_t* d_index2,
+    const float* level_sigma2, int n_levels, const orb_camera_t* cam1, const orb_camera_t* cam2,
+    int fix_scale, double probability, int min_inliers, int max_iterations,
+    orb_sim3_state_t* d_state, orb_sim3_corr_t* d_corr, void* stream);
+int orb_sim3_solver_max_stride(void);
+
+/* iterate(n_iterations) (:144-214) on every problem (find(): n_iterations =
+ * max_iterations).  d_active is optional (vbDiscarded inverted): a problem with
+ * d_active[p] == 0 is skipped and nothing of it is read or written.
+ * Draws: d_draws + p * draw_stride, raw rand() values.  Entry 3 * it + j
+ * serves lifetime iteration `it` (mnIterations before its increment), draw j.
+ * The device evaluates DUtils::Random::RandomInt(0, size - 1)
+ * (Thirdparty/DBoW2/DUtils/Random.cpp:47-50) as
+ * (int)(((double)r / ((double)rand_max + 1.0)) * size) with size = N, N - 1,
+ * N - 2 and removes each pick by the swap with the back of :175-183.  One draw
+ * stream per solver: the reference's single global rand() sequence interleaves
+ * the solvers of ComputeSim3's round-robin, and its order is the integrator's
+ * to reproduce.  A consumed r > rand_max makes the problem
+ * malformed: the iteration that reads it is not run and not counted, status
+ * becomes -1, the best of the earlier iterations stays, and the call returns
+ * "no more" without a Sim3.  max_iterations is the value given to setup (the
+ * device clamps the state's max_its to it); draw_stride < 3 * max_iterations
+ * is ORB_EINVAL.
+ * Per iteration ComputeSim3 (:237-351) and CheckInliers (:354-378), IEEE
+ * throughout with nothing special-cased (identical points: den = 0; a zero
+ * imaginary part: vec / 0; z = 0), then the acceptance rule in iteration order
+ * (:190-207): the best is taken on >=, the call returns on the first
+ * mnInliersi > mRansacMinInliers (strict), vbInliers is indexed through
+ * mvnIndices1; on success bNoMore stays false even at the last allowed
+ * iteration, and the next call runs nothing and returns bNoMore.  N <
+ * min_inliers, or status < 0, returns bNoMore at once.  The hypotheses of a
+ * call are evaluated side by side and the rule is replayed over them in order;
+ * work past a return is never visible, and the state after k calls of
+ * iterate(5) equals, bit for bit, the state after one call that runs the same
+ * iterations.
+ * Out: d_inliers12 + p * kp_stride, n1 bytes (vbInliers; all 0 unless a Sim3
+ * is returned); d_result[p]; the updated d_state[p] and the best_inlier bytes
+ * of d_corr.  ORB_EINVAL: a null required pointer, a negative count, kp_stride
+ * <= 0, max_iterations < 1, draw_stride < 3 * max_iterations.  n_problems ==
+ * 0: ORB_OK, no launch.
+ *
+ * Pins (the same list stands in tests/sim3_ref.py and DESIGN.md 4.9; OpenCV
+ * itself is not available to the project: unpinned against a real OpenCV).
+ * Float expressions are evaluated as written, no contraction.
+ *  P1  Rcw * X + tcw (constructor, Project): ((r0 x + r1 y) + r2 z) + t in
+ *      float, the project's existing pin; 1 / z, x * invz, fx * x + cx in float.
+ *  P2  scalar * Mat and Mat / scalar: the double scalar narrowed to float, then
+ *      v * s + 0.0f per element (cvtScale_).  C / P.cols is
+ *      c * (float)(1.0 / 3) + 0.0f; 2 * ang * vec / norm(vec) has
+ *      s = (float)((2.0 * ang) * (1.0 / norm)); sR = R * ms12i;
+ *      sRinv = R^T * (float)(1.0 / (double)ms12i).
+ *  P3  cv::reduce(P, C, 1, CV_REDUCE_SUM) over three columns:
+ *      (p0 + p2) + p1 in float (reduceC_'s two accumulators).
+ *  P4  A * B.t() (M = Pr2 * Pr1.t()): per element a double accumulator from 0,
+ *      k ascending, exact double products, narrowed once to float.
+ *  P5  A * B of 3 x 3 floats without a transpose (P3 = R * Pr2):
+ *      (a0 b0 + a1 b1) + a2 b2 in float.
+ *  P6  N11..N44: the float expressions as written, left to right (the doubles
+ *      that hold them narrow back to the same floats).
+ *  P7  cv::eigen on the symmetric 4 x 4 float matrix: OpenCV 3.x's
+ *      JacobiImpl_<float>, step by step: V = I, W = diag(A); indR[k] = the first
+ *      largest |A[k][m]|, m > k; indC[k] = the first largest |A[i][k]|, i < k;
+ *      up to 30 n^2 = 480 sweeps of: the pivot (k, l) = the first largest of
+ *      |A[i][indR[i]]|, i = 0..n-2, then of |A[indC[i]][i]|, i = 1..n-1
+ *      (strictly larger replaces); p = A[k][l]; stop when |p| <= FLT_EPSILON;
+ *      y = (float)((W[l] - W[k]) * 0.5); t = |y| + hypot(p, y); s = hypot(p, t);
+ *      c = t / s; s = p / s; t = (p / t) * p; y < 0 negates s and t;
+ *      A[k][l] = 0; W[k] -= t; W[l] += t; rotate(a, b) = (a c - b s, a s + b c)
+ *      over (A[i][k], A[i][l]) i < k, (A[k][i], A[i][l]) k < i < l,
+ *      (A[k][i], A[l][i]) i > l, and (V[k][i], V[l][i]) all i; indR and indC
+ *      recomputed for k and l only.  Then a selection sort, descending (swap
+ *      with the first largest remaining, strict <), eigenvectors as rows.
+ *      hypot(a, b) = (float)sqrt((double)a * a + (double)b * b).
+ *  P8  cv::norm(vec): sqrt(((0 + v0 v0) + v1 v1) + v2 v2), products and sums in
+ *      double; cv::norm returns that double.
+ *  P9  atan2 on doubles: fdlibm's e_atan2.c over s_atan.c, built from IEEE
+ *      operations alone (pinned_atan2), no libm call on either side.
+ *  P10 cv::Rodrigues, vector to matrix, in double: theta = sqrt((rx rx + ry ry)
+ *      + rz rz); theta < DBL_EPSILON gives I; else c, s = pinned_sincos_d(theta),
+ *      c1 = 1 - c, r *= 1 / theta, R_ij = (c I_ij + c1 r_i r_j) + s [r]x_ij,
+ *      each narrowed to float.
+ *  P11 Mat::dot: a double accumulator over the elements row-major, unrolled by
+ *      four: r += ((p0 + p1) + p2) + p3 per group, then r += p one at a time,
+ *      with exact double products (nom over nine elements, err over two).
+ *  P12 cv::pow(P3, 2): x * x in float; den adds those floats into a double,
+ *      row-major; ms12i = (float)(nom / den).
+ *  P13 the folded O1 - ms12i * mR12i * O2 (one gemm): u_k = (R_k0 o0 + R_k1 o1)
+ *      + R_k2 o2 in float, t_k = (float)((double)u_k * -(double)ms12i +
+ *      (double)O1_k).
+ *  P14 tinv = -sRinv * mt12i: 0.0f - ((a0 t0 + a1 t1) + a2 t2) in float.
+ *  P15 pow(epsilon, 3) = (x * x) * x in double; log = pinned_log; sin and cos =
+ *      pinned_sincos_d; sqrt and / are IEEE.
+ *  P16 thresholds: (float)(uint64_t)(9.210 * (double)sigma2). */
+orb_status_t orb_sim3_solver_iterate_batch(
+    orb_matcher_t* m, int n_problems, int kp_stride, orb_sim3_state_t* d_state,
+    orb_sim3_corr_t* d_corr, const uint32_t* d_draws, int draw_stride, uint32_t rand_max,
+    int max_iterations, int n_iterations, const uint8_t* d_active, uint8_t* d_inliers12,
+    orb_sim3_result_t* d_result, void* stream);
 
 /* ------------------------------------------------------ DBoW2 vocabulary */
 

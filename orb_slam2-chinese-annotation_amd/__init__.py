@@ -60,6 +60,20 @@ LOCAL_MAP_INFO_DTYPE = np.dtype([("n_local_kf", "<i4"), ("n_voted", "<i4"), ("n_
                                  ("ref_kf", "<i4"), ("max_votes", "<i4"),
                                  ("n_local_points", "<i4"), ("n_nulled", "<i4"), ("kept", "<i4")])
 assert LOCAL_MAP_INFO_DTYPE.itemsize == 32
+SIM3_CORR_DTYPE = np.dtype([("index1", "<i4"), ("x1", "<f4", (3,)), ("x2", "<f4", (3,)),
+                            ("p1", "<f4", (2,)), ("p2", "<f4", (2,)), ("max_err1", "<f4"),
+                            ("max_err2", "<f4"), ("best_inlier", "u1"), ("_pad", "u1", (3,))])
+SIM3_STATE_DTYPE = np.dtype([("status", "<i4"), ("n1", "<i4"), ("n", "<i4"), ("max_its", "<i4"),
+                             ("iterations", "<i4"), ("best_inliers", "<i4"),
+                             ("best_iteration", "<i4"), ("min_inliers", "<i4"),
+                             ("fix_scale", "<i4"), ("best_scale", "<f4"), ("best_R", "<f4", (9,)),
+                             ("best_t", "<f4", (3,)), ("best_T12", "<f4", (16,)),
+                             ("k1", "<f4", (4,)), ("k2", "<f4", (4,))])
+SIM3_RESULT_DTYPE = np.dtype([("has_sim3", "<i4"), ("no_more", "<i4"), ("n_inliers", "<i4"),
+                              ("iterations_run", "<i4"), ("T12", "<f4", (16,)),
+                              ("R", "<f4", (9,)), ("t", "<f4", (3,)), ("scale", "<f4")])
+assert SIM3_CORR_DTYPE.itemsize == 56 and SIM3_STATE_DTYPE.itemsize == 184
+assert SIM3_RESULT_DTYPE.itemsize == 132
 ORB_DEPTH_U16, ORB_DEPTH_F32 = 0, 1
 
 
@@ -238,6 +252,12 @@ def lib() -> ctypes.CDLL:
         "orb_track_local_merge_batch": (i32, [vp, i32, vp, i32, vp, vp, i32, vp, vp]),
         "orb_track_local_map_finish_batch": (i32, [vp, i32, vp, i32, vp, vp, vp, i64, i32, i32,
                                                    vp, vp]),
+        "orb_sim3_solver_setup_batch": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp,
+                                              vp, i32, vp, vp, i32, ctypes.c_double, i32, i32, vp,
+                                              vp, vp]),
+        "orb_sim3_solver_max_stride": (i32, []),
+        "orb_sim3_solver_iterate_batch": (i32, [vp, i32, i32, vp, vp, vp, i32, ctypes.c_uint32,
+                                                i32, i32, vp, vp, vp, vp]),
         "orb_synth_image": (None, [ctypes.c_uint64, i32, i32, i32, i32, vp, sz]),
         "orb_synth_local_map": (None, [ctypes.c_uint64, vp, vp, i32, i32, i32, i32, vp, vp, vp]),
     }
@@ -247,7 +267,9 @@ def lib() -> ctypes.CDLL:
              "orb_track_discard_outliers_batch", "orb_track_discard_outliers_batch_n",
              "orb_match_bow_batch", "orb_match_bow_batch_max_stride",
              "orb_update_local_map_batch", "orb_update_local_map_max_keyframes",
-             "orb_track_local_merge_batch", "orb_track_local_map_finish_batch")
+             "orb_track_local_merge_batch", "orb_track_local_map_finish_batch",
+             "orb_sim3_solver_setup_batch", "orb_sim3_solver_max_stride",
+             "orb_sim3_solver_iterate_batch")
     for name, (res, args) in sig.items():
         if name in newer and "ORB_AMD_LIB" in os.environ and not hasattr(L, name):
             continue
@@ -293,6 +315,13 @@ def update_local_map_max_keyframes() -> int:
     kf_stride) update_local_map_batch accepts; a pure function of k_local_map's
     LDS layout, callable without a device."""
     return lib().orb_update_local_map_max_keyframes()
+
+
+def sim3_solver_max_stride() -> int:
+    """orb_sim3_solver_max_stride(): the largest kp_stride the Sim3Solver batch
+    accepts; a pure function of k_sim3_iterate's LDS layout, callable without
+    a device."""
+    return lib().orb_sim3_solver_max_stride()
 
 
 class MapView:
@@ -1347,6 +1376,56 @@ class ORBmatcher:
             int(bool(null_outliers)), d_n_inliers or None, stream or None),
             "track_local_map_finish_batch")
 
+    # ------------------------------------- LoopClosing::ComputeSim3's solver, device batch
+    @staticmethod
+    def _camera4(cam):
+        v = [float(x) for x in cam]
+        return _Camera(*(v + [0.0] * (6 - len(v))))
+
+    def sim3_solver_setup_batch(self, n_problems, d_kf1_slot, d_kf2_slot, d_kf_keys, d_kf_nkeys,
+                                d_kf_point_index, d_kf_pose, kp_stride, d_points, d_match12,
+                                d_index1, d_index2, level_sigma2, cam1, cam2, fix_scale,
+                                d_state, d_corr, probability: float = 0.99,
+                                min_inliers: int = 20, max_iterations: int = 300,
+                                stream: int = 0):
+        """Sim3Solver's constructor and SetRansacParameters for n_problems
+        (pKF1, pKF2, vpMatched12) problems (orb_sim3_solver_setup_batch).  d_* are
+        device addresses in the keyframe slot layout of search_by_bow_batch;
+        d_kf1_slot, d_kf2_slot and d_index1 may be 0 (identity).  cam1, cam2:
+        (fx, fy, cx, cy[, bf, mb]).  d_state holds n_problems SIM3_STATE_DTYPE
+        records, d_corr n_problems x kp_stride SIM3_CORR_DTYPE records.
+        Asynchronous on `stream`."""
+        ls = np.ascontiguousarray(level_sigma2, np.float32).reshape(-1)
+        c1, c2 = self._camera4(cam1), self._camera4(cam2)
+        _check(lib().orb_sim3_solver_setup_batch(
+            self._h, n_problems, d_kf1_slot or None, d_kf2_slot or None, d_kf_keys or None,
+            d_kf_nkeys or None, d_kf_point_index or None, d_kf_pose or None, kp_stride,
+            d_points or None, d_match12 or None, d_index1 or None, d_index2 or None,
+            _ptr(ls) if len(ls) else None, len(ls), ctypes.byref(c1), ctypes.byref(c2),
+            int(bool(fix_scale)), float(probability), int(min_inliers), int(max_iterations),
+            d_state or None, d_corr or None, stream or None), "sim3_solver_setup_batch")
+
+    def sim3_solver_iterate_batch(self, n_problems, kp_stride, d_state, d_corr, d_draws,
+                                  draw_stride, n_iterations, d_inliers12, d_result,
+                                  d_active: int = 0, rand_max: int = 2147483647,
+                                  max_iterations: int = 300, stream: int = 0):
+        """Sim3Solver::iterate(n_iterations) on every problem whose d_active byte
+        is not 0 (d_active 0: all) (orb_sim3_solver_iterate_batch).  d_draws:
+        raw rand() values, uint32, entry 3 * it + j of each problem's
+        draw_stride entries for lifetime iteration it, draw j.  d_result holds
+        n_problems SIM3_RESULT_DTYPE records, d_inliers12 n_problems x
+        kp_stride bytes.  Asynchronous on `stream`."""
+        _check(lib().orb_sim3_solver_iterate_batch(
+            self._h, n_problems, kp_stride, d_state or None, d_corr or None, d_draws or None,
+            draw_stride, int(rand_max), int(max_iterations), int(n_iterations),
+            d_active or None, d_inliers12 or None, d_result or None, stream or None),
+            "sim3_solver_iterate_batch")
+
+    @staticmethod
+    def sim3_solver_max_stride() -> int:
+        """Largest kp_stride the Sim3Solver batch accepts."""
+        return lib().orb_sim3_solver_max_stride()
+
     # ------------------------------------------ MapPoint::ComputeDistinctiveDescriptors
     def ComputeDistinctiveDescriptors(self, obs_offs, obs_desc, descriptors=None):
         """MapPoint::ComputeDistinctiveDescriptors for many points (src/MapPoint.cc:250-326).
@@ -1371,6 +1450,94 @@ class ORBmatcher:
         _check(lib().orb_distinctive_descriptors_batch(self._h, n_mp, d_offs, d_desc, d_best,
                                                        d_out, stream or None),
                "distinctive_descriptors_batch")
+
+
+# ------------------------------------------------------------------ Sim3Solver
+class Sim3Solver:
+    """ORB_SLAM2::Sim3Solver for one (pKF1, pKF2, vpMatched12) problem on the
+    device batch of one (include/Sim3Solver.h).  keys1 / keys2: KEYPOINT_DTYPE
+    (mvKeysUn); point_index1: GetMapPointMatches() of pKF1 as indices into
+    `points` (MAP_POINT_DTYPE; negative NULL); pose1 / pose2: POSE_DTYPE records;
+    match12: the point index of vpMatched12[i1] or negative; index2:
+    GetIndexInKeyFrame(pKF2) per i1; index1 optional.  draws: raw rand() values,
+    three per iteration (uint32); the solver owns its draw stream."""
+
+    def __init__(self, matcher: "ORBmatcher", keys1, point_index1, pose1, keys2, pose2, points,
+                 match12, index2, level_sigma2, cam1, cam2, bFixScale: bool, draws,
+                 index1=None, rand_max: int = 2147483647, probability: float = 0.99,
+                 minInliers: int = 20, maxIterations: int = 300):
+        import torch
+
+        dev = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).cuda()
+        k1 = np.ascontiguousarray(keys1, KEYPOINT_DTYPE).reshape(-1)
+        k2 = np.ascontiguousarray(keys2, KEYPOINT_DTYPE).reshape(-1)
+        S = max(len(k1), len(k2), 1)
+        if S > sim3_solver_max_stride():
+            raise OrbError(ORB_ECAPACITY, "Sim3Solver")
+        self._m, self._S, self.mN1 = matcher, S, len(k1)
+        self._rand_max, self._max_its = int(rand_max), int(maxIterations)
+        keys = np.zeros((2, S), KEYPOINT_DTYPE)
+        keys[0, :len(k1)], keys[1, :len(k2)] = k1, k2
+        pidx = np.full((2, S), -1, np.int32)
+        pidx[0, :len(k1)] = np.asarray(point_index1, np.int32)[:len(k1)]
+        pose = np.zeros(2, POSE_DTYPE)
+        pose[0], pose[1] = pose1, pose2
+        pad = lambda a: np.concatenate([np.asarray(a, np.int32).reshape(-1)[:S],
+                                        np.full(max(S - len(a), 0), -1, np.int32)])
+        d = np.ascontiguousarray(draws, np.uint32).reshape(-1)
+        if len(d) < 3 * self._max_its:
+            raise OrbError(ORB_EINVAL, "Sim3Solver: fewer than 3 * maxIterations draws")
+        self._bufs = [dev(keys), dev(np.array([len(k1), len(k2)], np.int32)), dev(pidx), dev(pose),
+                      dev(np.ascontiguousarray(points, MAP_POINT_DTYPE)), dev(pad(match12)),
+                      dev(pad(index2)), dev(pad(index1)) if index1 is not None else None, dev(d),
+                      dev(np.array([0, 1], np.int32))]
+        self._state = torch.zeros(SIM3_STATE_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
+        self._corr = torch.zeros(S * SIM3_CORR_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
+        self._inl = torch.zeros(S, dtype=torch.uint8, device="cuda")
+        self._res = torch.zeros(SIM3_RESULT_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
+        self._draw_stride = len(d)
+        b = self._bufs
+        # a stream of the solver's own, behind what the current stream has queued
+        self._stream = torch.cuda.Stream()
+        self._stream.wait_stream(torch.cuda.current_stream())
+        stream = self._stream.cuda_stream
+        matcher.sim3_solver_setup_batch(
+            1, b[9].data_ptr(), b[9].data_ptr() + 4, b[0].data_ptr(), b[1].data_ptr(),
+            b[2].data_ptr(), b[3].data_ptr(), S, b[4].data_ptr(), b[5].data_ptr(),
+            b[7].data_ptr() if b[7] is not None else 0, b[6].data_ptr(), level_sigma2, cam1, cam2,
+            bFixScale, self._state.data_ptr(), self._corr.data_ptr(), probability, minInliers,
+            maxIterations, stream)
+
+    def state(self):
+        """The solver's members (SIM3_STATE_DTYPE record)."""
+        self._stream.synchronize()
+        return self._state.cpu().numpy().view(SIM3_STATE_DTYPE)[0]
+
+    def iterate(self, nIterations: int):
+        """(T12 (4 x 4) or None, bNoMore, vbInliers (mN1 bools), nInliers)."""
+        self._m.sim3_solver_iterate_batch(
+            1, self._S, self._state.data_ptr(), self._corr.data_ptr(), self._bufs[8].data_ptr(),
+            self._draw_stride, nIterations, self._inl.data_ptr(), self._res.data_ptr(), 0,
+            self._rand_max, self._max_its, self._stream.cuda_stream)
+        self._stream.synchronize()
+        r = self._res.cpu().numpy().view(SIM3_RESULT_DTYPE)[0]
+        inl = self._inl.cpu().numpy()[:self.mN1].astype(bool)
+        T = r["T12"].reshape(4, 4).copy() if r["has_sim3"] else None
+        return T, bool(r["no_more"]), inl, int(r["n_inliers"])
+
+    def find(self):
+        """(T12 or None, vbInliers12, nInliers)."""
+        T, _, inl, n = self.iterate(self._max_its)
+        return T, inl, n
+
+    def GetEstimatedRotation(self):
+        return self.state()["best_R"].reshape(3, 3).copy()
+
+    def GetEstimatedTranslation(self):
+        return self.state()["best_t"].copy()
+
+    def GetEstimatedScale(self) -> float:
+        return float(self.state()["best_scale"])
 
 
 # ------------------------------------------------------------------ vocabulary

@@ -255,3 +255,40 @@ struct LocalMapParams {
   orb_local_map_info_t* info;
   int32_t* table;         // the scratch tier's per-problem table, nMp entries each
 };
+
+// --------------------------------------------------------- sim3_kernels.hip
+// Sim3Solver's constructor and SetRansacParameters over nProblems (by value)
+struct Sim3SetupParams {
+  int nProblems, stride;
+  const int32_t* kf1Slot;  // null: p
+  const int32_t* kf2Slot;
+  const orb_keypoint_t* keys;
+  const int32_t* nkeys;
+  const int32_t* pointIndex;
+  const orb_pose_t* pose;
+  const orb_map_point_t* points;
+  const int32_t* match12;
+  const int32_t* index1;   // null: i1
+  const int32_t* index2;
+  int nLevels;
+  float maxErr[ORB_MAX_LEVELS];  // (float)(uint64_t)(9.210 * sigma2) per level
+  float k1[4], k2[4];            // fx, fy, cx, cy
+  int fixScale, minInliers, maxIterations;
+  double probability;            // mRansacProb (pinned_log(1 - p) is evaluated on the device)
+  orb_sim3_state_t* state;
+  orb_sim3_corr_t* corr;
+};
+
+// Sim3Solver::iterate over nProblems (by value)
+struct Sim3IterParams {
+  int nProblems, stride;
+  orb_sim3_state_t* state;
+  orb_sim3_corr_t* corr;
+  const uint32_t* draws;
+  int drawStride;
+  uint32_t randMax;
+  int maxIterations, nIterations;
+  const uint8_t* active;  // null: every problem
+  uint8_t* inliers12;
+  orb_sim3_result_t* result;
+};

@@ -242,4 +242,9 @@ int orb_k_local_map_max_keyframes(void);
 // distinct point ids the LDS table takes before a problem runs on the scratch table
 int orb_k_local_map_hash_cap(void);
 hipError_t orb_k_local_map(const LocalMapParams* params, hipStream_t s);
+// --------------------------------------------------------- sim3_kernels.hip
+// largest kp_stride whose staged correspondences and inlier rows fit one CU's LDS
+int orb_k_sim3_max_stride(void);
+hipError_t orb_k_sim3_setup(const Sim3SetupParams* params, hipStream_t s);
+hipError_t orb_k_sim3_iterate(const Sim3IterParams* params, hipStream_t s);
 }

@@ -14,6 +14,7 @@
 #include <algorithm>
 #include <cassert>
 #include <cstdint>
+#include <functional>
 #include <map>
 #include <stdexcept>
 #include <string>
@@ -914,6 +915,40 @@ class ORBmatcher {
           "track_local_map_finish_batch");
   }
 
+  // Sim3Solver's constructor with SetRansacParameters, and iterate, for
+  // n_problems (pKF1, pKF2, vpMatched12) problems (orb_sim3_solver_setup_batch,
+  // orb_sim3_solver_iterate_batch; src/Sim3Solver.cc).  d_kf1_slot, d_kf2_slot,
+  // d_index1 and d_active may be null (identity / every problem).
+  void sim3_solver_setup_batch(int n_problems, const int32_t* d_kf1_slot,
+                               const int32_t* d_kf2_slot, const KeyPoint* d_kf_keys,
+                               const int32_t* d_kf_nkeys, const int32_t* d_kf_point_index,
+                               const orb_pose_t* d_kf_pose, int kp_stride,
+                               const orb_map_point_t* d_points, const int32_t* d_match12,
+                               const int32_t* d_index1, const int32_t* d_index2,
+                               const std::vector<float>& levelSigma2, const orb_camera_t& cam1,
+                               const orb_camera_t& cam2, bool fix_scale, double probability,
+                               int min_inliers, int max_iterations, orb_sim3_state_t* d_state,
+                               orb_sim3_corr_t* d_corr, void* stream = nullptr) {
+    check(orb_sim3_solver_setup_batch(h_, n_problems, d_kf1_slot, d_kf2_slot, d_kf_keys,
+                                      d_kf_nkeys, d_kf_point_index, d_kf_pose, kp_stride, d_points,
+                                      d_match12, d_index1, d_index2, levelSigma2.data(),
+                                      (int)levelSigma2.size(), &cam1, &cam2, fix_scale ? 1 : 0,
+                                      probability, min_inliers, max_iterations, d_state, d_corr,
+                                      stream),
+          "sim3_solver_setup_batch");
+  }
+  void sim3_solver_iterate_batch(int n_problems, int kp_stride, orb_sim3_state_t* d_state,
+                                 orb_sim3_corr_t* d_corr, const uint32_t* d_draws,
+                                 int draw_stride, uint32_t rand_max, int max_iterations,
+                                 int n_iterations, const uint8_t* d_active, uint8_t* d_inliers12,
+                                 orb_sim3_result_t* d_result, void* stream = nullptr) {
+    check(orb_sim3_solver_iterate_batch(h_, n_problems, kp_stride, d_state, d_corr, d_draws,
+                                        draw_stride, rand_max, max_iterations, n_iterations,
+                                        d_active, d_inliers12, d_result, stream),
+          "sim3_solver_iterate_batch");
+  }
+  static int sim3_solver_max_stride() { return orb_sim3_solver_max_stride(); }
+
   float mfNNratio;
   bool mbCheckOrientation;
   orb_matcher_t* handle() { return h_; }
@@ -943,6 +978,107 @@ struct PoseFrame {
   orb_pose_t mTcw{};                // in: the start pose; out: what SetPose receives
   std::vector<uint8_t> mvbOutlier;  // written for the keypoints that have a MapPoint
   orb_pose_opt_info_t info{};       // n_edges, lm_iterations, rejected_trials of the last call
+};
+
+// ORB_SLAM2::Sim3Solver (include/Sim3Solver.h) for one problem on the device
+// batch of one.  The caller owns the device arrays (Problem) and says how a
+// result reaches the host: `toHost` waits for `stream` and copies device bytes
+// (hipStreamSynchronize + hipMemcpy in a HIP program; this header stays free of
+// the HIP runtime).  cv::Mat results are row-major float arrays.
+class Sim3Solver {
+ public:
+  struct Problem {  // the slot layout of orb_sim3_solver_setup_batch, one problem
+    const int32_t* d_kf1_slot;  // one entry each (null: slot 0)
+    const int32_t* d_kf2_slot;
+    const KeyPoint* d_kf_keys;
+    const int32_t* d_kf_nkeys;
+    const int32_t* d_kf_point_index;
+    const orb_pose_t* d_kf_pose;
+    int kp_stride;
+    const orb_map_point_t* d_points;
+    const int32_t* d_match12;  // vpMatched12 as point indices, kp_stride entries
+    const int32_t* d_index1;   // null: i1
+    const int32_t* d_index2;
+    const uint32_t* d_draws;   // the solver's own rand() stream, three values per iteration
+    int draw_stride;
+    uint32_t rand_max;
+    orb_sim3_state_t* d_state;  // the solver's members between calls
+    orb_sim3_corr_t* d_corr;    // kp_stride records
+    uint8_t* d_inliers12;       // kp_stride bytes
+    orb_sim3_result_t* d_result;
+  };
+  using ToHost = std::function<void(void* dst, const void* src, size_t bytes)>;
+
+  Sim3Solver(ORBmatcher& matcher, const Problem& problem, const std::vector<float>& levelSigma2,
+             const orb_camera_t& K1, const orb_camera_t& K2, bool bFixScale, ToHost toHost,
+             void* stream = nullptr)
+      : m_(matcher), p_(problem), sigma2_(levelSigma2), k1_(K1), k2_(K2), fix_(bFixScale),
+        toHost_(std::move(toHost)), stream_(stream) {
+    SetRansacParameters();
+  }
+
+  // Runs the constructor's loop again with the new parameters: mnIterations
+  // and the best so far start from zero.
+  void SetRansacParameters(double probability = 0.99, int minInliers = 20,
+                           int maxIterations = 300) {
+    maxIts_ = maxIterations;
+    m_.sim3_solver_setup_batch(1, p_.d_kf1_slot, p_.d_kf2_slot, p_.d_kf_keys, p_.d_kf_nkeys,
+                               p_.d_kf_point_index, p_.d_kf_pose, p_.kp_stride, p_.d_points,
+                               p_.d_match12, p_.d_index1, p_.d_index2, sigma2_, k1_, k2_, fix_,
+                               probability, minInliers, maxIterations, p_.d_state, p_.d_corr,
+                               stream_);
+  }
+
+  // cv::Mat iterate(nIterations, bNoMore, vbInliers, nInliers): true and T12
+  // (4 x 4) when a Sim3 is returned, false for the empty Mat.
+  bool iterate(int nIterations, bool& bNoMore, std::vector<bool>& vbInliers, int& nInliers,
+               float T12[16]) {
+    m_.sim3_solver_iterate_batch(1, p_.kp_stride, p_.d_state, p_.d_corr, p_.d_draws,
+                                 p_.draw_stride, p_.rand_max, maxIts_, nIterations, nullptr,
+                                 p_.d_inliers12, p_.d_result, stream_);
+    toHost_(&last_, p_.d_result, sizeof(last_));
+    const orb_sim3_state_t st = state();
+    std::vector<uint8_t> inl((size_t)std::max(st.n1, 0));
+    if (!inl.empty()) toHost_(inl.data(), p_.d_inliers12, inl.size());
+    vbInliers.assign(inl.begin(), inl.end());
+    bNoMore = last_.no_more != 0;
+    nInliers = last_.n_inliers;
+    if (last_.has_sim3) std::copy(last_.T12, last_.T12 + 16, T12);
+    return last_.has_sim3 != 0;
+  }
+
+  bool find(std::vector<bool>& vbInliers12, int& nInliers, float T12[16]) {
+    bool bFlag;
+    return iterate(maxIts_, bFlag, vbInliers12, nInliers, T12);
+  }
+
+  void GetEstimatedRotation(float R[9]) {
+    const orb_sim3_state_t st = state();
+    std::copy(st.best_R, st.best_R + 9, R);
+  }
+  void GetEstimatedTranslation(float t[3]) {
+    const orb_sim3_state_t st = state();
+    std::copy(st.best_t, st.best_t + 3, t);
+  }
+  float GetEstimatedScale() { return state().best_scale; }
+
+  orb_sim3_state_t state() {
+    orb_sim3_state_t st;
+    toHost_(&st, p_.d_state, sizeof(st));
+    return st;
+  }
+  const orb_sim3_result_t& result() const { return last_; }
+
+ private:
+  ORBmatcher& m_;
+  Problem p_;
+  std::vector<float> sigma2_;
+  orb_camera_t k1_, k2_;
+  bool fix_;
+  ToHost toHost_;
+  void* stream_;
+  int maxIts_ = 300;
+  orb_sim3_result_t last_{};
 };
 
 class Optimizer {

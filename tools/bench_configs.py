@@ -48,6 +48,13 @@ results table:
       against orb_match_bow over the same problems one call at a time (host
       clock; run once more with ORB_AMD_LIB naming the parent build for the
       baseline row alone) + exact check of four problems
+  S1  LoopClosing::ComputeSim3's solver: 64 loop candidates of about 150
+      correspondences each (256 keypoint slots, 30 % gross outliers, random
+      draws), device-resident, by device events (median of 20, minimum,
+      maximum): the setup call, one round of iterate(5) over all candidates,
+      the rounds to completion with the finished ones discarded, one find();
+      against the same calls one problem at a time (64 launches) + exact check
+      of four problems against tests/sim3_ref.py
   R1  RGB-D: 640x480 (TUM1 intrinsics and distortion, DepthMapFactor 5000),
       1000 features, 256 frames per launch, device-resident: extract ->
       undistort -> ComputeStereoFromRGBD -> closest points + UnprojectStereo ->
@@ -55,7 +62,7 @@ results table:
       same pipeline without the RGB-D stages (monocular matcher), each new
       kernel alone by HIP events with its algorithmic bytes + exact check
 
-Usage: python tools/bench_configs.py [--configs C1,C2,C3,C5,F1,F3,P1,R1,T1,M1,B1] [--steps K]
+Usage: python tools/bench_configs.py [--configs C1,C2,C3,C5,F1,F3,P1,R1,T1,M1,B1,S1] [--steps K]
 The oracle (CPU restatement) is used only for the CPU rows and parity checks.
 """
 import argparse
@@ -912,6 +919,110 @@ def b1(args, orb, oracle, torch):
     return out
 
 
+def s1(args, orb, oracle, torch):
+    import sim3_cases as SC
+    from sim3_ref import RESULT_DTYPE, STATE_DTYPE
+    P, S, MAXI = 64, SC.STRIDE, SC.MAX_ITERATIONS
+    rng = np.random.default_rng(31)
+    probs = [SC.make_problem(f"s{i}", 3000 + i, n_corr=int(rng.integers(130, 171)),
+                             n_outliers=45, n_extra=20, scale=1.05) for i in range(P)]
+    b = SC.Batch(probs, S, MAXI)
+
+    def dev(a):
+        return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).cuda()
+    d = {k: dev(getattr(b, k)) for k in ("kf1_slot", "kf2_slot", "keys", "nkeys", "point_index",
+                                         "pose", "points", "match12", "index2", "draws")}
+    state = torch.zeros(P * 184, dtype=torch.uint8, device="cuda")
+    corr = torch.zeros(P * S * 56, dtype=torch.uint8, device="cuda")
+    inl = torch.zeros(P * S, dtype=torch.uint8, device="cuda")
+    res = torch.zeros(P * 132, dtype=torch.uint8, device="cuda")
+    m = orb.ORBmatcher(0.75, True)
+    stream = torch.cuda.Stream()
+    sp = stream.cuda_stream
+
+    def setup(n=P, p0=0):
+        m.sim3_solver_setup_batch(
+            n, d["kf1_slot"].data_ptr() + 4 * p0, d["kf2_slot"].data_ptr() + 4 * p0,
+            d["keys"].data_ptr(), d["nkeys"].data_ptr(), d["point_index"].data_ptr(),
+            d["pose"].data_ptr(), S, d["points"].data_ptr(), d["match12"].data_ptr() + 4 * S * p0,
+            0, d["index2"].data_ptr() + 4 * S * p0, SC.LEVEL_SIGMA2, SC.CAM1, SC.CAM2, False,
+            state.data_ptr() + 184 * p0, corr.data_ptr() + 56 * S * p0, stream=sp)
+
+    def iterate(k, n=P, p0=0, active=0):
+        m.sim3_solver_iterate_batch(
+            n, S, state.data_ptr() + 184 * p0, corr.data_ptr() + 56 * S * p0,
+            d["draws"].data_ptr() + 4 * 3 * MAXI * p0, 3 * MAXI, k, inl.data_ptr() + S * p0,
+            res.data_ptr() + 132 * p0, active, stream=sp)
+
+    def events(prep, fn, reps=20):
+        t = []
+        for _ in range(reps):
+            prep()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            fn()
+            e1.record(stream)
+            torch.cuda.synchronize()
+            t.append(e0.elapsed_time(e1))
+        t.sort()
+        return {"median": t[len(t) // 2], "min": t[0], "max": t[-1]}
+
+    def results():
+        torch.cuda.synchronize()
+        return res.cpu().numpy().view(RESULT_DTYPE).copy()
+
+    def serial(fn):
+        for p in range(P):
+            fn(p)
+    for _ in range(3):
+        setup()
+        iterate(5)
+    t_setup = events(lambda: None, setup)
+    t_round = events(setup, lambda: iterate(5))
+    t_find = events(setup, lambda: iterate(MAXI))
+    t_round_serial = events(setup, lambda: serial(lambda p: iterate(5, 1, p)))
+    t_find_serial = events(setup, lambda: serial(lambda p: iterate(MAXI, 1, p)))
+    t_setup_serial = events(lambda: None, lambda: serial(lambda p: setup(1, p)))
+    # ComputeSim3's loop: rounds of iterate(5), the finished candidates discarded
+    # (the discard flags are read back every round, as the reference's loop reads them)
+    setup()
+    active = np.ones(P, np.uint8)
+    rounds, t0 = 0, time.perf_counter()
+    while active.any() and rounds < 61:
+        act = dev(active)
+        iterate(5, active=act.data_ptr())
+        r = results()
+        active &= ((r["no_more"] == 0) & (r["has_sim3"] == 0)).astype(np.uint8)
+        rounds += 1
+    loop_ms = (time.perf_counter() - t0) * 1e3
+    found = int(results()["has_sim3"].sum())
+    # exact check: find() on four problems against the restatement
+    setup()
+    iterate(MAXI)
+    r = results()
+    st = state.cpu().numpy().view(STATE_DTYPE)
+    exact = True
+    for p in (0, 1, P // 2, P - 1):
+        ref = probs[p].solver()
+        T, no_more, vb, n = ref.iterate(MAXI)
+        exact &= st[p].tobytes() == ref.state_record().tobytes()
+        exact &= r[p].tobytes() == ref.result_record(T, no_more, n).tobytes()
+    return {"config": "S1", "library": str(orb.LIB_PATH),
+            "workload": f"Sim3Solver, {P} candidates x {int(np.mean(st['n']))} correspondences "
+                        f"on average ({int(st['n'].min())}-{int(st['n'].max())}), {S} keypoint "
+                        f"slots, 45 gross outliers each, probability 0.99, min_inliers 20, "
+                        f"max_iterations {MAXI}",
+            "setup_ms": t_setup, "iterate5_ms": t_round, "find_ms": t_find,
+            "setup_serial_ms": t_setup_serial, "iterate5_serial_ms": t_round_serial,
+            "find_serial_ms": t_find_serial,
+            "iterate5_serial_over_batch": t_round_serial["median"] / t_round["median"],
+            "find_serial_over_batch": t_find_serial["median"] / t_find["median"],
+            "compute_sim3_rounds": rounds, "compute_sim3_loop_host_ms": loop_ms,
+            "found": found, "iterations_mean": float(st["iterations"].mean()),
+            "iterations_max": int(st["iterations"].max()),
+            "max_stride": orb.sim3_solver_max_stride(), "exact_vs_restatement": bool(exact)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--configs", default="C1,C2,C3,C5")
@@ -950,6 +1061,8 @@ def main():
             r = m1(args, orb, oracle, torch)
         elif c == "B1":
             r = b1(args, orb, oracle, torch)
+        elif c == "S1":
+            r = s1(args, orb, oracle, torch)
         else:
             raise SystemExit(f"unknown config {c}")
         print(json.dumps(r), flush=True)
