@@ -588,8 +588,9 @@ orb_status_t orb_match_bow(orb_matcher_t* m, int n_kf, const uint8_t* kf_desc,
  * prev_matched[i] (x, y pairs); f2's grid bounds are min_x..max_y.
  * matches12[i] = F2 index or -1; prev_matched is updated in place for matched
  * keypoints (:571-574); *nmatches = the reference's return value.  Host buffers;
- * both frames must have fewer than 2^19 keypoints and 4 * 4 * max(N1, N2) bytes
- * must fit the 160 KiB LDS of one CU (N <= 10240), else ORB_ECAPACITY. */
+ * 4 * 4 * max(N1, N2) bytes (N rounded up to a multiple of 4) and the kernel's
+ * 128 static bytes must fit the 160 KiB LDS of one CU (N <= 10232), else
+ * ORB_ECAPACITY. */
 orb_status_t orb_search_for_initialization(orb_matcher_t* m, const orb_frame_t* f1,
                                            const orb_frame_t* f2, float* prev_matched,
                                            int window_size, float nnratio,

@@ -1038,6 +1038,22 @@ class ORBmatcher:
             int(self.mbCheckOrientation), d_prev, d_matches12, d_nmatches, stream or None),
             "search_for_initialization_batch")
 
+    @staticmethod
+    def search_init_limits() -> dict:
+        """The SearchForInitialization kernels' sizes, read from the build: `topk`
+        (sorted candidates kept per query), `list` (candidates listed per query),
+        `stage` (level-0 F2 keypoints staged in LDS) and `max_stride` (largest
+        kp_stride / keypoint count accepted).  Callable without a device."""
+        L, out = lib(), {}
+        for key, name, res in (("topk", "orb_k_init_topk", ctypes.c_size_t),
+                               ("list", "orb_k_init_list_len", ctypes.c_size_t),
+                               ("stage", "orb_k_init_stage", ctypes.c_size_t),
+                               ("max_stride", "orb_k_init_max_stride", ctypes.c_int)):
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = res, []
+            out[key] = int(fn())
+        return out
+
     # ----------------------------------------------------- undistortion (Frame)
     @staticmethod
     def _cam(K, dist):

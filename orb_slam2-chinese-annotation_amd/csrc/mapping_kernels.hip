@@ -36,6 +36,9 @@
 #define INIT_LIST 256
 #define INIT_STAGE 1536  // F2 level-0 keypoints staged in LDS (48 B each)
 #define INIT_WG 256
+#define INIT_HIST_BINS 32                       // k_init_resolve's static LDS:
+#define INIT_STATIC_LDS (INIT_HIST_BINS * 4)    // the rotation histogram
+#define INIT_LDS_LIMIT (160 * 1024)             // LDS of one workgroup, gfx950
 
 // (InitParams, InitKey: orb_kernel_params.h)
 
@@ -246,7 +249,7 @@ __global__ __launch_bounds__(64) void k_init_resolve(
   // batch per F2 keypoint, and the F2 keypoint each i1 accepted (even if it
   // was stolen later: its histogram entry stays, :524-527)
   extern __shared__ __attribute__((aligned(16))) int sm[];
-  __shared__ int hist[32];
+  __shared__ int hist[INIT_HIST_BINS];
   const int p = blockIdx.x, lane = threadIdx.x;
   const int N1 = n1s[p], N2 = n2s[p], NQ = nQ[p];
   const int n2pad = (N2 + 3) & ~3;
@@ -391,11 +394,19 @@ __global__ __launch_bounds__(64) void k_init_resolve(
 
 extern "C" size_t orb_k_init_list_len(void) { return INIT_LIST; }
 extern "C" size_t orb_k_init_topk(void) { return INIT_TOPK; }
+extern "C" size_t orb_k_init_stage(void) { return INIT_STAGE; }
 
-// LDS bytes of k_init_resolve for a problem stride (both frames <= kpStride).
+// Dynamic LDS bytes of k_init_resolve for a problem stride (both frames <=
+// kpStride).  The kernel holds INIT_STATIC_LDS bytes more (hist).
 extern "C" size_t orb_k_init_lds(int kpStride) {
   const size_t pad = ((size_t)kpStride + 3) & ~(size_t)3;
   return (3 * pad + pad) * 4;
+}
+
+// Largest stride whose dynamic and static LDS together fit one workgroup:
+// 16 B per padded slot + 128 B <= 163,840 B, so 10,232 (exactly 160 KiB).
+extern "C" int orb_k_init_max_stride(void) {
+  return (int)((INIT_LDS_LIMIT - INIT_STATIC_LDS) / 16);
 }
 
 // scratch: qList/qOrder/ncand [P][kpStride] int, nQ/nStage [P] int, stage [P][kpStride]
@@ -422,7 +433,7 @@ extern "C" hipError_t orb_k_search_init(const orb_keypoint_t* keys1, const uint8
   e = hipGetLastError();
   if (e != hipSuccess) return e;
   const size_t lds = orb_k_init_lds(kpStride);
-  if (lds > 160 * 1024) return hipErrorInvalidValue;
+  if (lds + INIT_STATIC_LDS > INIT_LDS_LIMIT) return hipErrorInvalidValue;
   if (lds > 65536) {
     e = hipFuncSetAttribute((const void*)k_init_resolve,
                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);

@@ -146,6 +146,8 @@ hipError_t orb_k_triangulation(const orb_keypoint_t* k1, const uint8_t* d1, cons
 // ------------------------------------------------------ mapping_kernels.hip
 size_t orb_k_init_list_len(void);
 size_t orb_k_init_topk(void);
+size_t orb_k_init_stage(void);
+int orb_k_init_max_stride(void);
 size_t orb_k_init_lds(int kpStride);
 hipError_t orb_k_search_init(const orb_keypoint_t* keys1, const uint8_t* desc1, const int32_t* n1,
                              const orb_keypoint_t* keys2, const uint8_t* desc2, const int32_t* n2,

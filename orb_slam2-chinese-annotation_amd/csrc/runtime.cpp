@@ -1907,8 +1907,13 @@ static orb_status_t search_init_device(orb_matcher_t* m, int P, const orb_keypoi
   return ORB_OK;
 }
 
+// k_init_resolve keeps 16 B per slot of the stride (rounded up to 4 slots) in
+// dynamic LDS beside its 128 B static histogram; both must fit the 160 KiB of
+// one workgroup, so the largest stride is orb_k_init_max_stride() = 10,232
+// (163,712 + 128 = 163,840 B).  Counting the dynamic block alone let 10,233 to
+// 10,240 through to a launch that asks for more than the CU has.
 static bool init_stride_ok(int kp_stride) {
-  return kp_stride > 0 && kp_stride < (1 << 19) && orb_k_init_lds(kp_stride) <= 160 * 1024;
+  return kp_stride > 0 && kp_stride <= orb_k_init_max_stride();
 }
 
 orb_status_t orb_search_for_initialization(orb_matcher_t* m, const orb_frame_t* f1,

@@ -261,7 +261,9 @@ def grid_cells(keys, width, height):
     return cells, invW, invH
 
 
-def features_in_area(keys, cells, invW, invH, x, y, r, minL, maxL):
+def features_in_area(keys, cells, invW, invH, x, y, r, minL, maxL, closed=False):
+    """`closed` switches the window's strict `<` to the wrong neighbour `<=`
+    (sensitivity tests only)."""
     x, y, r = f32(x), f32(y), f32(r)
     x0 = max(0, int(math.floor(float(f32(f32(x - r) * invW)))))
     if x0 >= 64:
@@ -283,7 +285,8 @@ def features_in_area(keys, cells, invW, invH, x, y, r, minL, maxL):
                 k = keys[i]
                 if check and (k["octave"] < minL or (maxL >= 0 and k["octave"] > maxL)):
                     continue
-                if abs(f32(k["x"] - x)) < r and abs(f32(k["y"] - y)) < r:
+                dx, dy = abs(f32(k["x"] - x)), abs(f32(k["y"] - y))
+                if (dx <= r and dy <= r) if closed else (dx < r and dy < r):
                     out.append(i)
     return out
 
@@ -394,9 +397,19 @@ def _three_maxima(counts, ge=False):
 
 
 def search_for_initialization(keys1, desc1, keys2, desc2, width, height, prev, window,
-                              nnratio, check_ori):
+                              nnratio, check_ori, rules=(), trace=None):
     """Independent restatement of ORBmatcher::SearchForInitialization
-    (src/ORBmatcher.cc:429-577) in plain Python."""
+    (src/ORBmatcher.cc:429-577) in plain Python.
+
+    `rules` names wrong neighbours of the reference's rules (sensitivity tests
+    only): mdist_lt (skip on vMatchedDistance < d), th_lt (best < 50), ratio_le
+    (best <= second * nnratio), window_le (|dx| <= r), tie_last (the last
+    minimum in scan order), no_stolen_vote (a stolen query's histogram entry
+    goes with its match), no_level_f1 / no_level_f2 (the level filter dropped).
+    `trace`, a list, receives one dict per level-0 query in processing order:
+    i1, cand [(i2, distance) in scan order], mdist (vMatchedDistance of each
+    candidate when the query is processed), b1, b2, bi, accept, stole (the
+    previous owner or -1)."""
     cells, invW, invH = grid_cells(keys2, width, height)
     prev = np.array(prev, np.float32).reshape(len(keys1), 2).copy()
     m12 = np.full(len(keys1), -1, np.int32)
@@ -404,26 +417,42 @@ def search_for_initialization(keys1, desc1, keys2, desc2, width, height, prev, w
     m21 = [-1] * len(keys2)
     hist = [[] for _ in range(30)]
     n = 0
+    lvl2 = (-1, -1) if "no_level_f2" in rules else (0, 0)
     for i1 in range(len(keys1)):
-        if keys1[i1]["octave"] > 0:
+        if keys1[i1]["octave"] > 0 and "no_level_f1" not in rules:
             continue
-        idx = features_in_area(keys2, cells, invW, invH, prev[i1, 0], prev[i1, 1], window, 0, 0)
+        idx = features_in_area(keys2, cells, invW, invH, prev[i1, 0], prev[i1, 1], window,
+                               lvl2[0], lvl2[1], closed="window_le" in rules)
+        t = dict(i1=i1, cand=[], mdist=[], b1=1 << 31, b2=1 << 31, bi=-1, accept=False, stole=-1)
+        if trace is not None:
+            trace.append(t)
         if not idx:
             continue
         b1, b2, bi = 1 << 31, 1 << 31, -1
         for i2 in idx:
             d = hamming(desc1[i1], desc2[i2])
-            if mdist[i2] <= d:
+            t["cand"].append((i2, d))
+            t["mdist"].append(mdist[i2])
+            if (mdist[i2] < d) if "mdist_lt" in rules else (mdist[i2] <= d):
                 continue
-            if d < b1:
+            if d < b1 or ("tie_last" in rules and d == b1):
                 b2, b1, bi = b1, d, i2
             elif d < b2:
                 b2 = d
-        if b1 <= 50 and f32(b1) < f32(f32(b2) * f32(nnratio)):
+        t.update(b1=b1, b2=b2, bi=bi)
+        low = b1 < 50 if "th_lt" in rules else b1 <= 50
+        lim = f32(f32(b2) * f32(nnratio))
+        if low and (f32(b1) <= lim if "ratio_le" in rules else f32(b1) < lim):
             if m21[bi] >= 0:
+                t["stole"] = m21[bi]
                 m12[m21[bi]] = -1
                 n -= 1
+                if "no_stolen_vote" in rules:
+                    for h in hist:
+                        if m21[bi] in h:
+                            h.remove(m21[bi])
             m12[i1], m21[bi], mdist[bi] = bi, i1, b1
+            t["accept"] = True
             n += 1
             if check_ori:
                 hist[_rot_bin(keys1[i1]["angle"], keys2[bi]["angle"])].append(i1)
@@ -442,17 +471,20 @@ def search_for_initialization(keys1, desc1, keys2, desc2, width, height, prev, w
     return n, m12, prev
 
 
-def distinctive_descriptor(desc):
-    """MapPoint::ComputeDistinctiveDescriptors' BestIdx (src/MapPoint.cc:285-318)."""
+def distinctive_descriptor(desc, rules=()):
+    """MapPoint::ComputeDistinctiveDescriptors' BestIdx (src/MapPoint.cc:285-318).
+    `rules` (sensitivity tests only): median_upper (index n / 2 for
+    (n - 1) / 2), best_le (the last row with the smallest median)."""
     n = len(desc)
     if n == 0:
         return -1
     bits = np.unpackbits(desc, axis=1).astype(np.int32)
     D = (bits[:, None, :] != bits[None, :, :]).sum(-1)
+    k = n // 2 if "median_upper" in rules else int(0.5 * (n - 1))
     best, bi = 1 << 31, 0
     for i in range(n):
-        med = int(np.sort(D[i])[int(0.5 * (n - 1))])
-        if med < best:
+        med = int(np.sort(D[i])[k])
+        if med <= best if "best_le" in rules else med < best:
             best, bi = med, i
     return bi
 

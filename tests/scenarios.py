@@ -172,7 +172,8 @@ def observation_sets(rng, n_mp, max_obs=40, flip=0.08):
     lists, a few long ones; duplicated rows create median ties."""
     counts = rng.integers(1, max_obs + 1, n_mp)
     counts[rng.random(n_mp) < 0.05] = 0
-    counts[rng.random(n_mp) < 0.02] = rng.integers(65, 300)
+    long = rng.random(n_mp) < 0.02
+    counts[long] = rng.integers(65, 300, size=int(long.sum()))   # a length per long list
     offs = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
     desc = np.zeros((int(offs[-1]), 32), np.uint8)
     for p in range(n_mp):

@@ -3,6 +3,7 @@ against the CPU oracle: assignments index-exact, vbPrevMatched bit-exact."""
 import numpy as np
 import pytest
 
+import mapping_edge_cases
 import scenarios
 
 pytestmark = pytest.mark.gpu
@@ -32,33 +33,19 @@ def test_search_for_initialization(gpu, oracle, seed, frame2, w, h):
 @pytest.mark.parametrize("window,check", [(10, True), (50, False), (400, True), (2000, False)])
 def test_search_for_initialization_windows(gpu, oracle, window, check):
     # window 2000 covers the frame: every level-0 keypoint is a candidate
-    # (> INIT_LIST of them -> the whole-window rescan path)
+    # (> INIT_LIST of them, so the lists are cut short; every query still
+    # commits from its top-K, the whole-window rescan does not run here)
     s = scenarios.init_pair(oracle, 6, 1, w=640, h=480, nf=2000)
     (rn, rm, rp), (n, m12, prev) = _init_both(gpu, oracle, s, window, 0.9, check)
     assert n == rn and np.array_equal(m12, rm) and prev.tobytes() == rp.tobytes()
 
 
 def test_search_for_initialization_collisions(gpu, oracle):
-    # few distinct descriptors in a small area: steals, vMatchedDistance skips,
-    # batch conflicts and exhausted top-K lists on almost every query
-    rng = np.random.default_rng(11)
-    n1, n2 = 700, 500
-    k1 = np.zeros(n1, oracle.KEYPOINT_DTYPE)
-    k2 = np.zeros(n2, oracle.KEYPOINT_DTYPE)
-    for k, n in ((k1, n1), (k2, n2)):
-        k["x"] = rng.uniform(200, 260, n)
-        k["y"] = rng.uniform(200, 260, n)
-        k["angle"] = rng.uniform(0, 360, n)
-        k["octave"] = np.where(rng.random(n) < 0.8, 0, 1)
-    base = rng.integers(0, 256, (12, 32), dtype=np.uint8)
-    d1 = base[rng.integers(0, 12, n1)].copy()
-    d2 = base[rng.integers(0, 12, n2)].copy()
-    for d in (d1, d2):
-        bits = np.unpackbits(d, axis=1)
-        bits ^= (rng.random(bits.shape) < rng.uniform(0, 0.12, (len(d), 1))).astype(np.uint8)
-        d[:] = np.packbits(bits, axis=1)
-    prev = np.stack([k1["x"], k1["y"]], 1) + rng.uniform(-5, 5, (n1, 2)).astype(np.float32)
-    s = dict(k1=k1, d1=d1, k2=k2, d2=d2, prev=prev.astype(np.float32), w=640, h=480)
+    # few distinct descriptors in a small area: steals (chains of up to four),
+    # vMatchedDistance skips and batch conflicts.  No query's
+    # top-K list runs dry here (census in test_mapping_edge_cases.py): the
+    # list resolve and the rescan are reached by test_gpu_mapping_edges.py
+    s = mapping_edge_cases.crowd_collisions()
     for window, check in ((20, True), (40, False), (100, True)):
         (rn, rm, rp), (n, m12, p) = _init_both(gpu, oracle, s, window, 0.9, check)
         assert rn > 5
@@ -67,22 +54,7 @@ def test_search_for_initialization_collisions(gpu, oracle):
 
 def test_search_for_initialization_unstaged(gpu, oracle):
     # more level-0 F2 keypoints than the LDS stage holds: global grid scan path
-    rng = np.random.default_rng(12)
-    n = 2600
-    k1 = np.zeros(n, oracle.KEYPOINT_DTYPE)
-    k2 = np.zeros(n, oracle.KEYPOINT_DTYPE)
-    for k in (k1, k2):
-        k["x"] = rng.uniform(0, 640, n)
-        k["y"] = rng.uniform(0, 480, n)
-        k["angle"] = rng.uniform(0, 360, n)
-    base = rng.integers(0, 256, (40, 32), dtype=np.uint8)
-    d1 = base[rng.integers(0, 40, n)].copy()
-    d2 = base[rng.integers(0, 40, n)].copy()
-    for d in (d1, d2):
-        bits = np.unpackbits(d, axis=1)
-        bits ^= (rng.random(bits.shape) < 0.05).astype(np.uint8)
-        d[:] = np.packbits(bits, axis=1)
-    s = dict(k1=k1, d1=d1, k2=k2, d2=d2, prev=np.stack([k1["x"], k1["y"]], 1), w=640, h=480)
+    s = mapping_edge_cases.crowd_unstaged()
     (rn, rm, rp), (got_n, m12, p) = _init_both(gpu, oracle, s, 30, 0.9, True)
     assert rn > 10
     assert got_n == rn and np.array_equal(m12, rm) and p.tobytes() == rp.tobytes()
