@@ -91,6 +91,12 @@
  *                                  src/LoopClosing.cc)
  *   orb_sim3_solver_iterate_batch  Sim3Solver::iterate / find :144-220 with ComputeSim3
  *                                  :237-351, CheckInliers :354-378 and Project :396-417
+ *   orb_scene_median_depth(_batch) KeyFrame::ComputeSceneMedianDepth src/KeyFrame.cc:658-694
+ *   orb_create_new_map_points(_batch)  LocalMapping::CreateNewMapPoints: the neighbour
+ *                                  loop's gate src/LocalMapping.cc:289-311 and body :338-535
+ *                                  (parallax test, linear triangulation, both reprojection
+ *                                  checks, scale consistency) with the new point's
+ *                                  MapPoint::UpdateNormalAndDepth src/MapPoint.cc:349-402
  *   orb_vocabulary_create / _load_text / _destroy
  *                                  DBoW2 TemplatedVocabulary ctor + loadFromTextFile
  *                                  Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:1362-1448
@@ -1407,6 +1413,199 @@ orb_status_t orb_sim3_solver_iterate_batch(
     orb_sim3_corr_t* d_corr, const uint32_t* d_draws, int draw_stride, uint32_t rand_max,
     int max_iterations, int n_iterations, const uint8_t* d_active, uint8_t* d_inliers12,
     orb_sim3_result_t* d_result, void* stream);
+
+/* ------------------------------- LocalMapping::CreateNewMapPoints on the device */
+
+/* KeyFrame::ComputeSceneMedianDepth(q) (src/KeyFrame.cc:658-694) for n_problems
+ * keyframe slots in the slot layout of orb_match_bow_batch /
+ * orb_sim3_solver_setup_batch: problem p names slot d_slot[p] (NULL: slot p),
+ * whose count d_kf_nkeys[k] is clamped to [0, kp_stride], whose
+ * GetMapPointMatches() are indices into d_points at d_kf_point_index + k *
+ * kp_stride (any negative value is NULL; the reference does not ask isBad) and
+ * whose pose is d_kf_pose[k] (rcw row 2 and tcw[2] are read).  pos of d_points
+ * is read; the caller keeps every non-negative index inside it (NOT checked).
+ * Out: d_count[p] = vDepths.size(); d_median[p] = vDepths[(size - 1) / q] of
+ * the ascending depths, NaN when the keyframe has no point (the reference
+ * indexes an empty vector there).  The order statistic is found by rank
+ * counting over keys staged in LDS; "ascending" is the total order of the float
+ * bit patterns (-0 before +0, a NaN depth past the infinity of its sign), which
+ * is std::sort's order on everything the reference defines.
+ * Pin N1 below is the depth.  kp_stride above
+ * orb_scene_median_depth_max_stride() (4 bytes of LDS per slot in the 160 KiB of
+ * one CU; a pure function): ORB_ECAPACITY before any launch.  ORB_EINVAL: a null
+ * required pointer, n_problems < 0, kp_stride <= 0, q < 1.  n_problems == 0:
+ * ORB_OK, no launch.  Asynchronous on `stream`, no handle scratch. */
+orb_status_t orb_scene_median_depth_batch(
+    orb_matcher_t* m, int n_problems, const int32_t* d_slot, const int32_t* d_kf_nkeys,
+    const int32_t* d_kf_point_index, const orb_pose_t* d_kf_pose, int kp_stride,
+    const orb_map_point_t* d_points, int q, float* d_median, int32_t* d_count, void* stream);
+int orb_scene_median_depth_max_stride(void);
+/* One keyframe, host buffers: point_index[n] into points[n_points] (a
+ * non-negative index at or above n_points is ORB_EINVAL). */
+orb_status_t orb_scene_median_depth(orb_matcher_t* m, int n, const int32_t* point_index,
+                                    const orb_pose_t* pose, const orb_map_point_t* points,
+                                    int n_points, int q, float* median, int32_t* count);
+
+/* One status byte per keypoint of the current keyframe: one code per `continue`
+ * of the loop body (src/LocalMapping.cc:341-512). */
+#define ORB_NP_NOT_TRIED 0     /* the pair was gated (or the slot is past the count) */
+#define ORB_NP_NO_MATCH 1      /* match12[i1] < 0: not in vMatchedIndices */
+#define ORB_NP_ACCEPTED 2      /* a map point was created */
+#define ORB_NP_LOW_PARALLAX 3  /* :412-414 no stereo and very low parallax */
+#define ORB_NP_W_ZERO 4        /* :395 x3D.at<float>(3) == 0 */
+#define ORB_NP_Z1 5            /* :421 z1 <= 0 */
+#define ORB_NP_Z2 6            /* :425 z2 <= 0 */
+#define ORB_NP_REPROJ1 7       /* :447 / :458 */
+#define ORB_NP_REPROJ2 8       /* :474 / :485 */
+#define ORB_NP_ZERO_DIST 9     /* :498 dist1 == 0 || dist2 == 0 */
+#define ORB_NP_SCALE_RATIO 10  /* :511 */
+#define ORB_NP_UNDEFINED 11    /* undefined in the reference; rejected, see below */
+#define ORB_NP_NSTATUS 12
+
+typedef struct orb_new_point_info {
+  int32_t gated;        /* the pair was skipped at :299 / :309 */
+  int32_t overflow;     /* cursor + n_new > point_capacity: nothing else was written */
+  int32_t n_new;        /* nnew of this pair */
+  int32_t first_point;  /* the cursor before the call: point i is first_point + i */
+  int32_t counts[ORB_NP_NSTATUS]; /* keypoints per status; [ORB_NP_NOT_TRIED] stays 0 */
+} orb_new_point_info_t;  /* 64 bytes */
+
+/* The neighbour loop's gate (src/LocalMapping.cc:289-311) and body (:338-535)
+ * for n_problems (current keyframe, neighbour) pairs.  Problem p reads slots
+ * d_kf1_slot[p] (mpCurrentKeyFrame) and d_kf2_slot[p] (pKF2) of the slot arrays
+ * above plus d_kf_keys (mvKeysUn), d_kf_u_right (mvuRight) and d_kf_depth
+ * (mvDepth) at k * kp_stride (both NULL: monocular keyframes, every mvuRight
+ * is -1).  d_match12 + p * kp_stride holds what orb_search_for_triangulation
+ * writes: per keypoint of KF1 the index in KF2, or a negative value;
+ * vMatchedIndices is its non-negative entries in ascending index, each index of
+ * KF2 at most once (NOT checked).  ComputeF12 and the matcher are not part of
+ * this call, and neither is ComputeDistinctiveDescriptors
+ * (orb_distinctive_descriptors_batch).
+ * Host values: cam1, cam2 (all six fields; invfx = 1.0f / fx on the host as
+ * src/Frame.cc:115), scale_factors[n_levels] (mvScaleFactors; mfScaleFactor is
+ * read as scale_factors[1], which is 1.0f * scaleFactor exactly, so 2 <=
+ * n_levels <= 16), level_sigma2[n_levels] (mvLevelSigma2), monocular
+ * (mbMonocular).  d_median_depth[p] = ComputeSceneMedianDepth(2) of the
+ * neighbour (orb_scene_median_depth_batch), read only when monocular.
+ * Gate: baseline = (float)cv::norm(Ow2 - Ow1) (N3).  Stereo: baseline <
+ * cam2->mb skips the pair.  Monocular: (double)(baseline / median) < 0.01 skips
+ * it, and so does a NaN median.  A skipped pair writes info.gated = 1,
+ * first_point, zero counts and ORB_NP_NOT_TRIED for every keypoint below KF1's
+ * count; nothing else.
+ * Per match the reference's tests in its order, its two quirks included:
+ * cosParallaxStereo2 is evaluated only when KF1's keypoint is not stereo (the
+ * `else if` of :372), and KF2's right-image reprojection uses the current
+ * keyframe's mbf (:480).  bStereo = mvuRight >= 0.  The three branches are the
+ * linear triangulation (:383-399), UnprojectStereo(idx1) and
+ * UnprojectStereo(idx2) with the arithmetic of orb_unproject_stereo over
+ * d_kf_keys (KeyFrame::UnprojectStereo reads mvKeys; the stereo keyframes of
+ * this library are rectified, mvKeys == mvKeysUn).
+ * ORB_NP_UNDEFINED, tested before any arithmetic: idx2 at or above KF2's
+ * clamped count, an octave of either keypoint outside [0, n_levels), or a
+ * stereo flag on either keypoint whose depth is not > 0 (UnprojectStereo would
+ * return an empty Mat).  Nothing is indexed with the bad value.
+ * Out, per keypoint i1 below KF1's clamped count: d_status[p * kp_stride + i1];
+ * d_x3d + 3 * (p * kp_stride + i1) = x3D for every status that has one
+ * (ACCEPTED and Z1 .. SCALE_RATIO), untouched otherwise.
+ * Accepted matches in ascending i1 (the reference's creation order): the i-th
+ * becomes point c + i of d_points with c = d_point_cursor[d_cursor_index[p]]
+ * (a complete record: pos; normal, min_distance, max_distance as
+ * MapPoint::UpdateNormalAndDepth (src/MapPoint.cc:349-402) gives them for the
+ * observations {KF1, KF2} with reference keyframe KF1 -- with two observations
+ * the sum 0 + a + b of unit vectors does not depend on the std::map<KeyFrame*>
+ * order, float addition being commutative --; bad = 0, seen = 0, has_obs = 1,
+ * _pad = 0); d_new_pairs + 2 * (p * kp_stride + i) = (i1, idx2); c + i is
+ * stored at i1 of KF1's and at idx2 of KF2's d_kf_point_index row (the two
+ * AddMapPoint calls: the next neighbour's orb_search_for_triangulation must see
+ * them); the cursor advances by n_new.  d_info[p] as above.  If c < 0 or c +
+ * n_new > point_capacity the problem writes d_info[p] = {overflow = 1, rest 0}
+ * and nothing else.
+ * The caller's promises, NOT checked: the problems of one call share no cursor
+ * and no keyframe slot, and every slot number is inside the slot arrays.  The
+ * neighbours of one keyframe go in successive calls on one stream, as the
+ * reference runs them in sequence; the batch is independent keyframes / maps.
+ * Capacity: 16 bytes of LDS per slot (a problem's statuses and points wait
+ * there until its count is known); kp_stride above
+ * orb_create_new_map_points_max_stride() is ORB_ECAPACITY before any launch.
+ * ORB_EINVAL: a null required pointer (d_kf_u_right and d_kf_depth both or
+ * neither; d_median_depth required when monocular), n_problems < 0, kp_stride
+ * <= 0, point_capacity < 0, n_levels outside [2, 16], a scale factor or sigma2
+ * that is not finite and positive.  n_problems == 0: ORB_OK, no launch.
+ * Asynchronous on `stream`, no handle scratch, ordered by `stream` alone.
+ *
+ * Pins (the same list stands in tests/newpoints_ref.py and DESIGN.md 4.10;
+ * all unpinned against a real OpenCV).  Float expressions as written, no
+ * contraction; P-numbers are the Sim3 solver's pins above.
+ *  N1  Mat::dot of two 3-vectors (P11 below four elements): ((0 + p0) + p1) +
+ *      p2 with exact double products; row.dot(x) + t adds the float t widened,
+ *      in double, and narrows once: z of the median, x1 y1 z1 x2 y2 z2.
+ *  N2  xn = ((u - cx) * invfx, (v - cy) * invfy, 1); ray = Rwc * xn as 3 x 3 by
+ *      3 x 1 float products summed left to right: (rcw[i] x + rcw[3 + i] y) +
+ *      rcw[6 + i] * 1.0f.
+ *  N3  cv::norm (P8): the sqrt of a double sum, returned as a double.
+ *      cosParallaxRays = (float)(dot / (norm1 * norm2)), all in double (N1).
+ *  N4  cos(2 * atan2(mb / 2, depth)) on floats: a = (float)pinned_atan2 of the
+ *      widened mb / 2.0f and depth; (float) of pinned_sincos_d's cosine of the
+ *      widened 2.0f * a.  profiles/newpoints_libm.json counts how often glibc's
+ *      atan2f / cosf differ.
+ *  N5  A.row(r) = xn * T.row(2) - T.row(r) (addWeighted, beta = -1, gamma = 0):
+ *      (xn * T2k + Trk * -1.0f) + 0.0f per element, in float.
+ *  N6  cv::SVD::compute(A, w, u, vt, MODIFY_A | FULL_UV) on 4 x 4 float: OpenCV
+ *      3.x JacobiSVDImpl_<float> on At (row i of At = column i of A).  W[i] = the
+ *      double sum of squares of row i, k ascending from 0; Vt = I.  At most
+ *      max(m, 30) = 30 sweeps over the pairs i < j in order; p = the double dot
+ *      of rows i and j; the pair is skipped when |p| <= eps * sqrt(a * b), eps =
+ *      (double)(2 * FLT_EPSILON), a = W[i], b = W[j]; p *= 2; beta = a - b;
+ *      gamma = hypot(p, beta) = sqrt(p * p + beta * beta) in double (P7's
+ *      hypot, not narrowed); beta < 0: s = (float)sqrt(((gamma - beta) * 0.5) /
+ *      gamma), c = (float)(p / ((gamma * s) * 2)); otherwise c =
+ *      (float)sqrt((gamma + beta) / (gamma * 2)), s = (float)(p / ((gamma * c) *
+ *      2)); both rows of At and of Vt rotate in float: t0 = c * x + s * y, t1 =
+ *      (-s) * x + c * y; a and b are re-summed in double from the rotated rows;
+ *      the loop stops after a sweep without a rotation; W[i] = sqrt of the
+ *      re-summed squares; selection sort, descending: swap with the first later
+ *      maximum under strict <, the rows of Vt moving along.  Only vt.row(3) is
+ *      used; U's normalisation is not reproduced.
+ *  N7  x3D = v[0..2] / v[3] is Mat / double scalar, P2's statement: v * (float)
+ *      (1.0 / (double)v3) + 0.0f (adopted, as cvtScale_ evaluates it); one
+ *      correctly rounded float divide per element is the rejected alternative.
+ *      normali / cv::norm(normali) likewise: v * (float)(1.0 / norm) + 0.0f;
+ *      normal / n with n = 2: v * (float)(1.0 / 2.0) + 0.0f.
+ *  N8  UnprojectStereo: the statement of orb_unproject_stereo.
+ *  N9  double constants: (double)(ex * ex + ey * ey) > 5.991 * (double)sigma2,
+ *      the three-term float sum (ex ex + ey ey) + er er against 7.8 *
+ *      (double)sigma2; invz = (float)(1.0 / (double)z); cosParallaxRays <
+ *      0.9998 and baseline / median < 0.01 compared in double; u = (fx * x) *
+ *      invz + cx, u_r = u - mbf * invz in float; cosParallaxRays + 1 in float.
+ *  N10 dist = (float)cv::norm(x3D - Ow) (N3); ratioDist = dist2 / dist1,
+ *      ratioOctave = sf[o1] / sf[o2], ratioFactor = 1.5f * sf[1], max_distance =
+ *      dist1 * sf[o1], min_distance = max_distance / sf[n_levels - 1]: float. */
+orb_status_t orb_create_new_map_points_batch(
+    orb_matcher_t* m, int n_problems, const int32_t* d_kf1_slot, const int32_t* d_kf2_slot,
+    const orb_keypoint_t* d_kf_keys, const int32_t* d_kf_nkeys, int32_t* d_kf_point_index,
+    const orb_pose_t* d_kf_pose, const float* d_kf_u_right, const float* d_kf_depth,
+    int kp_stride, const int32_t* d_match12, const float* d_median_depth,
+    const orb_camera_t* cam1, const orb_camera_t* cam2, const float* scale_factors,
+    const float* level_sigma2, int n_levels, int monocular, orb_map_point_t* d_points,
+    int point_capacity, int32_t* d_point_cursor, const int32_t* d_cursor_index,
+    uint8_t* d_status, float* d_x3d, int32_t* d_new_pairs, orb_new_point_info_t* d_info,
+    void* stream);
+int orb_create_new_map_points_max_stride(void);
+/* One pair, host buffers.  keys / u_right / depth / point_index per keyframe
+ * (u_right1, depth1, u_right2, depth2 all NULL: monocular keyframes);
+ * point_index1[n1] and point_index2[n2] are updated in place; points
+ * [point_capacity] receives records *cursor .. *cursor + n_new - 1 and *cursor
+ * advances; status[n1], x3d[3 * n1], new_pairs[2 * n1] as above (entries the
+ * device leaves untouched keep the caller's value). */
+orb_status_t orb_create_new_map_points(
+    orb_matcher_t* m, int n1, const orb_keypoint_t* keys1, const float* u_right1,
+    const float* depth1, int32_t* point_index1, const orb_pose_t* pose1, int n2,
+    const orb_keypoint_t* keys2, const float* u_right2, const float* depth2,
+    int32_t* point_index2, const orb_pose_t* pose2, const int32_t* match12, float median_depth,
+    const orb_camera_t* cam1, const orb_camera_t* cam2, const float* scale_factors,
+    const float* level_sigma2, int n_levels, int monocular, orb_map_point_t* points,
+    int point_capacity, int32_t* cursor, uint8_t* status, float* x3d, int32_t* new_pairs,
+    orb_new_point_info_t* info);
 
 /* ------------------------------------------------------ DBoW2 vocabulary */
 

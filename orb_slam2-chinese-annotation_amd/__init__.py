@@ -74,6 +74,12 @@ SIM3_RESULT_DTYPE = np.dtype([("has_sim3", "<i4"), ("no_more", "<i4"), ("n_inlie
                               ("R", "<f4", (9,)), ("t", "<f4", (3,)), ("scale", "<f4")])
 assert SIM3_CORR_DTYPE.itemsize == 56 and SIM3_STATE_DTYPE.itemsize == 184
 assert SIM3_RESULT_DTYPE.itemsize == 132
+NEW_POINT_INFO_DTYPE = np.dtype([("gated", "<i4"), ("overflow", "<i4"), ("n_new", "<i4"),
+                                 ("first_point", "<i4"), ("counts", "<i4", (12,))])
+assert NEW_POINT_INFO_DTYPE.itemsize == 64
+# orb_new_point_info_t.counts / the status bytes (ORB_NP_*)
+(NP_NOT_TRIED, NP_NO_MATCH, NP_ACCEPTED, NP_LOW_PARALLAX, NP_W_ZERO, NP_Z1, NP_Z2, NP_REPROJ1,
+ NP_REPROJ2, NP_ZERO_DIST, NP_SCALE_RATIO, NP_UNDEFINED) = range(12)
 ORB_DEPTH_U16, ORB_DEPTH_F32 = 0, 1
 
 
@@ -258,6 +264,16 @@ def lib() -> ctypes.CDLL:
         "orb_sim3_solver_max_stride": (i32, []),
         "orb_sim3_solver_iterate_batch": (i32, [vp, i32, i32, vp, vp, vp, i32, ctypes.c_uint32,
                                                 i32, i32, vp, vp, vp, vp]),
+        "orb_scene_median_depth_batch": (i32, [vp, i32, vp, vp, vp, vp, i32, vp, i32, vp, vp, vp]),
+        "orb_scene_median_depth_max_stride": (i32, []),
+        "orb_scene_median_depth": (i32, [vp, i32, vp, vp, vp, i32, i32, vp, vp]),
+        "orb_create_new_map_points_batch": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp,
+                                                  vp, vp, vp, vp, vp, i32, i32, vp, i32, vp, vp,
+                                                  vp, vp, vp, vp, vp]),
+        "orb_create_new_map_points_max_stride": (i32, []),
+        "orb_create_new_map_points": (i32, [vp, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp,
+                                            vp, f32, vp, vp, vp, vp, i32, i32, vp, i32, vp, vp,
+                                            vp, vp, vp]),
         "orb_synth_image": (None, [ctypes.c_uint64, i32, i32, i32, i32, vp, sz]),
         "orb_synth_local_map": (None, [ctypes.c_uint64, vp, vp, i32, i32, i32, i32, vp, vp, vp]),
     }
@@ -269,7 +285,10 @@ def lib() -> ctypes.CDLL:
              "orb_update_local_map_batch", "orb_update_local_map_max_keyframes",
              "orb_track_local_merge_batch", "orb_track_local_map_finish_batch",
              "orb_sim3_solver_setup_batch", "orb_sim3_solver_max_stride",
-             "orb_sim3_solver_iterate_batch")
+             "orb_sim3_solver_iterate_batch", "orb_scene_median_depth_batch",
+             "orb_scene_median_depth_max_stride", "orb_scene_median_depth",
+             "orb_create_new_map_points_batch", "orb_create_new_map_points_max_stride",
+             "orb_create_new_map_points")
     for name, (res, args) in sig.items():
         if name in newer and "ORB_AMD_LIB" in os.environ and not hasattr(L, name):
             continue
@@ -1441,6 +1460,126 @@ class ORBmatcher:
     def sim3_solver_max_stride() -> int:
         """Largest kp_stride the Sim3Solver batch accepts."""
         return lib().orb_sim3_solver_max_stride()
+
+    # ----------------------------------------- LocalMapping::CreateNewMapPoints
+    def scene_median_depth_batch(self, n_problems, d_slot, d_kf_nkeys, d_kf_point_index,
+                                 d_kf_pose, kp_stride, d_points, d_median, d_count, q: int = 2,
+                                 stream: int = 0):
+        """KeyFrame::ComputeSceneMedianDepth(q) for n_problems keyframe slots
+        (orb_scene_median_depth_batch).  d_* are device addresses in the slot
+        layout of search_by_bow_batch; d_slot may be 0 (identity).  d_median:
+        n_problems floats (NaN for a keyframe without points), d_count:
+        n_problems int32.  Asynchronous on `stream`."""
+        _check(lib().orb_scene_median_depth_batch(
+            self._h, n_problems, d_slot or None, d_kf_nkeys or None, d_kf_point_index or None,
+            d_kf_pose or None, kp_stride, d_points or None, int(q), d_median or None,
+            d_count or None, stream or None), "scene_median_depth_batch")
+
+    def create_new_map_points_batch(self, n_problems, d_kf1_slot, d_kf2_slot, d_kf_keys,
+                                    d_kf_nkeys, d_kf_point_index, d_kf_pose, d_kf_u_right,
+                                    d_kf_depth, kp_stride, d_match12, d_median_depth, cam1, cam2,
+                                    scale_factors, level_sigma2, monocular, d_points,
+                                    point_capacity, d_point_cursor, d_cursor_index, d_status,
+                                    d_x3d, d_new_pairs, d_info, stream: int = 0):
+        """The gate and loop body of LocalMapping::CreateNewMapPoints for
+        n_problems (current keyframe, neighbour) pairs
+        (orb_create_new_map_points_batch).  d_* are device addresses;
+        d_kf_u_right / d_kf_depth 0: monocular keyframes; d_median_depth is read
+        only when `monocular`.  cam1, cam2: (fx, fy, cx, cy, bf, mb).  d_status:
+        n_problems x kp_stride bytes (NP_* codes), d_x3d: 3 floats per slot,
+        d_new_pairs: 2 int32 per slot, d_info: NEW_POINT_INFO_DTYPE records.
+        Asynchronous on `stream`."""
+        sf = np.ascontiguousarray(scale_factors, np.float32).reshape(-1)
+        ls = np.ascontiguousarray(level_sigma2, np.float32).reshape(-1)
+        if len(sf) != len(ls):
+            raise OrbError(ORB_EINVAL, "scale_factors and level_sigma2 differ in length")
+        c1, c2 = self._camera(cam1), self._camera(cam2)
+        _check(lib().orb_create_new_map_points_batch(
+            self._h, n_problems, d_kf1_slot or None, d_kf2_slot or None, d_kf_keys or None,
+            d_kf_nkeys or None, d_kf_point_index or None, d_kf_pose or None,
+            d_kf_u_right or None, d_kf_depth or None, kp_stride, d_match12 or None,
+            d_median_depth or None, ctypes.byref(c1), ctypes.byref(c2),
+            _ptr(sf) if len(sf) else None, _ptr(ls) if len(ls) else None, len(sf),
+            int(bool(monocular)), d_points or None, int(point_capacity), d_point_cursor or None,
+            d_cursor_index or None, d_status or None, d_x3d or None, d_new_pairs or None,
+            d_info or None, stream or None), "create_new_map_points_batch")
+
+    @staticmethod
+    def create_new_map_points_max_stride() -> int:
+        """Largest kp_stride create_new_map_points_batch accepts."""
+        return lib().orb_create_new_map_points_max_stride()
+
+    @staticmethod
+    def scene_median_depth_max_stride() -> int:
+        """Largest kp_stride scene_median_depth_batch accepts."""
+        return lib().orb_scene_median_depth_max_stride()
+
+    def ComputeSceneMedianDepth(self, point_index, pose, points, q: int = 2):
+        """KeyFrame::ComputeSceneMedianDepth(q) (src/KeyFrame.cc:658-694) for one
+        keyframe, host buffers: point_index = GetMapPointMatches() as indices
+        into `points` (MAP_POINT_DTYPE; negative NULL), pose a POSE_DTYPE record.
+        Returns (median float32, NaN without points; the number of depths)."""
+        pi = np.ascontiguousarray(point_index, np.int32).reshape(-1)
+        pts = np.ascontiguousarray(points, MAP_POINT_DTYPE).reshape(-1)
+        pose = np.ascontiguousarray(pose, POSE_DTYPE).reshape(1)
+        med, cnt = np.zeros(1, np.float32), np.zeros(1, np.int32)
+        _check(lib().orb_scene_median_depth(
+            self._h, len(pi), _ptr(pi) if len(pi) else None, _ptr(pose),
+            _ptr(pts) if len(pts) else None, len(pts), int(q), _ptr(med), _ptr(cnt)),
+            "ComputeSceneMedianDepth")
+        return med[0], int(cnt[0])
+
+    def CreateNewMapPoints(self, kf1, kf2, match12, cam1, cam2, scale_factors, level_sigma2,
+                           monocular, points, cursor, median_depth=float("nan"), status=None,
+                           x3d=None, new_pairs=None):
+        """The gate and loop body of LocalMapping::CreateNewMapPoints for one
+        (current keyframe, neighbour) pair, host buffers.  kf1 / kf2: dicts with
+        keys (KEYPOINT_DTYPE, mvKeysUn), u_right, depth (both None: monocular
+        keyframe), point_index (int32, updated in place) and pose (POSE_DTYPE).
+        points: a MAP_POINT_DTYPE array whose length is the capacity, updated in
+        place from `cursor` on.  Returns (info record, the cursor after the call,
+        status, x3d, new_pairs); the three arrays (given, or zero-filled) keep
+        their value where the call writes nothing."""
+        k1 = np.ascontiguousarray(kf1["keys"], KEYPOINT_DTYPE).reshape(-1)
+        k2 = np.ascontiguousarray(kf2["keys"], KEYPOINT_DTYPE).reshape(-1)
+        n1, n2 = len(k1), len(k2)
+        stereo = kf1.get("u_right") is not None or kf2.get("u_right") is not None
+        fa = lambda a, n: np.ascontiguousarray(
+            a if a is not None else np.full(n, -1, np.float32), np.float32).reshape(-1)
+        ur1, dp1 = fa(kf1.get("u_right"), n1), fa(kf1.get("depth"), n1)
+        ur2, dp2 = fa(kf2.get("u_right"), n2), fa(kf2.get("depth"), n2)
+        pi1, pi2 = kf1["point_index"], kf2["point_index"]
+        for a, n in ((pi1, n1), (pi2, n2)):
+            if not (isinstance(a, np.ndarray) and a.dtype == np.int32 and a.flags.c_contiguous
+                    and len(a) == n):
+                raise OrbError(ORB_EINVAL, "point_index: a contiguous int32 array per keypoint")
+        if not (isinstance(points, np.ndarray) and points.dtype == MAP_POINT_DTYPE
+                and points.flags.c_contiguous):
+            raise OrbError(ORB_EINVAL, "points: a contiguous MAP_POINT_DTYPE array")
+        m12 = np.ascontiguousarray(match12, np.int32).reshape(-1)
+        if len(m12) != n1:
+            raise OrbError(ORB_EINVAL, "match12: one entry per keypoint of kf1")
+        p1 = np.ascontiguousarray(kf1["pose"], POSE_DTYPE).reshape(1)
+        p2 = np.ascontiguousarray(kf2["pose"], POSE_DTYPE).reshape(1)
+        sf = np.ascontiguousarray(scale_factors, np.float32).reshape(-1)
+        ls = np.ascontiguousarray(level_sigma2, np.float32).reshape(-1)
+        if len(sf) != len(ls):
+            raise OrbError(ORB_EINVAL, "scale_factors and level_sigma2 differ in length")
+        status = np.zeros(n1, np.uint8) if status is None else status
+        x3d = np.zeros((n1, 3), np.float32) if x3d is None else x3d
+        new_pairs = np.zeros((n1, 2), np.int32) if new_pairs is None else new_pairs
+        cur = np.array([cursor], np.int32)
+        info = np.zeros(1, NEW_POINT_INFO_DTYPE)
+        c1, c2 = self._camera(cam1), self._camera(cam2)
+        q = lambda a, n: _ptr(a) if n else None
+        _check(lib().orb_create_new_map_points(
+            self._h, n1, q(k1, n1), q(ur1, n1 and stereo), q(dp1, n1 and stereo), q(pi1, n1),
+            _ptr(p1), n2, q(k2, n2), q(ur2, n2 and stereo), q(dp2, n2 and stereo), q(pi2, n2),
+            _ptr(p2), q(m12, n1), float(median_depth), ctypes.byref(c1), ctypes.byref(c2),
+            _ptr(sf) if len(sf) else None, _ptr(ls) if len(ls) else None, len(sf),
+            int(bool(monocular)), q(points, len(points)), len(points), _ptr(cur), q(status, n1),
+            q(x3d, n1), q(new_pairs, n1), _ptr(info)), "CreateNewMapPoints")
+        return info[0], int(cur[0]), status, x3d, new_pairs
 
     # ------------------------------------------ MapPoint::ComputeDistinctiveDescriptors
     def ComputeDistinctiveDescriptors(self, obs_offs, obs_desc, descriptors=None):

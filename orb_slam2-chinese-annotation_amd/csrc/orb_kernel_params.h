@@ -292,3 +292,46 @@ struct Sim3IterParams {
   uint8_t* inliers12;
   orb_sim3_result_t* result;
 };
+
+// ----------------------------------------------------- newpoints_kernels.hip
+// KeyFrame::ComputeSceneMedianDepth over nProblems keyframe slots (by value)
+struct MedianDepthParams {
+  int nProblems, stride, q;
+  const int32_t* slot;          // null: p
+  const int32_t* nkeys;
+  const int32_t* pointIndex;
+  const orb_pose_t* pose;
+  const orb_map_point_t* points;
+  float* median;
+  int32_t* count;
+};
+
+// LocalMapping::CreateNewMapPoints' gate and loop body over nProblems
+// (current keyframe, neighbour) pairs (by value)
+struct NewPointsParams {
+  int nProblems, stride;
+  const int32_t* kf1Slot;
+  const int32_t* kf2Slot;
+  const orb_keypoint_t* keys;
+  const int32_t* nkeys;
+  int32_t* pointIndex;          // in/out: the two AddMapPoint calls
+  const orb_pose_t* pose;
+  const float* uRight;          // null (with depth): monocular keyframes, all -1
+  const float* depth;
+  const int32_t* match12;
+  const float* medianDepth;     // read only when monocular
+  orb_map_point_t* points;
+  int pointCapacity;
+  int32_t* pointCursor;
+  const int32_t* cursorIndex;
+  float k1[4], inv1[2], bf1, mb1;  // fx fy cx cy, invfx invfy (1.0f / f on the host), mbf, mb
+  float k2[4], inv2[2], mb2;
+  int nLevels;
+  float scaleFactors[ORB_MAX_LEVELS], sigma2[ORB_MAX_LEVELS];
+  float ratioFactor;            // 1.5f * mfScaleFactor
+  int monocular;
+  uint8_t* status;
+  float* x3d;
+  int32_t* newPairs;
+  orb_new_point_info_t* info;
+};

@@ -249,4 +249,10 @@ hipError_t orb_k_local_map(const LocalMapParams* params, hipStream_t s);
 int orb_k_sim3_max_stride(void);
 hipError_t orb_k_sim3_setup(const Sim3SetupParams* params, hipStream_t s);
 hipError_t orb_k_sim3_iterate(const Sim3IterParams* params, hipStream_t s);
+// ---------------------------------------------------- newpoints_kernels.hip
+// largest kp_stride whose staged depth keys / statuses and points fit one CU's LDS
+int orb_k_median_depth_max_stride(void);
+int orb_k_new_points_max_stride(void);
+hipError_t orb_k_median_depth(const MedianDepthParams* params, hipStream_t s);
+hipError_t orb_k_new_points(const NewPointsParams* params, hipStream_t s);
 }

@@ -56,87 +56,7 @@ static size_t sim3_iter_lds(int stride) {
 }
 
 // --------------------------------------------------------------------- pins
-// P9: fdlibm's s_atan.c / e_atan2.c from IEEE operations alone
-__device__ __forceinline__ double pinned_atan(double x) {
-  const double atanhi[4] = {4.63647609000806093515e-01, 7.85398163397448278999e-01,
-                            9.82793723247329054082e-01, 1.57079632679489655800e+00};
-  const double atanlo[4] = {2.26987774529616870924e-17, 3.06161699786838301793e-17,
-                            1.39033110312309984516e-17, 6.12323399573676603587e-17};
-  const double aT0 = 3.33333333333329318027e-01, aT1 = -1.99999999998764832476e-01,
-               aT2 = 1.42857142725034663711e-01, aT3 = -1.11111104054623557880e-01,
-               aT4 = 9.09088713343650656196e-02, aT5 = -7.69187620504482999495e-02,
-               aT6 = 6.66107313738753120669e-02, aT7 = -5.83357013379057348645e-02,
-               aT8 = 4.97687799461593236017e-02, aT9 = -3.65315727442169155270e-02,
-               aT10 = 1.62858201153657823623e-02;
-  const int hx = (int)((unsigned long long)__double_as_longlong(x) >> 32);
-  const int ix = hx & 0x7fffffff;
-  if (ix >= 0x44100000) {  // |x| >= 2^66
-    if (x != x) return x + x;
-    return hx > 0 ? atanhi[3] + atanlo[3] : -atanhi[3] - atanlo[3];
-  }
-  int id;
-  if (ix < 0x3fdc0000) {  // |x| < 0.4375
-    if (ix < 0x3e200000) return x;  // |x| < 2^-29
-    id = -1;
-  } else {
-    x = __builtin_fabs(x);
-    if (ix < 0x3ff30000) {    // |x| < 1.1875
-      if (ix < 0x3fe60000) {  // 7/16 <= |x| < 11/16
-        id = 0;
-        x = (2.0 * x - 1.0) / (2.0 + x);
-      } else {
-        id = 1;
-        x = (x - 1.0) / (x + 1.0);
-      }
-    } else if (ix < 0x40038000) {  // |x| < 2.4375
-      id = 2;
-      x = (x - 1.5) / (1.0 + 1.5 * x);
-    } else {
-      id = 3;
-      x = -1.0 / x;
-    }
-  }
-  const double z = x * x, w = z * z;
-  const double s1 = z * (aT0 + w * (aT2 + w * (aT4 + w * (aT6 + w * (aT8 + w * aT10)))));
-  const double s2 = w * (aT1 + w * (aT3 + w * (aT5 + w * (aT7 + w * aT9))));
-  if (id < 0) return x - x * (s1 + s2);
-  const double hi = id == 0 ? atanhi[0] : id == 1 ? atanhi[1] : id == 2 ? atanhi[2] : atanhi[3];
-  const double lo = id == 0 ? atanlo[0] : id == 1 ? atanlo[1] : id == 2 ? atanlo[2] : atanlo[3];
-  const double r = hi - ((x * (s1 + s2) - lo) - x);
-  return hx < 0 ? -r : r;
-}
-
-__device__ __forceinline__ double pinned_atan2(double y, double x) {
-  const double pi = 3.1415926535897931160e+00, pi_o_2 = 1.5707963267948965580e+00,
-               pi_o_4 = 7.8539816339744827900e-01, pi_lo = 1.2246467991473531772e-16;
-  if (x != x || y != y) return x + y;
-  const unsigned long long bx = (unsigned long long)__double_as_longlong(x);
-  const unsigned long long by = (unsigned long long)__double_as_longlong(y);
-  const int hx = (int)(bx >> 32), hy = (int)(by >> 32);
-  const int ix = hx & 0x7fffffff, iy = hy & 0x7fffffff;
-  if (x == 1.0) return pinned_atan(y);
-  const int m = ((hy >> 31) & 1) | ((hx >> 30) & 2);  // 2 * sign(x) + sign(y)
-  if (y == 0.0) return m == 0 || m == 1 ? y : (m == 2 ? pi : -pi);
-  if (x == 0.0) return hy < 0 ? -pi_o_2 : pi_o_2;
-  const double inf = __builtin_inf();
-  if (__builtin_fabs(x) == inf) {
-    if (__builtin_fabs(y) == inf)
-      return m == 0 ? pi_o_4 : m == 1 ? -pi_o_4 : m == 2 ? 3.0 * pi_o_4 : -3.0 * pi_o_4;
-    return m == 0 ? 0.0 : m == 1 ? -0.0 : m == 2 ? pi : -pi;
-  }
-  if (__builtin_fabs(y) == inf) return hy < 0 ? -pi_o_2 : pi_o_2;
-  const int k = (iy - ix) >> 20;
-  double z;
-  if (k > 60) z = pi_o_2 + 0.5 * pi_lo;
-  else if (hx < 0 && k < -60) z = 0.0;
-  else z = pinned_atan(__builtin_fabs(y / x));
-  switch (m) {
-    case 0: return z;
-    case 1: return -z;
-    case 2: return pi - (z - pi_lo);
-    default: return (z - pi_lo) - pi;
-  }
-}
+// P9: pinned_atan / pinned_atan2 (fdlibm's s_atan.c / e_atan2.c) are in orb_device.h
 
 // P7's hypot
 __device__ __forceinline__ float sim3_hypot(float a, float b) {

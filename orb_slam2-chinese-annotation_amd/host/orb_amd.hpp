@@ -949,6 +949,107 @@ class ORBmatcher {
   }
   static int sim3_solver_max_stride() { return orb_sim3_solver_max_stride(); }
 
+  // LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:245-537) as device
+  // batches: KeyFrame::ComputeSceneMedianDepth(q) per keyframe slot
+  // (orb_scene_median_depth_batch) and the neighbour loop's gate and body per
+  // (current keyframe, neighbour) pair (orb_create_new_map_points_batch).
+  // d_slot may be null (identity); d_kf_u_right and d_kf_depth both null:
+  // monocular keyframes; d_median_depth is read only when `monocular`.
+  void scene_median_depth_batch(int n_problems, const int32_t* d_slot, const int32_t* d_kf_nkeys,
+                                const int32_t* d_kf_point_index, const orb_pose_t* d_kf_pose,
+                                int kp_stride, const orb_map_point_t* d_points, int q,
+                                float* d_median, int32_t* d_count, void* stream = nullptr) {
+    check(orb_scene_median_depth_batch(h_, n_problems, d_slot, d_kf_nkeys, d_kf_point_index,
+                                       d_kf_pose, kp_stride, d_points, q, d_median, d_count,
+                                       stream),
+          "scene_median_depth_batch");
+  }
+  void create_new_map_points_batch(
+      int n_problems, const int32_t* d_kf1_slot, const int32_t* d_kf2_slot,
+      const KeyPoint* d_kf_keys, const int32_t* d_kf_nkeys, int32_t* d_kf_point_index,
+      const orb_pose_t* d_kf_pose, const float* d_kf_u_right, const float* d_kf_depth,
+      int kp_stride, const int32_t* d_match12, const float* d_median_depth,
+      const orb_camera_t& cam1, const orb_camera_t& cam2, const std::vector<float>& scaleFactors,
+      const std::vector<float>& levelSigma2, bool monocular, orb_map_point_t* d_points,
+      int point_capacity, int32_t* d_point_cursor, const int32_t* d_cursor_index,
+      uint8_t* d_status, float* d_x3d, int32_t* d_new_pairs, orb_new_point_info_t* d_info,
+      void* stream = nullptr) {
+    assert(scaleFactors.size() == levelSigma2.size());
+    check(orb_create_new_map_points_batch(
+              h_, n_problems, d_kf1_slot, d_kf2_slot, d_kf_keys, d_kf_nkeys, d_kf_point_index,
+              d_kf_pose, d_kf_u_right, d_kf_depth, kp_stride, d_match12, d_median_depth, &cam1,
+              &cam2, scaleFactors.data(), levelSigma2.data(), (int)scaleFactors.size(),
+              monocular ? 1 : 0, d_points, point_capacity, d_point_cursor, d_cursor_index,
+              d_status, d_x3d, d_new_pairs, d_info, stream),
+          "create_new_map_points_batch");
+  }
+  static int scene_median_depth_max_stride() { return orb_scene_median_depth_max_stride(); }
+  static int create_new_map_points_max_stride() {
+    return orb_create_new_map_points_max_stride();
+  }
+
+  // One keyframe of LocalMapping::CreateNewMapPoints on host buffers, under the
+  // reference's names.  mvpMapPoints: GetMapPointMatches() as indices into the
+  // map's points (negative: NULL); a keyframe without stereo has empty mvuRight
+  // and mvDepth.
+  struct KeyFrameView {
+    std::vector<KeyPoint> mvKeysUn;
+    std::vector<float> mvuRight, mvDepth;
+    std::vector<int32_t> mvpMapPoints;
+    orb_pose_t pose;
+  };
+  // KeyFrame::ComputeSceneMedianDepth(q) (src/KeyFrame.cc:658-694): NaN when
+  // the keyframe has no point; nDepths receives vDepths.size().
+  float ComputeSceneMedianDepth(const KeyFrameView& kf, const std::vector<orb_map_point_t>& points,
+                                int q = 2, int* nDepths = nullptr) {
+    float median = 0.f;
+    int32_t count = 0;
+    check(orb_scene_median_depth(h_, (int)kf.mvpMapPoints.size(), kf.mvpMapPoints.data(),
+                                 &kf.pose, points.data(), (int)points.size(), q, &median, &count),
+          "ComputeSceneMedianDepth");
+    if (nDepths) *nDepths = count;
+    return median;
+  }
+  // The gate and loop body for (mpCurrentKeyFrame, pKF2) with the matches of
+  // SearchForTriangulation as match12 (per keypoint of the current keyframe
+  // the index in pKF2, or negative).  points.size() is the capacity; new points
+  // are written from `cursor` on, which advances; both keyframes' mvpMapPoints
+  // receive the new indices.  status, x3D (3 floats) and newPairs (2 ints) have
+  // one entry per keypoint of the current keyframe; entries the call does not
+  // write are zero.
+  orb_new_point_info_t CreateNewMapPoints(
+      KeyFrameView& current, KeyFrameView& kf2, const std::vector<int32_t>& match12,
+      const orb_camera_t& cam1, const orb_camera_t& cam2, const std::vector<float>& scaleFactors,
+      const std::vector<float>& levelSigma2, bool mbMonocular, float medianDepthKF2,
+      std::vector<orb_map_point_t>& points, int& cursor, std::vector<uint8_t>& status,
+      std::vector<float>& x3D, std::vector<int32_t>& newPairs) {
+    const size_t n1 = current.mvKeysUn.size(), n2 = kf2.mvKeysUn.size();
+    assert(match12.size() == n1 && current.mvpMapPoints.size() == n1 &&
+           kf2.mvpMapPoints.size() == n2 && scaleFactors.size() == levelSigma2.size());
+    const bool stereo = !current.mvuRight.empty() || !kf2.mvuRight.empty();
+    std::vector<float> ur1 = current.mvuRight, dp1 = current.mvDepth, ur2 = kf2.mvuRight,
+                       dp2 = kf2.mvDepth;
+    if (stereo) {
+      ur1.resize(n1, -1.f), dp1.resize(n1, -1.f), ur2.resize(n2, -1.f), dp2.resize(n2, -1.f);
+    }
+    status.assign(n1, 0);
+    x3D.assign(3 * n1, 0.0f);
+    newPairs.assign(2 * n1, 0);
+    orb_new_point_info_t info;
+    int32_t cur = cursor;
+    check(orb_create_new_map_points(
+              h_, (int)n1, current.mvKeysUn.data(), stereo ? ur1.data() : nullptr,
+              stereo ? dp1.data() : nullptr, current.mvpMapPoints.data(), &current.pose, (int)n2,
+              kf2.mvKeysUn.data(), stereo ? ur2.data() : nullptr, stereo ? dp2.data() : nullptr,
+              kf2.mvpMapPoints.data(), &kf2.pose, match12.data(), medianDepthKF2, &cam1, &cam2,
+              scaleFactors.data(), levelSigma2.data(), (int)scaleFactors.size(),
+              mbMonocular ? 1 : 0, points.data(), (int)points.size(), &cur, status.data(),
+              x3D.data(), newPairs.data(), &info),
+          "CreateNewMapPoints");
+    cursor = cur;
+    return info;
+  }
+
   float mfNNratio;
   bool mbCheckOrientation;
   orb_matcher_t* handle() { return h_; }

@@ -55,6 +55,13 @@ results table:
       the rounds to completion with the finished ones discarded, one find();
       against the same calls one problem at a time (64 launches) + exact check
       of four problems against tests/sim3_ref.py
+  N1  LocalMapping::CreateNewMapPoints: 64 (current keyframe, neighbour) pairs
+      of about 300 SearchForTriangulation matches each (384 keypoint slots,
+      mixed stereo / monocular keypoints, 12 % gross outliers), device-resident,
+      through the gate and the body in one launch, by device events (median of
+      20, minimum, maximum); the median-depth batch over the 64 neighbours;
+      against the same call one pair at a time (64 launches) + exact check of
+      four problems against tests/newpoints_ref.py
   R1  RGB-D: 640x480 (TUM1 intrinsics and distortion, DepthMapFactor 5000),
       1000 features, 256 frames per launch, device-resident: extract ->
       undistort -> ComputeStereoFromRGBD -> closest points + UnprojectStereo ->
@@ -62,7 +69,7 @@ results table:
       same pipeline without the RGB-D stages (monocular matcher), each new
       kernel alone by HIP events with its algorithmic bytes + exact check
 
-Usage: python tools/bench_configs.py [--configs C1,C2,C3,C5,F1,F3,P1,R1,T1,M1,B1,S1] [--steps K]
+Usage: python tools/bench_configs.py [--configs C1,C2,C3,C5,F1,F3,P1,R1,T1,M1,B1,S1,N1] [--steps K]
 The oracle (CPU restatement) is used only for the CPU rows and parity checks.
 """
 import argparse
@@ -1023,6 +1030,109 @@ def s1(args, orb, oracle, torch):
             "max_stride": orb.sim3_solver_max_stride(), "exact_vs_restatement": bool(exact)}
 
 
+def n1(args, orb, oracle, torch):
+    import newpoints_cases as NC
+    from newpoints_ref import MAP_POINT_DTYPE, NEW_POINT_INFO_DTYPE
+    P, S = 64, 384
+    rng = np.random.default_rng(41)
+    cases = [NC.natural_case(f"n{i}", 5000 + i, int(rng.integers(280, 321)), False, n_extra=20,
+                             n_exist=30) for i in range(P)]
+    b = NC.pack(cases, S)
+    cap = int(b["base"][-1])
+
+    def dev(a):
+        return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).cuda()
+    d = {k: dev(b[k]) for k in ("keys", "u_right", "depth", "pose", "nkeys", "match12",
+                                "kf1_slot", "kf2_slot", "median", "cursor_index")}
+    pidx0, cur0, pts0 = dev(b["point_index"]), dev(b["cursor"]), dev(b["points"])
+    pidx, cur, pts = pidx0.clone(), cur0.clone(), pts0.clone()
+    status = torch.zeros(P * S, dtype=torch.uint8, device="cuda")
+    x3d = torch.zeros(P * S * 3, dtype=torch.float32, device="cuda")
+    pairs = torch.zeros(P * S * 2, dtype=torch.int32, device="cuda")
+    info = torch.zeros(P * 64, dtype=torch.uint8, device="cuda")
+    med = torch.zeros(P, dtype=torch.float32, device="cuda")
+    cnt = torch.zeros(P, dtype=torch.int32, device="cuda")
+    m = orb.ORBmatcher(0.6, False)
+    stream = torch.cuda.Stream()
+    sp = stream.cuda_stream
+
+    def reset():
+        with torch.cuda.stream(stream):
+            pidx.copy_(pidx0)
+            cur.copy_(cur0)
+            pts.copy_(pts0)
+
+    def create(n=P, p0=0):
+        m.create_new_map_points_batch(
+            n, d["kf1_slot"].data_ptr() + 4 * p0, d["kf2_slot"].data_ptr() + 4 * p0,
+            d["keys"].data_ptr(), d["nkeys"].data_ptr(), pidx.data_ptr(), d["pose"].data_ptr(),
+            d["u_right"].data_ptr(), d["depth"].data_ptr(), S, d["match12"].data_ptr() + 4 * S * p0,
+            d["median"].data_ptr() + 4 * p0, NC.CAM_N, NC.CAM_N, NC.SCALE_FACTORS,
+            NC.LEVEL_SIGMA2, False, pts.data_ptr(), cap, cur.data_ptr(),
+            d["cursor_index"].data_ptr() + 4 * p0, status.data_ptr() + S * p0,
+            x3d.data_ptr() + 12 * S * p0, pairs.data_ptr() + 8 * S * p0, info.data_ptr() + 64 * p0,
+            sp)
+
+    def median():
+        m.scene_median_depth_batch(P, d["kf2_slot"].data_ptr(), d["nkeys"].data_ptr(),
+                                   pidx0.data_ptr(), d["pose"].data_ptr(), S, pts0.data_ptr(),
+                                   med.data_ptr(), cnt.data_ptr(), 2, sp)
+
+    def events(prep, fn, reps=20):
+        t = []
+        for _ in range(reps):
+            prep()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            fn()
+            e1.record(stream)
+            torch.cuda.synchronize()
+            t.append(e0.elapsed_time(e1))
+        t.sort()
+        return {"median": t[len(t) // 2], "min": t[0], "max": t[-1]}
+
+    for _ in range(3):
+        reset()
+        create()
+        median()
+    t_batch = events(reset, create)
+    t_serial = events(reset, lambda: [create(1, p) for p in range(P)])
+    t_median = events(lambda: None, median)
+    reset()
+    create()
+    torch.cuda.synchronize()
+    inf = info.cpu().numpy().view(NEW_POINT_INFO_DTYPE)
+    st = status.cpu().numpy().reshape(P, S)
+    xs = x3d.cpu().numpy().reshape(P, S, 3)
+    pt = pts.cpu().numpy().view(MAP_POINT_DTYPE)
+    exact = True
+    for p in (0, 1, P // 2, P - 1):
+        ref = cases[p].ref()
+        n1k = len(cases[p].match12)
+        lo, hi = int(b["base"][p]), int(b["base"][p + 1])
+        got = inf[p].copy()
+        got["first_point"] -= lo
+        exact &= got.tobytes() == ref["info"].tobytes()
+        exact &= st[p, :n1k].tobytes() == ref["status"].tobytes()
+        has = np.isin(ref["status"], (2, 5, 6, 7, 8, 9, 10))
+        exact &= xs[p, :n1k][has].tobytes() == ref["x3d"][has].tobytes()
+        exact &= pt[lo:hi].tobytes() == ref["points"].tobytes()
+    n_match = [int((c.match12 >= 0).sum()) for c in cases]
+    return {"config": "N1", "library": str(orb.LIB_PATH),
+            "workload": f"CreateNewMapPoints, {P} keyframe pairs x {int(np.mean(n_match))} matches "
+                        f"on average ({min(n_match)}-{max(n_match)}), {S} keypoint slots, stereo "
+                        f"keyframes (60 % stereo keypoints), 12 % gross outliers",
+            "create_ms": t_batch, "create_serial_ms": t_serial,
+            "create_serial_over_batch": t_serial["median"] / t_batch["median"],
+            "median_depth_ms": t_median, "n_new_mean": float(inf["n_new"].mean()),
+            "n_new_total": int(inf["n_new"].sum()), "gated": int(inf["gated"].sum()),
+            "status_counts": inf["counts"].sum(0).tolist(),
+            "max_stride": orb.ORBmatcher.create_new_map_points_max_stride(),
+            "kernel_resources": "k_new_points: 167 VGPRs, 106 SGPRs, no scratch, occupancy 3 "
+                                "waves/SIMD (hipcc -Rpass-analysis=kernel-resource-usage, gfx950)",
+            "exact_vs_restatement": bool(exact)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--configs", default="C1,C2,C3,C5")
@@ -1063,6 +1173,8 @@ def main():
             r = b1(args, orb, oracle, torch)
         elif c == "S1":
             r = s1(args, orb, oracle, torch)
+        elif c == "N1":
+            r = n1(args, orb, oracle, torch)
         else:
             raise SystemExit(f"unknown config {c}")
         print(json.dumps(r), flush=True)
