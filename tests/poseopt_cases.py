@@ -86,7 +86,7 @@ def run_ref(c, libm=False, **kw):
     k = c["keys"]
     return ref.pose_optimization(
         np.stack([k["x"], k["y"]], 1), k["octave"], c["u_right"], c["point_index"], c["points"],
-        c.get("levels", INV_LEVEL_SIGMA2), CAM, c["pose"]["rcw"][0], c["pose"]["tcw"][0],
+        c.get("levels", INV_LEVEL_SIGMA2), c.get("cam", CAM), c["pose"]["rcw"][0], c["pose"]["tcw"][0],
         c["pose"]["ow"][0], c["outlier"], libm=libm, **kw)
 
 

@@ -48,8 +48,9 @@ CHI2_STEREO = f32(7.815)  # :390
 
 
 # ------------------------------------------------------------------ pins
-def pinned_sincos_d(x: float):
-    """DESIGN.md App. A.6 without the final narrowing: (sin x, cos x) as doubles."""
+def pinned_sincos_d(x: float, trace=None):
+    """DESIGN.md App. A.6 without the final narrowing: (sin x, cos x) as doubles.
+    trace["quadrants"] collects the quadrant q of every finite argument."""
     if not math.isfinite(x):
         return math.nan, math.nan
     invpio2 = 6.36619772367581382433e-01
@@ -68,6 +69,8 @@ def pinned_sincos_d(x: float):
     w = 1.0 - hz
     cs = w + (((1.0 - w) - hz) + z * pc)
     q = int(min(max(k, -2147483648.0), 2147483647.0)) & 3  # the saturating (int)k of the device
+    if trace is not None:
+        trace["quadrants"].add(q)
     return ((sn, cs), (cs, -sn), (-sn, -cs), (-cs, sn))[q]
 
 
@@ -81,11 +84,14 @@ def _div(a: float, b: float) -> float:
 
 
 # ------------------------------------------------- Eigen closed forms (scalars)
-def quat_from_matrix(m):
-    """Eigen Quaterniond(Matrix3d): returns (x, y, z, w)."""
+def quat_from_matrix(m, branches=None):
+    """Eigen Quaterniond(Matrix3d): returns (x, y, z, w).  branches collects the
+    branch taken: "trace", or the index 0 / 1 / 2 of the largest diagonal entry."""
     t = (m[0][0] + m[1][1]) + m[2][2]
     q = [0.0, 0.0, 0.0, 0.0]
     if t > 0.0:
+        if branches is not None:
+            branches.add("trace")
         t = _sqrt(t + 1.0)
         q[3] = 0.5 * t
         t = _div(0.5, t)
@@ -98,6 +104,8 @@ def quat_from_matrix(m):
             i = 1
         if m[2][2] > m[i][i]:
             i = 2
+        if branches is not None:
+            branches.add(i)
         j = (i + 1) % 3
         k = (j + 1) % 3
         t = _sqrt(((m[i][i] - m[j][j]) - m[k][k]) + 1.0)
@@ -109,10 +117,13 @@ def quat_from_matrix(m):
     return q
 
 
-def normalize_rotation(q):
-    """SE3Quat::normalizeRotation (se3quat.h:280-285)."""
+def normalize_rotation(q, flips=None, where=None):
+    """SE3Quat::normalizeRotation (se3quat.h:280-285).  flips collects `where`
+    when the sign is flipped."""
     if q[3] < 0:
         q = [-q[0], -q[1], -q[2], -q[3]]
+        if flips is not None:
+            flips.add(where)
     n = _sqrt(((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3])
     return [_div(q[0], n), _div(q[1], n), _div(q[2], n), _div(q[3], n)]
 
@@ -176,7 +187,7 @@ def se3_exp(u, libm=False, trace=None):
             s, c = math.sin(theta), math.cos(theta)
             th3 = math.pow(theta, 3)
         else:
-            s, c = pinned_sincos_d(theta)
+            s, c = pinned_sincos_d(theta, trace if trace is not None and "quadrants" in trace else None)
             th3 = (theta * theta) * theta
         a = _div(s, theta)
         b = _div(1.0 - c, theta * theta)
@@ -184,21 +195,26 @@ def se3_exp(u, libm=False, trace=None):
         R = [[(eye[i][j] + a * Om[i][j]) + b * Om2[i][j] for j in range(3)] for i in range(3)]
         V = [[(eye[i][j] + b * Om[i][j]) + d * Om2[i][j] for j in range(3)] for i in range(3)]
     t = [(V[i][0] * up[0] + V[i][1] * up[1]) + V[i][2] * up[2] for i in range(3)]
-    return normalize_rotation(quat_from_matrix(R)), t
+    full = trace is not None and "quat_step" in trace
+    q = quat_from_matrix(R, trace["quat_step"] if full else None)
+    return normalize_rotation(q, trace["flips"] if full else None, "exp"), t
 
 
-def se3_mul(a, b):
+def se3_mul(a, b, trace=None):
     """SE3Quat::operator* (se3quat.h:104-110)."""
     qa, ta = a
     qb, tb = b
     r = quat_rotate(qa, tb[0], tb[1], tb[2])
-    return normalize_rotation(quat_mul(qa, qb)), [ta[0] + r[0], ta[1] + r[1], ta[2] + r[2]]
+    return (normalize_rotation(quat_mul(qa, qb), None if trace is None else trace["flips"], "mul"),
+            [ta[0] + r[0], ta[1] + r[1], ta[2] + r[2]])
 
 
-def to_se3quat(rcw, tcw):
+def to_se3quat(rcw, tcw, trace=None):
     """Converter::toSE3Quat (src/Converter.cc:39-49), SE3Quat(R, t) (se3quat.h:58-60)."""
     R = [[float(f32(rcw[3 * i + j])) for j in range(3)] for i in range(3)]
-    return normalize_rotation(quat_from_matrix(R)), [float(f32(v)) for v in tcw]
+    q = quat_from_matrix(R, None if trace is None else trace["quat_start"])
+    return (normalize_rotation(q, None if trace is None else trace["flips"], "start"),
+            [float(f32(v)) for v in tcw])
 
 
 def pose_from_se3quat(est):
@@ -214,9 +230,15 @@ def pose_from_se3quat(est):
 
 
 # ------------------------------------------------------------ LDLT<MatrixXd>
-def ldlt_solve(H, b, x_prev, pivots=None):
+def ldlt_solve(H, b, x_prev, pivots=None, trace=None, variants=()):
     """LinearSolverDense::solve (linear_solver_dense.h:104-112) on the lower
-    triangle of the 6x6 H: returns (ok, x); x = x_prev when !isPositive()."""
+    triangle of the 6x6 H: returns (ok, x); x = x_prev when !isPositive().
+    trace["pivots"] collects the (k, idx) pairs, trace["pivot_sequences"] the
+    whole transposition lists, trace["pivot_ties"] counts the
+    steps whose largest |diagonal| is held by more than one remaining entry.
+    variants (NOT the reference): "tie_last" takes the last of equal
+    magnitudes, "no_pivot" never swaps, "half_swap_<k><idx>" leaves the two
+    diagonal entries where they were in the swap of that one (k, idx)."""
     n = 6
     m = [list(r) for r in H]
     tr = [0] * n
@@ -224,15 +246,22 @@ def ldlt_solve(H, b, x_prev, pivots=None):
     for k in range(n):
         idx, best = k, abs(m[k][k])
         for i in range(k + 1, n):
-            if abs(m[i][i]) > best:
+            if abs(m[i][i]) > best or ("tie_last" in variants and abs(m[i][i]) == best):
                 idx, best = i, abs(m[i][i])
+        if "no_pivot" in variants:
+            idx = k
         tr[k] = idx
+        if trace is not None:
+            trace["pivots"].add((k, idx))
+            if [abs(m[i][i]) for i in range(k, n)].count(best) > 1:
+                trace["pivot_ties"] += 1
         if idx != k:
             for j in range(k):
                 m[k][j], m[idx][j] = m[idx][j], m[k][j]
             for r in range(idx + 1, n):
                 m[r][k], m[r][idx] = m[r][idx], m[r][k]
-            m[k][k], m[idx][idx] = m[idx][idx], m[k][k]
+            if "half_swap_%d%d" % (k, idx) not in variants:
+                m[k][k], m[idx][idx] = m[idx][idx], m[k][k]
             for i in range(k + 1, idx):
                 m[i][k], m[idx][i] = m[idx][i], m[i][k]
         if k > 0:
@@ -250,6 +279,8 @@ def ldlt_solve(H, b, x_prev, pivots=None):
             positive = False
     if pivots is not None:
         pivots[:] = tr
+    if trace is not None:
+        trace["pivot_sequences"].add(tuple(tr))
     if not positive:
         return False, list(x_prev)
     y = list(b)
@@ -272,12 +303,13 @@ def ldlt_solve(H, b, x_prev, pivots=None):
 
 
 # ------------------------------------------------------------ per-edge passes
-def huber(e, delta):
+def huber(e, delta, strict=False):
     """RobustKernelHuber::robustify (robust_kernel_impl.cpp:78-91), elementwise:
-    returns (rho0, rho1, inlier branch taken)."""
+    returns (rho0, rho1, inlier branch taken).  strict=True is NOT the
+    reference: it compares with < in place of <=."""
     dsqr = delta * delta
     with np.errstate(all="ignore"):
-        inl = e <= dsqr
+        inl = (e < dsqr) if strict else (e <= dsqr)
         sq = np.sqrt(e)
         return np.where(inl, e, (2 * sq) * delta - dsqr), np.where(inl, 1.0, delta / sq), inl
 
@@ -335,13 +367,28 @@ def _seq_sum(v):
 
 
 def pose_optimization(keys_xy, octave, u_right, point_index, points, inv_level_sigma2, cam,
-                      rcw, tcw, ow, outlier=None, libm=False, classify_from_final=False):
+                      rcw, tcw, ow, outlier=None, libm=False, classify_from_final=False,
+                      variants=()):
     """Optimizer::PoseOptimization (src/Optimizer.cc:243-477).  Returns a dict:
     rcw, tcw, ow (float32), outlier (uint8, slots without an edge as given),
     n_inliers, n_edges, lm_iterations, rejected_trials and `trace`.
     classify_from_final=True is NOT the reference: it classifies every edge at
     the final estimate, the behaviour the stale-error rule differs from (the
-    tests use it to show that the rule matters)."""
+    tests use it to show that the rule matters).  variants names further wrong
+    neighbours, none of them the reference either: "classify_ge" (chi2 >= the
+    threshold is an outlier), "huber_lt", "stereo_le" (mvuRight <= 0 is
+    monocular), "tie_last", "no_pivot" and "half_swap_<k><idx>" (ldlt_solve), "three_edges" (returns
+    below four edges), "ten_edges" (one round up to ten edges) and
+    "classify_from_final".
+    trace also holds: pivots, the set of (k, idx) over all solves,
+    pivot_sequences and pivot_ties; quat_start / quat_step, the Quaterniond(Matrix3d) branches of
+    toSE3Quat and of exp; flips, where normalizeRotation changed the sign
+    ("start", "exp", "mul"); quadrants of pinned_sincos_d; skipped_rounds, the
+    rounds whose optimize() had no active edge; max_theta, the largest step angle;
+    round_outliers, the edge positions flagged after each round; chi2_first, the
+    float32 chi2 values the first round classified."""
+    variants = tuple(variants)
+    classify_from_final = classify_from_final or "classify_from_final" in variants
     keys_xy = np.asarray(keys_xy, f32).reshape(-1, 2)
     n = len(keys_xy)
     octave = np.asarray(octave, np.int64)
@@ -353,7 +400,9 @@ def pose_optimization(keys_xy, octave, u_right, point_index, points, inv_level_s
     trace = dict(rounds=0, lm_iterations=0, rejected_trials=0, term_qmax=0, term_rho0=0, term_nbad=0,
                  term_iterations=0, stale_rounds=0, stale_chi_differs=0, stale_changed_flags=0, outlier_to_inlier=0,
                  exp_small=0, exp_large=0, huber_inlier=False, huber_outlier=False,
-                 not_positive=0, n_mono=0, n_stereo=0, ended=[])  # ended: the rule that ended each optimize()
+                 not_positive=0, n_mono=0, n_stereo=0, ended=[],  # ended: the rule that ended each optimize()
+                 pivots=set(), pivot_sequences=set(), pivot_ties=0, quat_start=set(), quat_step=set(), flips=set(),
+                 quadrants=set(), skipped_rounds=[], max_theta=0.0, round_outliers=[], chi2_first=None)
     res = dict(rcw=pose_in[0], tcw=pose_in[1], ow=pose_in[2], outlier=out_flags, n_inliers=0,
                n_edges=0, lm_iterations=0, rejected_trials=0, trace=trace)
     ei = np.nonzero(pidx >= 0)[0]  # :290-294, ascending keypoint order
@@ -364,9 +413,10 @@ def pose_optimization(keys_xy, octave, u_right, point_index, points, inv_level_s
         return res
     res["n_edges"] = E
     out_flags[ei] = 0  # :301, :342
-    if E < 3:  # :384-385
+    if E < (4 if "three_edges" in variants else 3):  # :384-385
         return res
-    stereo = ~(ur[ei] < 0)  # :298
+    with np.errstate(invalid="ignore"):
+        stereo = ~((ur[ei] <= 0) if "stereo_le" in variants else (ur[ei] < 0))  # :298
     trace["n_mono"], trace["n_stereo"] = int((~stereo).sum()), int(stereo.sum())
     X = np.asarray(points, f32).reshape(-1, 3)[pidx[ei]].astype(f64)
     obs = np.stack([keys_xy[ei, 0], keys_xy[ei, 1], ur[ei]], 1).astype(f64)
@@ -375,7 +425,7 @@ def pose_optimization(keys_xy, octave, u_right, point_index, points, inv_level_s
     thr = np.where(stereo, CHI2_STEREO, CHI2_MONO).astype(f32)
     flags = np.zeros(E, bool)  # mvbOutlier of the edges == their level
     robust = True
-    est0 = to_se3quat(rcw, tcw)
+    est0 = to_se3quat(rcw, tcw, trace)
     est = est0
     x = [0.0] * 6  # BlockSolver::_x: kept when the solver reports !ok
     n_bad_edges = 0
@@ -383,7 +433,7 @@ def pose_optimization(keys_xy, octave, u_right, point_index, points, inv_level_s
     def robust_chi2(chi2, act):
         """SparseOptimizer::activeRobustChi2 (sparse_optimizer.cpp:100-114)."""
         if robust:
-            r0, r1, inl = huber(chi2, ed.delta)
+            r0, r1, inl = huber(chi2, ed.delta, "huber_lt" in variants)
             if act.any():
                 trace["huber_inlier"] |= bool(inl[act].any())
                 trace["huber_outlier"] |= bool((~inl[act]).any())
@@ -436,10 +486,13 @@ def pose_optimization(keys_xy, octave, u_right, point_index, points, inv_level_s
                     Hl = [list(r) for r in H]
                     for j in range(6):
                         Hl[j][j] = H[j][j] + lam  # setLambda (block_solver.hpp:564-589)
-                    ok2, x = ldlt_solve(Hl, b, x)
+                    ok2, x = ldlt_solve(Hl, b, x, None, trace, variants)
                     if not ok2:
                         trace["not_positive"] += 1
-                    est = se3_mul(se3_exp(x, libm, trace), est)  # oplusImpl (.h:73-76)
+                    theta = _sqrt((x[0] * x[0] + x[1] * x[1]) + x[2] * x[2])
+                    if theta > trace["max_theta"]:
+                        trace["max_theta"] = theta
+                    est = se3_mul(se3_exp(x, libm, trace), est, trace)  # oplusImpl (.h:73-76)
                     _, _, _, chi2t = ed.error(est)
                     last_est = est
                     tmp, _ = robust_chi2(chi2t, act)
@@ -478,13 +531,17 @@ def pose_optimization(keys_xy, octave, u_right, point_index, points, inv_level_s
                     break
             trace["term_" + ended] += 1
             trace["ended"].append(ended)
+        else:
+            trace["skipped_rounds"].append(it)
         # ---- classification (:402-465): active edges from their last _error,
         # level-1 edges recomputed at the final estimate (:411-414)
         _, _, _, chi_last = ed.error(last_est)
         _, _, _, chi_fin = ed.error(est)
         with np.errstate(all="ignore"):
             chi = (chi_fin if classify_from_final else np.where(act, chi_last, chi_fin)).astype(f32)
-            new = chi > thr
+            new = (chi >= thr) if "classify_ge" in variants else (chi > thr)
+            if it == 0:
+                trace["chi2_first"] = chi.copy()
             if last_est is not est and act.any():
                 trace["stale_rounds"] += 1
                 trace["stale_chi_differs"] += int(
@@ -492,10 +549,11 @@ def pose_optimization(keys_xy, octave, u_right, point_index, points, inv_level_s
                 trace["stale_changed_flags"] += int(((chi_fin.astype(f32) > thr) != new)[act].sum())
         trace["outlier_to_inlier"] += int((flags & ~new).sum())
         flags = new
+        trace["round_outliers"].append(tuple(int(e) for e in np.nonzero(new)[0]))
         n_bad_edges = int(new.sum())
         if it == 2:
             robust = False  # :433-435
-        if E < 10:  # :467
+        if E < (11 if "ten_edges" in variants else 10):  # :467
             break
     out_flags[ei] = flags
     R, tc, o = pose_from_se3quat(est)

@@ -50,7 +50,7 @@ def _case(seed, n_kp, n_edges, kind, noise=1.0):
 def _one_frame(gpu, c):
     return gpu.ORBmatcher().PoseOptimization(
         c["keys"], c["u_right"], c["point_index"], c["points"], c.get("levels", pc.INV_LEVEL_SIGMA2),
-        pc.CAM, c["pose"], c["outlier"])
+        c.get("cam", pc.CAM), c["pose"], c["outlier"])
 
 
 # ------------------------------------------------------------------- one frame
@@ -91,10 +91,14 @@ def _batch_case(i):
     return _case(5000 + i, e + 5 + i % 7, e, ("mixed", "mono", "stereo")[i % 3], float(i % 2))
 
 
-def _pack_batch(gpu, torch, cases, kp_stride, layout, share=False):
+def _pack_batch(gpu, torch, cases, kp_stride, layout, share=False, levels=None, cam=None):
     """Packs the cases into one device batch; returns the call that runs it.  layout: "f3" packed
     float3 points, "mp" orb_map_point_t records.  share: one point array for
-    all problems (pt_stride 0), the indices offset into it."""
+    all problems (pt_stride 0), the indices offset into it.  levels, cam: the
+    level table and camera of the call when they are not pc.INV_LEVEL_SIGMA2
+    and pc.CAM."""
+    levels = pc.INV_LEVEL_SIGMA2 if levels is None else levels
+    cam = pc.CAM if cam is None else cam
     P = len(cases)
     keys = np.zeros((P, kp_stride), gpu.KEYPOINT_DTYPE)
     ur = np.full((P, kp_stride), 55.0, f32)
@@ -129,7 +133,7 @@ def _pack_batch(gpu, torch, cases, kp_stride, layout, share=False):
     def launch(m, stream=0):
         m.pose_optimization_batch(P, d_nk.data_ptr(), d_keys.data_ptr(), d_ur.data_ptr(),
                                   kp_stride, d_idx.data_ptr(), d_pts.data_ptr(), stride_bytes,
-                                  pt_stride, pc.INV_LEVEL_SIGMA2, pc.CAM, d_pin.data_ptr(),
+                                  pt_stride, levels, cam, d_pin.data_ptr(),
                                   d_pout.data_ptr(), d_outl.data_ptr(), d_info.data_ptr(),
                                   stream=stream)
         return d_pout, d_outl, d_info
