@@ -72,13 +72,44 @@ __global__ __launch_bounds__(256) void k_pyr_resize_generic(
     const uint32_t a = (uint32_t)alpha[dx], a0 = a & 0xFFFFu, a1 = a >> 16;
     const uint32_t h0 = a0 * buf_ld8(im.r, r0 + sx) + a1 * buf_ld8(im.r, r0 + sx1);
     const uint32_t h1 = a0 * buf_ld8(im.r, r1 + sx) + a1 * buf_ld8(im.r, r1 + sx1);
+    // the shift and the clamp as written: this kernel also takes the levels whose
+    // weight tables fail the bound pyr_vpack rests on (orb_resize_tables.h)
     int v = min((int)((__umul24(h0, b0) + __umul24(h1, b1) + (1u << 21)) >> 22), 255);
-    __asm__ volatile("" : "+v"(v));  // see k_pyr_resize
+    // opaque to instruction selection: ROCm 7.2 hipcc fuses shift+clamp+pack of
+    // byte pairs into v_ashr_pk_u8_i32 and then ORs the next bytes into its
+    // undefined upper half (observed miscompile on gfx950)
+    __asm__ volatile("" : "+v"(v));
     packed |= (uint32_t)v << (8 * j);
   }
   const __amdgpu_buffer_rsrc_t rd =
       make_rsrc(dst + (long long)blockIdx.z * dstImgPitch, (uint32_t)(dh * dstStride));
   buf_st32(rd, (uint32_t)(y * dstStride + xs), packed);
+}
+
+// Vertical stage of the tiled kernels: four pixels' (h0 b0 + h1 b1 + 2^21) >> 22
+// packed into one dword.  With every weight pair summing to <= 2049 (the planner
+// checks the tables, orb_resize_tables.h) that sum is below 2^30, so the result
+// is <= 255 without a clamp and is the top byte of four times the sum: b4 holds
+// the row's two weights times 4 (as beta packs them, shifted left by 2: at most
+// 8196 each, and h < 2^20, both 24-bit operands), the rounding term becomes
+// 2^23, and three byte permutes gather the four top bytes in place of four
+// shifts, four clamps and three shift-ors.
+__device__ __forceinline__ uint32_t pyr_vpack(const uint32_t* h0, const uint32_t* h1, uint32_t b4) {
+  const uint32_t b0 = b4 & 0xFFFFu, b1 = b4 >> 16;
+  uint32_t t[4];
+  // two v_mad_u32_u24 per pixel, written out: from __umul24(..) + __umul24(..) + c
+  // the compiler makes two multiplies and a v_add3, and masks to 24 bits every
+  // h0 that reaches it through k_pyr_resize's kept-or-fresh merge
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    uint32_t u;
+    __asm__("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(u) : "v"(h0[j]), "v"(b0), "s"(1u << 23));
+    __asm__("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(t[j]) : "v"(h1[j]), "v"(b1), "v"(u));
+  }
+  // v_perm selectors: 0-3 the second operand's bytes, 4-7 the first's, 0x0C zero
+  const uint32_t lo = __builtin_amdgcn_perm(t[1], t[0], 0x0C0C0703u);
+  const uint32_t hi = __builtin_amdgcn_perm(t[3], t[2], 0x0C0C0703u);
+  return __builtin_amdgcn_perm(hi, lo, 0x05040100u);
 }
 
 // Source-window staging in 16-byte groups: element i of a window of nR rows x
@@ -206,8 +237,28 @@ __global__ __launch_bounds__(256) void k_pyr_resize(
     sel[j] = bj | (0x0Cu << 8) | ((bj + 1) << 16) | (0x0Cu << 24);
     wts[j] = __builtin_bit_cast(u16x2, (uint32_t)al[j]);
   }
-  auto hrow = [&](int srow, uint32_t* h) {
-    const uint32_t* R = tile[srow] + k0;
+  // The thread's four output rows: both staged source rows of each as dword
+  // offsets into the window, and the row weights times 4 (pyr_vpack), the same
+  // for every image of the loop below.  Output row r + 1 mostly starts on the
+  // staged row that output row r ends on (four rows in five at 1.2): its first
+  // taps are then the previous row's second taps -- same staged row, same
+  // column selectors and weights -- and are kept instead of computed again.
+  // The rows are compared after the clamp and the - syA, so the image's top and
+  // bottom edges stay exact.  A wave holds two ty values: where only one of
+  // them starts on a fresh row, the extra hrow runs under a partial exec mask.
+  int ro0[PYR_TH / 8], ro1[PYR_TH / 8];
+  uint32_t be4[PYR_TH / 8];
+  bool fresh[PYR_TH / 8];
+#pragma unroll
+  for (int rr = 0; rr < PYR_TH / 8; ++rr) {
+    ro0[rr] = (min(max(yo[rr], 0), sh - 1) - syA) * SW + k0;
+    ro1[rr] = (min(max(yo[rr] + 1, 0), sh - 1) - syA) * SW + k0;
+    fresh[rr] = rr == 0 || ro0[rr] != ro1[rr - 1];
+    be4[rr] = (uint32_t)be[rr] << 2;
+  }
+  const int dstOff = (y0 + (PYR_TH / 8) * ty) * dstStride + xs;  // the first of the four rows
+  auto hrow = [&](int ro, uint32_t* h) {
+    const uint32_t* R = &tile[0][0] + ro;
     const uint32_t w0 = R[0], w1 = R[1], w2 = R[2];
     const uint32_t W0 = __builtin_amdgcn_alignbyte(w1, w0, sh0);
     const uint32_t W1 = __builtin_amdgcn_alignbyte(w2, w1, sh0);
@@ -221,26 +272,20 @@ __global__ __launch_bounds__(256) void k_pyr_resize(
     // whole dword store at xs < dw stays inside the row (padding bytes unused)
     const __amdgpu_buffer_rsrc_t rd =
         make_rsrc(dst + (long long)zc * dstImgPitch, (uint32_t)(dh * dstStride));
+    uint32_t h0[4], h1[4];
 #pragma unroll
     for (int rr = 0; rr < PYR_TH / 8; ++rr) {
       const int y = y0 + (PYR_TH / 8) * ty + rr;
       if (y >= dh) break;
-      const uint32_t b0 = (uint32_t)be[rr] & 0xFFFFu, b1 = (uint32_t)be[rr] >> 16;
-      uint32_t h0[4], h1[4];
-      hrow(min(max(yo[rr], 0), sh - 1) - syA, h0);
-      hrow(min(max(yo[rr] + 1, 0), sh - 1) - syA, h1);
-      uint32_t packed = 0;
+      if (fresh[rr]) {
+        hrow(ro0[rr], h0);
+      } else {
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        // h <= 255*2048 and b <= 2048: 24-bit multiplies, sum < 2^31
-        int v = min((int)((__umul24(h0[j], b0) + __umul24(h1[j], b1) + (1u << 21)) >> 22), 255);
-        // opaque to instruction selection: ROCm 7.2 hipcc fuses shift+clamp+pack of
-        // byte pairs into v_ashr_pk_u8_i32 and then ORs the next bytes into its
-        // undefined upper half (observed miscompile on gfx950)
-        __asm__ volatile("" : "+v"(v));
-        packed |= (uint32_t)v << (8 * j);
+        for (int j = 0; j < 4; ++j) h0[j] = h1[j];
       }
-      buf_st32(rd, (uint32_t)(y * dstStride + xs), packed);
+      hrow(ro1[rr], h1);
+      // one address register for the four rows: the row step is a scalar offset
+      __builtin_amdgcn_raw_buffer_store_b32(pyr_vpack(h0, h1, be4[rr]), rd, dstOff, rr * dstStride, 0);
     }
   };
   for (; z < nImg; z += gridDim.z) {
@@ -306,7 +351,7 @@ __global__ __launch_bounds__(256) void k_pyr_resize2(
   for (int rr = 0; rr < PYR_TH / 8; ++rr) {
     const int y = min(y0 + (PYR_TH / 8) * ty + rr, h2 - 1);
     yo[rr] = yo2[y];
-    be[rr] = be2[y];
+    be[rr] = be2[y] << 2;  // both weights times 4 (pyr_vpack)
   }
   // ---- R1: level-l columns [X0, X1e), rows [Y0, Y1e); owned [X0, ownX) x [Y0, ownY)
   const int xl = min(x0 + PYR_TW - 1, w2 - 1), yl = min(y0 + PYR_TH - 1, h2 - 1);
@@ -331,7 +376,7 @@ __global__ __launch_bounds__(256) void k_pyr_resize2(
   if (tid < nR1) {  // both source rows of level-l row Y0 + tid, relative to r0a
     const int yy = yo1[Y0 + tid];
     sYo[tid] = (min(max(yy, 0), h0 - 1) - r0a) | ((min(max(yy + 1, 0), h0 - 1) - r0a) << 16);
-    sBe[tid] = be1[Y0 + tid];
+    sBe[tid] = be1[Y0 + tid] << 2;  // both weights times 4 (pyr_vpack)
   }
   const int nStage = (nW0 + 3) >> 2;
   const uint32_t magic = div_magic(nStage);
@@ -361,17 +406,6 @@ __global__ __launch_bounds__(256) void k_pyr_resize2(
     for (int j = 0; j < 4; ++j)
       h[j] = __builtin_amdgcn_udot2(__builtin_bit_cast(u16x2, __builtin_amdgcn_perm(W1, W0, sel[j])),
                                     wts[j], 0u, false);
-  };
-  auto vsum = [](const uint32_t* ha, const uint32_t* hb, uint32_t b) {
-    const uint32_t b0 = b & 0xFFFFu, b1 = b >> 16;
-    uint32_t packed = 0;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      int v = min((int)((__umul24(ha[j], b0) + __umul24(hb[j], b1) + (1u << 21)) >> 22), 255);
-      __asm__ volatile("" : "+v"(v));  // see k_pyr_resize
-      packed |= (uint32_t)v << (8 * j);
-    }
-    return packed;
   };
   // level l+1 taps from R1 (relative to X0 / Y0)
   const int rel0 = xo[0] - X0;
@@ -413,7 +447,7 @@ __global__ __launch_bounds__(256) void k_pyr_resize2(
         uint32_t ha[4], hb[4];
         hsum(&s0[sy][rl >> 2], rl & 3, s1, w1v, ha);
         hsum(&s0[sy1][rl >> 2], rl & 3, s1, w1v, hb);
-        const uint32_t v = vsum(ha, hb, (uint32_t)sBe[r]);
+        const uint32_t v = pyr_vpack(ha, hb, (uint32_t)sBe[r]);
         r1[r][g] = v;
         if (Y0 + r < ownY && X0 + 4 * g < ownX)
           buf_st32(rm, (uint32_t)((Y0 + r) * midStride + X0 + 4 * g), v);
@@ -431,7 +465,7 @@ __global__ __launch_bounds__(256) void k_pyr_resize2(
         uint32_t ha[4], hb[4];
         hsum(&r1[min(max(yo[rr], 0), h1 - 1) - Y0][k0], sh0, sel, wts, ha);
         hsum(&r1[min(max(yo[rr] + 1, 0), h1 - 1) - Y0][k0], sh0, sel, wts, hb);
-        buf_st32(rd, (uint32_t)(y * dstStride + xs), vsum(ha, hb, (uint32_t)be[rr]));
+        buf_st32(rd, (uint32_t)(y * dstStride + xs), pyr_vpack(ha, hb, (uint32_t)be[rr]));
       }
     }
   }
@@ -2218,7 +2252,7 @@ __global__ __launch_bounds__(256) void k_blur_levels(
       }
       // the pinned kernel sums to 257 per axis: saturate (row sums <= 255*257 fit u16)
       int ve = min((int)((se + (1u << 15)) >> 16), 255), vo = min((int)((so + (1u << 15)) >> 16), 255);
-      __asm__ volatile("" : "+v"(ve), "+v"(vo));  // see k_pyr_resize: keep the byte pack opaque
+      __asm__ volatile("" : "+v"(ve), "+v"(vo));  // see k_pyr_resize_generic: keep the byte pack opaque
       packedE |= (uint32_t)ve << (8 * c);
       packedO |= (uint32_t)vo << (8 * c);
     }

@@ -188,34 +188,12 @@ static orb_status_t build_plan(orb_extractor* h, int W, int H) {
     // resize tables (level l from level l-1), SURVEY.md Appendix A.2
     if (l) {
       const int sw = P.lv[l - 1].w, sh = P.lv[l - 1].h;
-      const double scale_x = 1. / ((double)d.w / sw), scale_y = 1. / ((double)d.h / sh);
       d.rtabX = (int)rtab.size();
       rtab.resize(rtab.size() + 2 * (size_t)d.w);
-      int xmax = d.w;
-      for (int dx = 0; dx < d.w; ++dx) {
-        float fx = (float)((dx + 0.5) * scale_x - 0.5);
-        int sx = (int)floorf(fx);
-        fx -= sx;
-        if (sx < 0) { fx = 0; sx = 0; }
-        if (sx + 1 >= sw) {
-          xmax = std::min(xmax, dx);
-          if (sx >= sw - 1) { fx = 0; sx = sw - 1; }
-        }
-        const short a0 = satShort(cvRoundF((1.f - fx) * 2048)), a1 = satShort(cvRoundF(fx * 2048));
-        rtab[d.rtabX + dx] = sx;
-        rtab[d.rtabX + d.w + dx] = (int32_t)(((uint32_t)(uint16_t)a1 << 16) | (uint16_t)a0);
-      }
-      d.xmax = xmax;
+      d.xmax = orb_resize_table_x(d.w, sw, &rtab[d.rtabX], &rtab[d.rtabX + d.w]);
       d.rtabY = (int)rtab.size();
       rtab.resize(rtab.size() + 2 * (size_t)d.h);
-      for (int dy = 0; dy < d.h; ++dy) {
-        float fy = (float)((dy + 0.5) * scale_y - 0.5);
-        int sy = (int)floorf(fy);
-        fy -= sy;
-        const short b0 = satShort(cvRoundF((1.f - fy) * 2048)), b1 = satShort(cvRoundF(fy * 2048));
-        rtab[d.rtabY + dy] = sy;
-        rtab[d.rtabY + d.h + dy] = (int32_t)(((uint32_t)(uint16_t)b1 << 16) | (uint16_t)b0);
-      }
+      orb_resize_table_y(d.h, sh, &rtab[d.rtabY], &rtab[d.rtabY + d.h]);
       // k_pyr_resize stages each 128 x 32 output tile's source window in LDS
       // (narrow 44 x 44 dwords up to a 1.25 downscale, wide 64 x 64 beyond),
       // and each thread's 4 columns read 8 staged source bytes: the level takes
@@ -242,9 +220,15 @@ static orb_status_t build_plan(orb_extractor* h, int W, int H) {
         return true;
       };
       const bool narrowOk = (double)sw / d.w <= 1.25 && (double)sh / d.h <= 1.25;
-      d.resizeMode = narrowOk && tiles_fit(44, 44) ? ORB_RESIZE_NARROW
-                     : tiles_fit(64, 64)          ? ORB_RESIZE_WIDE
-                                                  : ORB_RESIZE_GENERIC;
+      // the tiled kernels take the result byte as the top byte of the scaled
+      // vertical sum, which needs every weight pair to sum to <= 2049: true of
+      // these tables by construction (orb_resize_tables.h), and checked here
+      const bool bounded = orb_resize_weights_bounded(&rtab[d.rtabX + d.w], d.w) &&
+                           orb_resize_weights_bounded(&rtab[d.rtabY + d.h], d.h);
+      d.resizeMode = !bounded                        ? ORB_RESIZE_GENERIC
+                     : narrowOk && tiles_fit(44, 44) ? ORB_RESIZE_NARROW
+                     : tiles_fit(64, 64)             ? ORB_RESIZE_WIDE
+                                                     : ORB_RESIZE_GENERIC;
     }
   }
   // Pairs of levels built by one launch (k_pyr_resize2: level l + 1 from a

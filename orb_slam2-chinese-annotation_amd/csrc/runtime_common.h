@@ -26,6 +26,7 @@
 
 #include "../../include/orb_abi.h"
 #include "orb_kernels.h"
+#include "orb_resize_tables.h"  // cvRoundF, satShort
 
 namespace {
 
@@ -39,9 +40,6 @@ namespace {
       return _e == hipErrorOutOfMemory ? ORB_ENOMEM : ORB_EDEVICE; \
     }                                                   \
   } while (0)
-
-static inline int cvRoundF(float v) { return (int)lrintf(v); }
-static inline short satShort(int v) { return (short)std::min(std::max(v, -32768), 32767); }
 
 static inline bool stream_capturing(hipStream_t s) {
   hipStreamCaptureStatus cst = hipStreamCaptureStatusNone;
