@@ -1679,9 +1679,16 @@ orb_status_t orb_vocabulary_score(orb_vocabulary_t* v, int n_pairs, const int32_
                                   const uint32_t* a_words, const double* a_values,
                                   const int32_t* b_offs, const uint32_t* b_words,
                                   const double* b_values, double* out);
-/* Device-pointer form (e.g. on orb_vocabulary_transform_batch outputs, whose
- * frame f occupies [f * stride, f * stride + d_n_words[f]): the caller builds
- * the offsets).  The vectors are not validated.  Asynchronous on `stream`. */
+/* Device-pointer form.  The vectors are not validated.  Asynchronous on
+ * `stream`.  An offsets array describes back-to-back vectors: pair p ends where
+ * pair p + 1 begins.  orb_vocabulary_transform_batch leaves frame f at
+ * [f * stride, f * stride + d_n_words[f]) with a gap behind it, so its outputs
+ * are scored in place one pair per call: the caller builds, on the device, the
+ * two offsets (f * stride, f * stride + d_n_words[f]) of every frame and passes
+ * n_pairs = 1 with d_a_offs / d_b_offs pointing at the two entries of the
+ * frames to compare (the words / values pointers stay the buffers' bases);
+ * or it compacts the frames first.  Spanning the gaps with pairs of their own
+ * would score uninitialised words. */
 orb_status_t orb_vocabulary_score_batch(orb_vocabulary_t* v, int n_pairs, const int32_t* d_a_offs,
                                         const uint32_t* d_a_words, const double* d_a_values,
                                         const int32_t* d_b_offs, const uint32_t* d_b_words,

@@ -703,3 +703,122 @@ def compute_image_bounds(cols, rows, K, dist):
     if fn(cols, rows, _p(K), _p(dist), len(dist), _p(b)) != 0:
         raise ValueError("unsupported distortion model")
     return b
+
+
+# ------------------------------------------------------- place recognition
+def _bow_arrays(bow):
+    w = np.ascontiguousarray(bow[0], np.uint32)
+    v = np.ascontiguousarray(bow[1], np.float64)
+    if len(w) != len(v):
+        raise ValueError("BowVector words and values differ in length")
+    return w, v
+
+
+def bow_score(a, b, scoring=0):
+    """TemplatedVocabulary::score(a, b) -> the ScoringObject.cpp:23-311 body of
+    `scoring` (BowVector.h:45-53 codes; KL is not restated) on std::maps built
+    from the (words, values) pairs."""
+    fn = lib().oracle_bow_score
+    vp, i32 = ctypes.c_void_p, ctypes.c_int
+    fn.argtypes = [i32, i32, vp, vp, i32, vp, vp, vp]
+    fn.restype = i32
+    aw, av = _bow_arrays(a)
+    bw, bv = _bow_arrays(b)
+    out = ctypes.c_double(0)
+    if fn(scoring, len(aw), _p(aw), _p(av), len(bw), _p(bw), _p(bv), ctypes.byref(out)) != 0:
+        raise ValueError("KL calls log(): not restated")
+    return out.value
+
+
+class KeyFrameDatabase:
+    """src/KeyFrameDatabase.cc:42-339 as placerec_oracle.cpp restates it, with
+    the interface of tests/placerec_ref.KeyFrameDatabase."""
+
+    def __init__(self, voc_size, scoring=0):
+        L = lib()
+        vp, i32, i64, u64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_uint64
+        for name, res, args in [
+                ("oracle_kfdb_create", vp, [i32, i32]),
+                ("oracle_kfdb_destroy", None, [vp]),
+                ("oracle_kfdb_size", i32, [vp]),
+                ("oracle_kfdb_add", i32, [vp, i64, i32, vp, vp]),
+                ("oracle_kfdb_erase", None, [vp, i64]),
+                ("oracle_kfdb_clear", None, [vp]),
+                ("oracle_kfdb_set_covisibility", i32, [vp, i64, i32, vp]),
+                ("oracle_kfdb_detect_loop", i32, [vp, u64, i32, vp, vp, i32, vp, ctypes.c_float,
+                                                  vp, i32]),
+                ("oracle_kfdb_detect_relocalization", i32, [vp, u64, i32, vp, vp, vp, i32]),
+                ("oracle_kfdb_last_query", i32, [vp, vp, vp, vp, i32]),
+                ("oracle_kfdb_last_min_common", i32, [vp]),
+                ("oracle_kfdb_last_elected", i32, [vp, vp, i32])]:
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = res, args
+        self._L = L
+        self._h = L.oracle_kfdb_create(int(voc_size), int(scoring))
+        if not self._h:
+            raise ValueError("KL calls log(): not restated")
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            self._L.oracle_kfdb_destroy(self._h)
+            self._h = None
+
+    def __len__(self):
+        return self._L.oracle_kfdb_size(self._h)
+
+    def add(self, kf_id, bow):
+        w, v = _bow_arrays(bow)
+        if self._L.oracle_kfdb_add(self._h, int(kf_id), len(w), _p(w), _p(v)) != 0:
+            raise ValueError("keyframe already present or malformed BowVector")
+
+    def erase(self, kf_id):
+        self._L.oracle_kfdb_erase(self._h, int(kf_id))
+
+    def clear(self):
+        self._L.oracle_kfdb_clear(self._h)
+
+    def set_covisibility(self, kf_id, neighbour_ids):
+        nb = np.ascontiguousarray([int(i) for i in neighbour_ids][:10], np.int64)
+        if self._L.oracle_kfdb_set_covisibility(self._h, int(kf_id), len(nb), _p(nb)) != 0:
+            raise ValueError("keyframe not in the database")
+
+    def _candidates(self, call):
+        cap = max(len(self), 1)
+        out = np.zeros(cap, np.int64)
+        n = call(_p(out), cap)
+        if n < 0:
+            raise ValueError("malformed BowVector")
+        return out[:n].tolist()
+
+    def DetectLoopCandidates(self, mnId, bow, connected_ids, minScore):
+        w, v = _bow_arrays(bow)
+        cn = np.ascontiguousarray([int(i) for i in connected_ids], np.int64)
+        return self._candidates(lambda o, c: self._L.oracle_kfdb_detect_loop(
+            self._h, int(mnId), len(w), _p(w), _p(v), len(cn), _p(cn), float(np.float32(minScore)),
+            o, c))
+
+    def DetectRelocalizationCandidates(self, mnId, bow):
+        w, v = _bow_arrays(bow)
+        return self._candidates(lambda o, c: self._L.oracle_kfdb_detect_relocalization(
+            self._h, int(mnId), len(w), _p(w), _p(v), o, c))
+
+    @property
+    def last_min_common(self):
+        return self._L.oracle_kfdb_last_min_common(self._h)
+
+    def last_query(self):
+        """(ids, word counts, scores, scored flags) of lKFsSharingWords."""
+        n = self._L.oracle_kfdb_last_query(self._h, None, None, None, 0)
+        ids = np.zeros(n, np.int64)
+        words = np.zeros(n, np.int32)
+        scores = np.zeros(n, np.float32)
+        self._L.oracle_kfdb_last_query(self._h, _p(ids), _p(words), _p(scores), n)
+        return ids, words, scores, (words > self.last_min_common).astype(np.uint8)
+
+    @property
+    def last_elected(self):
+        """pBestKF of every retained entry, before the duplicate filter."""
+        n = self._L.oracle_kfdb_last_elected(self._h, None, 0)
+        ids = np.zeros(n, np.int64)
+        self._L.oracle_kfdb_last_elected(self._h, _p(ids), n)
+        return ids.tolist()

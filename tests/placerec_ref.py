@@ -9,7 +9,12 @@ numpy.float32.  The inverted file is a real list per word, walked as the
 reference walks it: nothing here sorts keyframes.
 
 A BowVector is (words, values): ascending word ids and their values, the
-layout ORBVocabulary.transform / oracle.vocab_transform produce."""
+layout ORBVocabulary.transform / oracle.vocab_transform produce.
+
+`switch` (score, KeyFrameDatabase) names one rule to state wrongly, one of
+SWITCHES; tests/test_placerec_edge_cases.py uses it to show that each directed
+case of placerec_edge_cases.py would catch a kernel wrong in that way.  None,
+the default, is the reference."""
 import bisect
 import math
 
@@ -17,6 +22,58 @@ import numpy as np
 
 L1_NORM, L2_NORM, CHI_SQUARE, KL, BHATTACHARYYA, DOT_PRODUCT = range(6)  # BowVector.h:45-53
 f32 = np.float32
+NAN = float("nan")
+
+SWITCHES = (
+    "retain_ge",          # it->first >= minScoreToRetain            (DB:189, :324)
+    "minscore_gt",        # si > minScore                            (DB:140)
+    "best_ge",            # pKF2 score >= bestScore                  (DB:167, :301)
+    "neigh_minscore",     # loop neighbours also tested against minScore   (DB:164)
+    "connected_counted",  # connected keyframes marked and counted, only not listed   (DB:99-103)
+    "common_ge",          # loop neighbour gate mnLoopWords >= minCommonWords   (DB:164)
+    "best_from_zero",     # loop bestAccScore starts at 0            (DB:149)
+    "neigh_reverse",      # neighbours accumulated last to first     (DB:160, :292)
+    "pairwise",           # the score's terms added as a pairwise tree, not a chain
+    "no_chi_guard",       # chi-square without `vi + wi != 0.0`      (SO:148)
+    "no_l2_clamp",        # L2 without `score >= 1`                  (SO:114)
+    "order_by_slot",      # lKFsSharingWords in add order alone
+)
+
+
+def _sqrt(x):
+    """sqrt of <math.h>: NaN for a negative argument, where math.sqrt raises."""
+    return math.sqrt(x) if not x < 0 else NAN
+
+
+def _div(x, y):
+    """IEEE x / y, where Python raises on y == 0."""
+    if y != 0:
+        return x / y
+    if x != x or x == 0:
+        return NAN
+    return math.copysign(math.inf, x) * math.copysign(1.0, y)
+
+
+class _Sum:
+    """`score += term`: the reference's chain; or, switched, an adjacent-pair tree."""
+
+    def __init__(self, pairwise):
+        self.s = 0.0
+        self.terms = [] if pairwise else None
+
+    def add(self, t):
+        if self.terms is None:
+            self.s += t
+        else:
+            self.terms.append(t)
+
+    def value(self):
+        if self.terms is None:
+            return self.s
+        t = self.terms or [0.0]
+        while len(t) > 1:
+            t = [t[i] + t[i + 1] if i + 1 < len(t) else t[i] for i in range(0, len(t), 2)]
+        return t[0]
 
 
 def _common(v1, v2):
@@ -36,30 +93,33 @@ def _common(v1, v2):
             j = bisect.bisect_left(w2, w1[i])    # SO:56 v2.lower_bound
 
 
-def score(v1, v2, scoring=L1_NORM):
+def score(v1, v2, scoring=L1_NORM, switch=None):
     """TemplatedVocabulary::score -> m_scoring_object->score(v1, v2)."""
-    s = 0.0
+    acc = _Sum(switch == "pairwise")
     if scoring == L1_NORM:                       # SO:23-68
         for vi, wi in _common(v1, v2):
-            s += math.fabs(vi - wi) - math.fabs(vi) - math.fabs(wi)   # SO:41
-        return -s / 2.0                          # SO:65
+            acc.add(math.fabs(vi - wi) - math.fabs(vi) - math.fabs(wi))   # SO:41
+        return -acc.value() / 2.0                # SO:65
     if scoring == L2_NORM:                       # SO:73-120
         for vi, wi in _common(v1, v2):
-            s += vi * wi                         # SO:91
-        return 1.0 if s >= 1 else 1.0 - math.sqrt(1.0 - s)            # SO:114-117
+            acc.add(vi * wi)                     # SO:91
+        s = acc.value()
+        if s >= 1 and switch != "no_l2_clamp":   # SO:114-115
+            return 1.0
+        return 1.0 - _sqrt(1.0 - s)              # SO:117
     if scoring == CHI_SQUARE:                    # SO:125-170
         for vi, wi in _common(v1, v2):
-            if vi + wi != 0.0:                   # SO:148
-                s += vi * wi / (vi + wi)
-        return 2. * s                            # SO:167
+            if vi + wi != 0.0 or switch == "no_chi_guard":   # SO:148
+                acc.add(_div(vi * wi, vi + wi))
+        return 2. * acc.value()                  # SO:167
     if scoring == BHATTACHARYYA:                 # SO:226-266
         for vi, wi in _common(v1, v2):
-            s += math.sqrt(vi * wi)              # SO:245
-        return s
+            acc.add(_sqrt(vi * wi))              # SO:245
+        return acc.value()
     if scoring == DOT_PRODUCT:                   # SO:271-311
         for vi, wi in _common(v1, v2):
-            s += vi * wi                         # SO:290
-        return s
+            acc.add(vi * wi)                     # SO:290
+        return acc.value()
     raise ValueError("KL calls log(): not restated")
 
 
@@ -78,11 +138,16 @@ class KeyFrame:
         self.mnRelocWords = 0
         self.mRelocScore = f32(0)
         self.neighbours = []   # ids: snapshot of GetBestCovisibilityKeyFrames(10)
+        self.seq = 0           # add sequence number (read by the order_by_slot switch only)
 
 
 class KeyFrameDatabase:
-    def __init__(self, voc_size, scoring=L1_NORM):
+    def __init__(self, voc_size, scoring=L1_NORM, switch=None):
+        assert switch is None or switch in SWITCHES
         self.scoring = scoring
+        self.switch = switch
+        self.n_added = 0
+        self.last_entries = []   # (entry id, accScore, pBestKF id) of lAccScoreAndMatch
         self.voc_size = voc_size
         self.mvInvertedFile = [[] for _ in range(voc_size)]   # DB:38
         self.kfs = {}          # keyframes in the database, by id
@@ -95,6 +160,8 @@ class KeyFrameDatabase:
         assert kf_id not in self.kfs
         pKF = KeyFrame(kf_id, bow)               # a keyframe added again is a new one
         self.kfs[kf_id] = pKF
+        pKF.seq = self.n_added
+        self.n_added += 1
         for w in pKF.mBowVec[0]:
             self.mvInvertedFile[w].append(pKF)   # DB:48
 
@@ -121,7 +188,19 @@ class KeyFrameDatabase:
     def _neighbours(self, pKF):
         # an id that is not in the database is never reached by the walk, so its
         # mn*Query cannot equal the query's id: leaving it out changes nothing
-        return [self.kfs[i] for i in pKF.neighbours if i in self.kfs]
+        nb = [self.kfs[i] for i in pKF.neighbours if i in self.kfs]
+        return nb[::-1] if self.switch == "neigh_reverse" else nb
+
+    def _score(self, bow, pKFi):
+        return f32(score(bow, pKFi.mBowVec, self.scoring, self.switch))
+
+    def _listed(self, lKFsSharingWords):
+        if self.switch == "order_by_slot":
+            lKFsSharingWords.sort(key=lambda k: k.seq)
+        return lKFsSharingWords
+
+    def _better(self, s2, bestScore):            # DB:167, :301
+        return s2 >= bestScore if self.switch == "best_ge" else s2 > bestScore
 
     def last_query(self):
         """(ids, word counts, scores, scored flags) of lKFsSharingWords."""
@@ -135,6 +214,7 @@ class KeyFrameDatabase:
 
     def DetectLoopCandidates(self, mnId, bow, connected_ids, minScore):   # DB:79-202
         minScore = f32(minScore)
+        sw = self.switch
         spConnectedKeyFrames = {self.kfs[i] for i in connected_ids if i in self.kfs}   # DB:81
         lKFsSharingWords = []
         for w in [int(x) for x in bow[0]]:       # DB:89
@@ -144,8 +224,12 @@ class KeyFrameDatabase:
                     if pKFi not in spConnectedKeyFrames:   # DB:99
                         pKFi.mnLoopQuery = mnId
                         lKFsSharingWords.append(pKFi)
+                    elif sw == "connected_counted":
+                        pKFi.mnLoopQuery = mnId
                 pKFi.mnLoopWords += 1            # DB:106
+        lKFsSharingWords = self._listed(lKFsSharingWords)
         self.last, self.last_kind, self.last_min_common = lKFsSharingWords, "loop", 0
+        self.last_entries, self.last_elected = [], []
         if not lKFsSharingWords:                 # DB:111
             return []
         maxCommonWords = 0
@@ -157,25 +241,30 @@ class KeyFrameDatabase:
         lScoreAndMatch = []
         for pKFi in lKFsSharingWords:            # DB:129
             if pKFi.mnLoopWords > minCommonWords:              # DB:133
-                si = f32(score(bow, pKFi.mBowVec, self.scoring))   # DB:137
+                si = self._score(bow, pKFi)      # DB:137
                 pKFi.mLoopScore = si             # DB:139
-                if si >= minScore:               # DB:140
+                if si > minScore if sw == "minscore_gt" else si >= minScore:   # DB:140
                     lScoreAndMatch.append((si, pKFi))
         if not lScoreAndMatch:                   # DB:145
             return []
         lAccScoreAndMatch = []
-        bestAccScore = minScore                  # DB:149
+        bestAccScore = f32(0) if sw == "best_from_zero" else minScore   # DB:149
         for si, pKFi in lScoreAndMatch:          # DB:152
             bestScore = si                       # DB:157-159
             accScore = si
             pBestKF = pKFi
             for pKF2 in self._neighbours(pKFi):  # DB:160
-                if pKF2.mnLoopQuery == mnId and pKF2.mnLoopWords > minCommonWords:   # DB:164
+                enough = pKF2.mnLoopWords >= minCommonWords if sw == "common_ge" \
+                    else pKF2.mnLoopWords > minCommonWords
+                if sw == "neigh_minscore" and not pKF2.mLoopScore >= minScore:
+                    continue
+                if pKF2.mnLoopQuery == mnId and enough:          # DB:164
                     accScore = f32(accScore + pKF2.mLoopScore)   # DB:166
-                    if pKF2.mLoopScore > bestScore:              # DB:167
+                    if self._better(pKF2.mLoopScore, bestScore):   # DB:167
                         pBestKF = pKF2
                         bestScore = pKF2.mLoopScore
             lAccScoreAndMatch.append((accScore, pBestKF))        # DB:175
+            self.last_entries.append((pKFi.mnId, accScore, pBestKF.mnId))
             if accScore > bestAccScore:          # DB:176
                 bestAccScore = accScore
         return self._retain(lAccScoreAndMatch, bestAccScore)
@@ -189,7 +278,9 @@ class KeyFrameDatabase:
                     pKFi.mnRelocQuery = mnId
                     lKFsSharingWords.append(pKFi)
                 pKFi.mnRelocWords += 1           # DB:234
+        lKFsSharingWords = self._listed(lKFsSharingWords)
         self.last, self.last_kind, self.last_min_common = lKFsSharingWords, "reloc", 0
+        self.last_entries, self.last_elected = [], []
         if not lKFsSharingWords:                 # DB:238
             return []
         maxCommonWords = 0
@@ -201,7 +292,7 @@ class KeyFrameDatabase:
         lScoreAndMatch = []
         for pKFi in lKFsSharingWords:            # DB:258
             if pKFi.mnRelocWords > minCommonWords:             # DB:262
-                si = f32(score(bow, pKFi.mBowVec, self.scoring))   # DB:267
+                si = self._score(bow, pKFi)      # DB:267
                 pKFi.mRelocScore = si            # DB:268
                 lScoreAndMatch.append((si, pKFi))
         if not lScoreAndMatch:                   # DB:274
@@ -216,10 +307,11 @@ class KeyFrameDatabase:
                 if pKF2.mnRelocQuery != mnId:    # DB:296
                     continue
                 accScore = f32(accScore + pKF2.mRelocScore)    # DB:299
-                if pKF2.mRelocScore > bestScore:               # DB:301
+                if self._better(pKF2.mRelocScore, bestScore):    # DB:301
                     pBestKF = pKF2
                     bestScore = pKF2.mRelocScore
             lAccScoreAndMatch.append((accScore, pBestKF))      # DB:309
+            self.last_entries.append((pKFi.mnId, accScore, pBestKF.mnId))
             if accScore > bestAccScore:          # DB:310
                 bestAccScore = accScore
         return self._retain(lAccScoreAndMatch, bestAccScore)
@@ -230,7 +322,7 @@ class KeyFrameDatabase:
         out = []
         self.last_elected = []   # pBestKF of every retained entry, before the duplicate filter
         for acc, pKFi in lAccScoreAndMatch:
-            if acc > minScoreToRetain:
+            if acc >= minScoreToRetain if self.switch == "retain_ge" else acc > minScoreToRetain:
                 self.last_elected.append(pKFi.mnId)
                 if pKFi not in spAlreadyAddedKF:
                     out.append(pKFi.mnId)
