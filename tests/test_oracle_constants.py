@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 from conftest import PKG_DIR, REFERENCE, reference_present
+from orient_desc_ref import pattern_header as _pattern_header
 
 SRC = REFERENCE / "src" / "ORBextractor.cc"
 FACTS = json.loads((PKG_DIR.parent / "tests" / "golden" / "reference_facts.json").read_text())
@@ -42,12 +43,6 @@ def reference_constants():
             m = re.search(r"\b" + n + r"\s*=?\s*(\d+)\b", text)
             out[rel][n] = int(m.group(1)) if m else None
     return out
-
-
-def _pattern_header():
-    text = (PKG_DIR / "csrc" / "orb_pattern_data.h").read_text()
-    body = text.split("{", 1)[1].split("}", 1)[0]
-    return [int(v) for v in re.findall(r"-?\d+", body)]
 
 
 def test_pattern_table_is_the_reference_table():
