@@ -97,6 +97,10 @@
  *                                  (parallax test, linear triangulation, both reprojection
  *                                  checks, scale consistency) with the new point's
  *                                  MapPoint::UpdateNormalAndDepth src/MapPoint.cc:349-402
+ *   orb_search_for_triangulation_batch  device-batched SearchForTriangulation
+ *                                  src/ORBmatcher.cc:718-901 as the neighbour loop of
+ *                                  CreateNewMapPoints calls it src/LocalMapping.cc:313-318,
+ *                                  on the slot arrays of orb_create_new_map_points_batch
  *   orb_vocabulary_create / _load_text / _destroy
  *                                  DBoW2 TemplatedVocabulary ctor + loadFromTextFile
  *                                  Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:1362-1448
@@ -1476,11 +1480,18 @@ typedef struct orb_new_point_info {
  * above plus d_kf_keys (mvKeysUn), d_kf_u_right (mvuRight) and d_kf_depth
  * (mvDepth) at k * kp_stride (both NULL: monocular keyframes, every mvuRight
  * is -1).  d_match12 + p * kp_stride holds what orb_search_for_triangulation
- * writes: per keypoint of KF1 the index in KF2, or a negative value;
- * vMatchedIndices is its non-negative entries in ascending index, each index of
- * KF2 at most once (NOT checked).  ComputeF12 and the matcher are not part of
- * this call, and neither is ComputeDistinctiveDescriptors
- * (orb_distinctive_descriptors_batch).
+ * (or orb_search_for_triangulation_batch, on the device) writes: per keypoint
+ * of KF1 the index in KF2, or a negative value; vMatchedIndices is its
+ * non-negative entries in ascending index.  An index of KF2 may repeat: the
+ * matcher never sets vbMatched2 (src/ORBmatcher.cc:744-797), so several
+ * keypoints of KF1 can take one keypoint of KF2.  Every accepted match still
+ * creates its point and its pair, and KF2's d_kf_point_index entry ends as the
+ * id of the largest accepted i1 that names it, as the reference's sequential
+ * AddMapPoint calls leave it: ids ascend with i1 and the store is an atomic
+ * maximum, which is that id whenever the entry's previous value is below the
+ * cursor (always so for an entry the matcher can return: it is negative).
+ * ComputeF12 and the matcher are not part of this call, and neither is
+ * ComputeDistinctiveDescriptors (orb_distinctive_descriptors_batch).
  * Host values: cam1, cam2 (all six fields; invfx = 1.0f / fx on the host as
  * src/Frame.cc:115), scale_factors[n_levels] (mvScaleFactors; mfScaleFactor is
  * read as scale_factors[1], which is 1.0f * scaleFactor exactly, so 2 <=
@@ -1606,6 +1617,86 @@ orb_status_t orb_create_new_map_points(
     const float* level_sigma2, int n_levels, int monocular, orb_map_point_t* points,
     int point_capacity, int32_t* cursor, uint8_t* status, float* x3d, int32_t* new_pairs,
     orb_new_point_info_t* info);
+
+/* Device-batched SearchForTriangulation(pKF1, pKF2, F12, vMatchedPairs,
+ * bOnlyStereo) (src/ORBmatcher.cc:718-901) as the neighbour loop of
+ * LocalMapping::CreateNewMapPoints calls it (src/LocalMapping.cc:313-318):
+ * n_problems independent (KF1, KF2) problems in one launch, every array a
+ * device pointer, asynchronous on `stream`, no host synchronisation, upload or
+ * download.  The arrays are the keyframe slot arrays orb_match_bow_batch and
+ * orb_create_new_map_points_batch take, so the same allocations pass unchanged:
+ * slot k has d_kf_keys (mvKeysUn), d_kf_point_index, d_kf_fv_nodes and
+ * d_kf_fv_feats at k * kp_stride, d_kf_desc at 32 * k * kp_stride, d_kf_fv_offs
+ * at k * (kp_stride + 1), the counts d_kf_nkeys[k] and d_kf_n_fv_nodes[k],
+ * d_kf_u_right (mvuRight) at k * kp_stride (NULL: every keypoint is monocular)
+ * and the pose d_kf_pose[k].  Problem p matches slot d_kf1_slot[p]
+ * (mpCurrentKeyFrame) against slot d_kf2_slot[p] (pKF2); a slot may serve many
+ * problems on either side; the caller keeps the slot numbers inside the arrays
+ * (NOT checked).  d_f12 + 9 * p is ComputeF12(pKF1, pKF2), row-major.
+ * Host values: cam2 (fx, fy, cx, cy of pKF2 are read), scale_factors[n_levels]
+ * and level_sigma2[n_levels] of pKF2, only_stereo (bOnlyStereo),
+ * check_orientation (mbCheckOrientation).
+ * Derived on the device: GetMapPoint(i) != NULL is d_kf_point_index[i] >= 0 (a
+ * keypoint with a point is skipped on either side; isBad is not asked, :768,
+ * :792); stereo is mvuRight >= 0 (0.0 is stereo); the epipole of KF1 in KF2
+ * (:728-733) from d_kf_pose[kf1].ow and d_kf_pose[kf2].rcw / tcw with the
+ * arithmetic of orb_search_for_triangulation: C2 = ((r0 x + r1 y) + r2 z) + t
+ * row by row, invz = 1.0f / C2z, ex = (fx * C2x) * invz + cx, in float, left to
+ * right, no contraction.  An infinite or NaN epipole behaves as in the
+ * reference: the `<` of the epipole gate (:814-821) is false and nothing is
+ * skipped.
+ * Out: d_match12 + p * kp_stride, every entry below KF1's clamped count (the
+ * rest is not written): the KF2 index matched to the KF1 keypoint, or -1; this
+ * is the row orb_create_new_map_points_batch reads.  d_info[p] as below.  Per
+ * problem the row and n_matches are orb_search_for_triangulation's on the same
+ * inputs: the last passing candidate of minimum distance wins, dist <= 50, the
+ * epipole gate on mono-mono pairs only, den == 0 rejects, (double)dsqr < 3.84
+ * * (double)sigma2[octave of the KF2 keypoint], the rotation histogram with
+ * the strict three-maxima scan.  vbMatched2 is never set in the reference, so
+ * one KF2 index may be the match of several KF1 keypoints (n_shared2).
+ * Malformed slots are found on the device exactly as orb_match_bow_batch finds
+ * them: counts are clamped to [0, kp_stride] and n_fv_nodes to [0, count]; an
+ * offset that decreases (or a negative first one), an offset above the slot's
+ * count or a feature index >= the slot's count in either FeatureVector gives
+ * n_matches = -1, the other fields 0 and the row all -1 over KF1's clamped
+ * count, and nothing is indexed with the bad value.  A KF2 keypoint whose
+ * octave is outside [0, n_levels) is undefined in the reference (it reads past
+ * mvScaleFactors / mvLevelSigma2): a candidate that passes the point, stereo
+ * and distance tests and has such an octave is skipped without indexing and
+ * counted, once per (KF1 keypoint, candidate) pair, in n_undefined.  Ascending
+ * node ids and a feature listed in one node only are the caller's promise and
+ * are NOT checked (the node join is a binary search over the ids).
+ * Capacity: one workgroup per problem keeps 8 bytes per keypoint slot in LDS
+ * (the match word per KF1 keypoint; the partner node per KF1 node, later the
+ * match count per KF2 keypoint): 8 * ((kp_stride + 3) & ~3) + 1024 bytes must
+ * fit the 160 KiB of one CU; orb_search_for_triangulation_batch_max_stride()
+ * is the largest such kp_stride (a pure function, callable without a device;
+ * it is above orb_create_new_map_points_max_stride(), so the two calls chain at
+ * every stride the second accepts).  Above it: ORB_ECAPACITY before anything is
+ * launched, nothing is written.
+ * ORB_EINVAL: a null required pointer (all but d_kf_u_right), n_problems < 0,
+ * kp_stride <= 0, n_levels outside [1, 16], a scale factor or sigma2 that is
+ * not finite and positive.  n_problems == 0: ORB_OK, no launch.
+ * The call takes the handle's mutex; its kernel keeps all state in LDS and the
+ * caller's arrays and uses none of the handle's scratch, so it is ordered by
+ * `stream` alone. */
+typedef struct orb_tri_match_info {
+  int32_t n_matches;      /* the return value (after the rotation filter); -1: malformed slot */
+  int32_t n_accepted;     /* nmatches before the filter (src/ORBmatcher.cc:835) */
+  int32_t n_common_nodes; /* node ids present in both FeatureVectors */
+  int32_t n_tried;        /* KF1 keypoints of common nodes that pass the point and stereo tests */
+  int32_t n_shared2;      /* final matches whose KF2 index another final match names too */
+  int32_t n_undefined;    /* candidates skipped for an octave outside [0, n_levels) */
+} orb_tri_match_info_t;   /* 24 bytes */
+orb_status_t orb_search_for_triangulation_batch(
+    orb_matcher_t* m, int n_problems, const int32_t* d_kf1_slot, const int32_t* d_kf2_slot,
+    const orb_keypoint_t* d_kf_keys, const uint8_t* d_kf_desc, const int32_t* d_kf_nkeys,
+    const int32_t* d_kf_point_index, const uint32_t* d_kf_fv_nodes, const int32_t* d_kf_fv_offs,
+    const uint32_t* d_kf_fv_feats, const int32_t* d_kf_n_fv_nodes, const float* d_kf_u_right,
+    const orb_pose_t* d_kf_pose, int kp_stride, const float* d_f12, const orb_camera_t* cam2,
+    const float* scale_factors, const float* level_sigma2, int n_levels, int only_stereo,
+    int check_orientation, int32_t* d_match12, orb_tri_match_info_t* d_info, void* stream);
+int orb_search_for_triangulation_batch_max_stride(void);
 
 /* ------------------------------------------------------ DBoW2 vocabulary */
 

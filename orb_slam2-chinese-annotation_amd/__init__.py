@@ -77,6 +77,10 @@ assert SIM3_RESULT_DTYPE.itemsize == 132
 NEW_POINT_INFO_DTYPE = np.dtype([("gated", "<i4"), ("overflow", "<i4"), ("n_new", "<i4"),
                                  ("first_point", "<i4"), ("counts", "<i4", (12,))])
 assert NEW_POINT_INFO_DTYPE.itemsize == 64
+TRI_MATCH_INFO_DTYPE = np.dtype([("n_matches", "<i4"), ("n_accepted", "<i4"),
+                                 ("n_common_nodes", "<i4"), ("n_tried", "<i4"),
+                                 ("n_shared2", "<i4"), ("n_undefined", "<i4")])
+assert TRI_MATCH_INFO_DTYPE.itemsize == 24
 # orb_new_point_info_t.counts / the status bytes (ORB_NP_*)
 (NP_NOT_TRIED, NP_NO_MATCH, NP_ACCEPTED, NP_LOW_PARALLAX, NP_W_ZERO, NP_Z1, NP_Z2, NP_REPROJ1,
  NP_REPROJ2, NP_ZERO_DIST, NP_SCALE_RATIO, NP_UNDEFINED) = range(12)
@@ -274,6 +278,10 @@ def lib() -> ctypes.CDLL:
         "orb_create_new_map_points": (i32, [vp, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp,
                                             vp, f32, vp, vp, vp, vp, i32, i32, vp, i32, vp, vp,
                                             vp, vp, vp]),
+        "orb_search_for_triangulation_batch": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                                     vp, vp, vp, i32, vp, vp, vp, vp, i32, i32,
+                                                     i32, vp, vp, vp]),
+        "orb_search_for_triangulation_batch_max_stride": (i32, []),
         "orb_synth_image": (None, [ctypes.c_uint64, i32, i32, i32, i32, vp, sz]),
         "orb_synth_local_map": (None, [ctypes.c_uint64, vp, vp, i32, i32, i32, i32, vp, vp, vp]),
     }
@@ -288,7 +296,8 @@ def lib() -> ctypes.CDLL:
              "orb_sim3_solver_iterate_batch", "orb_scene_median_depth_batch",
              "orb_scene_median_depth_max_stride", "orb_scene_median_depth",
              "orb_create_new_map_points_batch", "orb_create_new_map_points_max_stride",
-             "orb_create_new_map_points")
+             "orb_create_new_map_points", "orb_search_for_triangulation_batch",
+             "orb_search_for_triangulation_batch_max_stride")
     for name, (res, args) in sig.items():
         if name in newer and "ORB_AMD_LIB" in os.environ and not hasattr(L, name):
             continue
@@ -327,6 +336,12 @@ def match_bow_batch_max_stride() -> int:
     """orb_match_bow_batch_max_stride(): a pure function of k_bow_batch's LDS
     layout, callable without a device."""
     return lib().orb_match_bow_batch_max_stride()
+
+
+def search_for_triangulation_batch_max_stride() -> int:
+    """orb_search_for_triangulation_batch_max_stride(): a pure function of
+    k_tri_batch's LDS layout, callable without a device."""
+    return lib().orb_search_for_triangulation_batch_max_stride()
 
 
 def update_local_map_max_keyframes() -> int:
@@ -1503,6 +1518,42 @@ class ORBmatcher:
             int(bool(monocular)), d_points or None, int(point_capacity), d_point_cursor or None,
             d_cursor_index or None, d_status or None, d_x3d or None, d_new_pairs or None,
             d_info or None, stream or None), "create_new_map_points_batch")
+
+    def search_for_triangulation_batch(self, n_problems, d_kf1_slot, d_kf2_slot, d_kf_keys,
+                                       d_kf_desc, d_kf_nkeys, d_kf_point_index, d_kf_fv_nodes,
+                                       d_kf_fv_offs, d_kf_fv_feats, d_kf_n_fv_nodes, d_kf_u_right,
+                                       d_kf_pose, kp_stride, d_f12, cam2, scale_factors,
+                                       level_sigma2, only_stereo, d_match12, d_info,
+                                       stream: int = 0):
+        """Device-batched SearchForTriangulation for n_problems (KF1, KF2) pairs
+        (orb_search_for_triangulation_batch) with this matcher's
+        mbCheckOrientation.  d_* are device addresses (a torch tensor's
+        data_ptr()) in the keyframe slot layout of search_by_bow_batch and
+        create_new_map_points_batch; d_kf_u_right 0: every keypoint is
+        monocular; d_f12: nine floats per problem (ComputeF12, row-major).
+        cam2: (fx, fy, cx, cy[, bf, mb]) of pKF2; scale_factors and
+        level_sigma2 are pKF2's.  d_match12: n_problems x kp_stride int32, the
+        row create_new_map_points_batch reads; d_info: TRI_MATCH_INFO_DTYPE
+        records.  Asynchronous on `stream`."""
+        sf = np.ascontiguousarray(scale_factors, np.float32).reshape(-1)
+        ls = np.ascontiguousarray(level_sigma2, np.float32).reshape(-1)
+        if len(sf) != len(ls):
+            raise OrbError(ORB_EINVAL, "scale_factors and level_sigma2 differ in length")
+        c2 = self._camera4(cam2)
+        _check(lib().orb_search_for_triangulation_batch(
+            self._h, n_problems, d_kf1_slot or None, d_kf2_slot or None, d_kf_keys or None,
+            d_kf_desc or None, d_kf_nkeys or None, d_kf_point_index or None,
+            d_kf_fv_nodes or None, d_kf_fv_offs or None, d_kf_fv_feats or None,
+            d_kf_n_fv_nodes or None, d_kf_u_right or None, d_kf_pose or None, kp_stride,
+            d_f12 or None, ctypes.byref(c2), _ptr(sf) if len(sf) else None,
+            _ptr(ls) if len(ls) else None, len(sf), int(bool(only_stereo)),
+            int(self.mbCheckOrientation), d_match12 or None, d_info or None, stream or None),
+            "search_for_triangulation_batch")
+
+    @staticmethod
+    def search_for_triangulation_batch_max_stride() -> int:
+        """Largest kp_stride search_for_triangulation_batch accepts."""
+        return lib().orb_search_for_triangulation_batch_max_stride()
 
     @staticmethod
     def create_new_map_points_max_stride() -> int:

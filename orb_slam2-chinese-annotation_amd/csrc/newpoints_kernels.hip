@@ -499,7 +499,10 @@ __global__ __launch_bounds__(NP_T) void k_new_points(const NewPointsParams P) {
     pair[0] = i;
     pair[1] = idx2;
     P.pointIndex[(size_t)s1 * P.stride + i] = id;
-    P.pointIndex[(size_t)s2 * P.stride + idx2] = id;  // idx2 < n2 <= stride: pass 1
+    // idx2 < n2 <= stride: pass 1.  Several accepted i1 may name one idx2 (the
+    // matcher never sets vbMatched2): the reference's last AddMapPoint is the
+    // largest i1, ids ascend with i1, and the entry was below the cursor
+    atomicMax(&P.pointIndex[(size_t)s2 * P.stride + idx2], id);
   }
   if (tid == 0) {
     orb_new_point_info_t info;

@@ -235,6 +235,22 @@ struct BowBatchParams {
   int checkOri, minMatches;
 };
 
+// SearchForTriangulation over nProblems (KF1, KF2) pairs of keyframe slots (by
+// value): one set of slot arrays serves both sides
+struct TriBatchParams {
+  int nProblems, stride;
+  const int32_t* kf1Slot;
+  const int32_t* kf2Slot;
+  BowSlots kf;
+  const int32_t* pointIndex;   // mvpMapPoints per keypoint (>= 0: the keypoint is skipped)
+  const float* uRight;         // null: every keypoint is monocular
+  const orb_pose_t* pose;
+  const float* f12;            // ComputeF12, nine floats per problem, row-major
+  float fx, fy, cx, cy;        // pKF2
+  int nLevels, onlyStereo, checkOri;
+  float scale[ORB_MAX_LEVELS], sigma2[ORB_MAX_LEVELS];  // pKF2
+};
+
 // ----------------------------------------------------- localmap_kernels.hip
 // Tracking::UpdateLocalMap over nProblems frames against one map view (by
 // value): the view's device pointers, the per-problem arrays and strides

@@ -230,6 +230,10 @@ hipError_t orb_k_track_discard(int nProblems, int stride, long long mpStride, in
 int orb_k_bow_batch_max_stride(void);
 hipError_t orb_k_bow_batch(const BowBatchParams* params, int32_t* kpMatch,
                            orb_bow_match_info_t* info, hipStream_t s);
+// SearchForTriangulation over keyframe slot pairs; largest kp_stride as above
+int orb_k_tri_batch_max_stride(void);
+hipError_t orb_k_tri_batch(const TriBatchParams* params, int32_t* match12,
+                           orb_tri_match_info_t* info, hipStream_t s);
 hipError_t orb_k_track_local_merge(int nProblems, int stride, int mpStride, const int32_t* nkeys,
                                    const int32_t* kmLocal, const int32_t* localIndex,
                                    int32_t* kpMatch, hipStream_t s);

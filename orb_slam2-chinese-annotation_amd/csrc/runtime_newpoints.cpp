@@ -114,6 +114,56 @@ orb_status_t orb_create_new_map_points_batch(
   return ORB_OK;
 }
 
+// SearchForTriangulation for the same pairs on the same slot arrays
+// (src/ORBmatcher.cc:718-901; k_tri_batch in track_kernels.hip): its d_match12
+// row is what orb_create_new_map_points_batch reads.
+int orb_search_for_triangulation_batch_max_stride(void) { return orb_k_tri_batch_max_stride(); }
+
+orb_status_t orb_search_for_triangulation_batch(
+    orb_matcher_t* m, int n_problems, const int32_t* d_kf1_slot, const int32_t* d_kf2_slot,
+    const orb_keypoint_t* d_kf_keys, const uint8_t* d_kf_desc, const int32_t* d_kf_nkeys,
+    const int32_t* d_kf_point_index, const uint32_t* d_kf_fv_nodes, const int32_t* d_kf_fv_offs,
+    const uint32_t* d_kf_fv_feats, const int32_t* d_kf_n_fv_nodes, const float* d_kf_u_right,
+    const orb_pose_t* d_kf_pose, int kp_stride, const float* d_f12, const orb_camera_t* cam2,
+    const float* scale_factors, const float* level_sigma2, int n_levels, int only_stereo,
+    int check_orientation, int32_t* d_match12, orb_tri_match_info_t* d_info, void* stream) {
+  if (!m || n_problems < 0 || kp_stride <= 0 || !cam2 || !scale_factors || !level_sigma2 ||
+      n_levels < 1 || n_levels > ORB_MAX_LEVELS)
+    return ORB_EINVAL;
+  for (int l = 0; l < n_levels; ++l)
+    if (!(scale_factors[l] > 0.f && scale_factors[l] <= 1e15f) ||
+        !(level_sigma2[l] > 0.f && level_sigma2[l] <= 1e15f))
+      return ORB_EINVAL;
+  if (kp_stride > orb_k_tri_batch_max_stride()) return ORB_ECAPACITY;  // nothing is launched
+  if (n_problems == 0) return ORB_OK;
+  if (!d_kf1_slot || !d_kf2_slot || !d_kf_keys || !d_kf_desc || !d_kf_nkeys ||
+      !d_kf_point_index || !d_kf_fv_nodes || !d_kf_fv_offs || !d_kf_fv_feats ||
+      !d_kf_n_fv_nodes || !d_kf_pose || !d_f12 || !d_match12 || !d_info)
+    return ORB_EINVAL;
+  std::lock_guard<std::mutex> g(m->mu);
+  hipSetDevice(m->device);
+  hipStream_t s = stream ? (hipStream_t)stream : m->stream;
+  TriBatchParams P;
+  memset(&P, 0, sizeof(P));
+  P.nProblems = n_problems;
+  P.stride = kp_stride;
+  P.kf1Slot = d_kf1_slot;
+  P.kf2Slot = d_kf2_slot;
+  P.kf = BowSlots{d_kf_keys, d_kf_desc, d_kf_nkeys, d_kf_fv_nodes, d_kf_fv_offs, d_kf_fv_feats,
+                  d_kf_n_fv_nodes};
+  P.pointIndex = d_kf_point_index;
+  P.uRight = d_kf_u_right;
+  P.pose = d_kf_pose;
+  P.f12 = d_f12;
+  P.fx = cam2->fx, P.fy = cam2->fy, P.cx = cam2->cx, P.cy = cam2->cy;
+  P.nLevels = n_levels;
+  P.onlyStereo = only_stereo ? 1 : 0;
+  P.checkOri = check_orientation ? 1 : 0;
+  for (int l = 0; l < n_levels; ++l) P.scale[l] = scale_factors[l], P.sigma2[l] = level_sigma2[l];
+  HIP_TRY(orb_k_tri_batch(&P, d_match12, d_info, s));
+  return ORB_OK;
+}
+
 orb_status_t orb_scene_median_depth(orb_matcher_t* m, int n, const int32_t* point_index,
                                     const orb_pose_t* pose, const orb_map_point_t* points,
                                     int n_points, int q, float* median, int32_t* count) {

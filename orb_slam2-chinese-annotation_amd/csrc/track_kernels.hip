@@ -5,7 +5,9 @@
 // with SearchLocalPoints' already-matched marking (:1333-1354); and of
 // TrackReferenceKeyFrame's and Relocalization's matcher stage, SearchByBoW(pKF,
 // F, vpMapPointMatches) (src/ORBmatcher.cc:164-306), as the same kind of batch
-// (k_bow_batch, at the end of the file).
+// (k_bow_batch, at the end of the file); and, after it, of the neighbour loop
+// of LocalMapping::CreateNewMapPoints, SearchForTriangulation
+// (src/ORBmatcher.cc:718-901), on the same keyframe slots (k_tri_batch).
 //
 // k_frame_batch: one workgroup of four waves per problem, the problem's grid
 // built before it by k_grid_build.  Per pass: every wave projects last-frame
@@ -500,6 +502,25 @@ __device__ __forceinline__ int bb_bad_feats(const int32_t* offs, const uint32_t*
     for (int q = offs[0] + tid; q < offs[nNodes]; q += BB_T) bad |= (feats[q] >= (uint32_t)count);
   return bad;
 }
+// The merge-join on node id, a node of the first FeatureVector per thread:
+// partner[a] = the position in bNodes of the node with aNodes[a]'s id, -1 none.
+// Returns this thread's count of common nodes.
+__device__ __forceinline__ int bb_join_nodes(const uint32_t* aNodes, int na, const uint32_t* bNodes,
+                                             int nb, int* partner, int tid) {
+  int common = 0;
+  for (int a = tid; a < na; a += BB_T) {
+    const uint32_t id = aNodes[a];
+    int lo = 0, hi = nb;
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (bNodes[mid] < id) lo = mid + 1; else hi = mid;
+    }
+    const bool found = lo < nb && bNodes[lo] == id;
+    partner[a] = found ? lo : -1;
+    common += found;
+  }
+  return common;
+}
 
 __global__ __launch_bounds__(BB_T) void k_bow_batch(BowBatchParams P, int32_t* __restrict__ kpMatch,
                                                     orb_bow_match_info_t* __restrict__ info) {
@@ -559,19 +580,7 @@ __global__ __launch_bounds__(BB_T) void k_bow_batch(BowBatchParams P, int32_t* _
   if (tid < 8) ctl[tid] = 0;
   __syncthreads();
   {
-    int common = 0;
-    for (int a = tid; a < nnK; a += BB_T) {
-      const uint32_t id = kNodes[a];
-      int lo = 0, hi = nnF;
-      while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (fNodes[mid] < id) lo = mid + 1; else hi = mid;
-      }
-      const bool found = lo < nnF && fNodes[lo] == id;
-      partner[a] = found ? lo : -1;
-      common += found;
-    }
-    common = wave_sum(common);
+    const int common = wave_sum(bb_join_nodes(kNodes, nnK, fNodes, nnF, partner, tid));
     if (lane == 0 && common) atomicAdd(&ctl[2], common);
   }
   __syncthreads();
@@ -738,6 +747,281 @@ extern "C" hipError_t orb_k_bow_batch(const BowBatchParams* params, int32_t* kpM
     if (e != hipSuccess) return e;
   }
   hipLaunchKernelGGL(k_bow_batch, dim3(P.nProblems), dim3(BB_T), lds, s, P, kpMatch, info);
+  return hipGetLastError();
+}
+
+// ================================== SearchForTriangulation as a device batch
+// src/ORBmatcher.cc:718-901 for the neighbour loop of
+// LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:313-318): one
+// workgroup of eight waves per (KF1, KF2) problem, one launch for validation,
+// the epipole, matching, the rotation filter and the outputs.  vbMatched2 is
+// never set, so every KF1 keypoint is independent and so is every (KF1
+// keypoint, KF2 candidate) pair: the waves draw KF1 nodes from an LDS counter
+// and spread the node's c1 x c2 pairs over their lanes, so that a node of
+// eight features on either side is one trip of 64 lanes, not eight trips of
+// eight.  A passing pair leaves (dist << 20) | (0xFFFFF - position in KF2's
+// feature list) in the KF1 keypoint's LDS word by atomicMin: the minimum is
+// the last passing candidate of minimum distance (k_tri_match's key).  The
+// words become KF2 index | rotation bin << 24 once the matching is over; the
+// partner table of the node join is dead by then and counts the matches per
+// KF2 keypoint (n_shared2).
+#define TB_T BB_T  // the FeatureVector checks above stride by BB_T
+#define TB_STATIC_LDS ((size_t)1024)  // hist[32], ctl[8], two level tables and the block vote
+#define TB_NONE 0xFFFFFFFFu
+
+// ComputeThreeMaxima (src/ORBmatcher.cc:1765-1809) as three_maxima states it,
+// with the if / else-if chain written as selects (max1 >= max2 >= max3, so
+// s > max1 implies s > max2 implies s > max3): the chain's index shuffle ends
+// up in scratch memory, this form stays in registers.
+__device__ __forceinline__ void tb_three_maxima(const int* h, int& ind1, int& ind2, int& ind3) {
+  int max1 = 0, max2 = 0, max3 = 0;
+  ind1 = ind2 = ind3 = -1;
+#pragma unroll 1
+  for (int i = 0; i < 30; ++i) {
+    const int s = h[i];
+    const bool g1 = s > max1, g2 = s > max2, g3 = s > max3;
+    max3 = g2 ? max2 : (g3 ? s : max3);
+    ind3 = g2 ? ind2 : (g3 ? i : ind3);
+    max2 = g1 ? max1 : (g2 ? s : max2);
+    ind2 = g1 ? ind1 : (g2 ? i : ind2);
+    max1 = g1 ? s : max1;
+    ind1 = g1 ? i : ind1;
+  }
+  if (max2 < 0.1f * (float)max1) { ind2 = -1; ind3 = -1; }
+  else if (max3 < 0.1f * (float)max1) { ind3 = -1; }
+}
+
+__global__ __launch_bounds__(TB_T) void k_tri_batch(TriBatchParams P, int32_t* __restrict__ match12,
+                                                    orb_tri_match_info_t* __restrict__ info) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t dyn[];
+  __shared__ int hist[32];
+  __shared__ int ctl[8];  // next node, tried, common nodes, accepted, removed, shared, undefined
+  __shared__ float lvScale[ORB_MAX_LEVELS], lvSigma2[ORB_MAX_LEVELS];
+  static_assert(sizeof(hist) + sizeof(ctl) + sizeof(lvScale) + sizeof(lvSigma2) + 256 <=
+                    TB_STATIC_LDS, "capacity rule counts these");
+  const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+  const int S = (P.stride + 3) & ~3;
+  uint32_t* mword = dyn;            // per KF1 keypoint: the match key, then KF2 index | bin << 24
+  int* partner = (int*)(dyn + S);   // per KF1 node: position of KF2's node, -1 none; then
+  int* cnt2 = partner;              // per KF2 keypoint: final matches that name it
+
+  const int s1 = P.kf1Slot[p], s2 = P.kf2Slot[p];
+  const size_t b1 = (size_t)s1 * P.stride, b2 = (size_t)s2 * P.stride;
+  const int n1 = min(max(P.kf.nkeys[s1], 0), P.stride);
+  const int n2 = min(max(P.kf.nkeys[s2], 0), P.stride);
+  const int nn1 = min(max(P.kf.nFvNodes[s1], 0), n1);
+  const int nn2 = min(max(P.kf.nFvNodes[s2], 0), n2);
+  const orb_keypoint_t* K1 = P.kf.keys + b1;
+  const uint8_t* D1 = P.kf.desc + b1 * 32;
+  const uint32_t* N1 = P.kf.fvNodes + b1;
+  const int32_t* O1 = P.kf.fvOffs + (size_t)s1 * ((size_t)P.stride + 1);
+  const uint32_t* F1 = P.kf.fvFeats + b1;
+  const int32_t* PI1 = P.pointIndex + b1;
+  const float* UR1 = P.uRight ? P.uRight + b1 : nullptr;
+  const orb_keypoint_t* K2 = P.kf.keys + b2;
+  const uint8_t* D2 = P.kf.desc + b2 * 32;
+  const uint32_t* N2 = P.kf.fvNodes + b2;
+  const int32_t* O2 = P.kf.fvOffs + (size_t)s2 * ((size_t)P.stride + 1);
+  const uint32_t* F2 = P.kf.fvFeats + b2;
+  const int32_t* PI2 = P.pointIndex + b2;
+  const float* UR2 = P.uRight ? P.uRight + b2 : nullptr;
+  int32_t* M12 = match12 + (size_t)p * P.stride;
+
+  // ---- malformed slots, as k_bow_batch finds them
+  int bad = bb_bad_offsets(O1, nn1, n1, tid) | bb_bad_offsets(O2, nn2, n2, tid);
+  bad = __syncthreads_or(bad);
+  if (!bad) {
+    bad = bb_bad_feats(O1, F1, nn1, n1, tid) | bb_bad_feats(O2, F2, nn2, n2, tid);
+    bad = __syncthreads_or(bad);
+  }
+  if (bad) {
+    for (int i = tid; i < n1; i += TB_T) M12[i] = -1;
+    if (tid == 0) {
+      info[p].n_matches = -1;
+      info[p].n_accepted = 0;
+      info[p].n_common_nodes = 0;
+      info[p].n_tried = 0;
+      info[p].n_shared2 = 0;
+      info[p].n_undefined = 0;
+    }
+    return;
+  }
+
+  // ---- the epipole of KF1 in KF2 (:728-733), the arithmetic of the one-problem
+  // entry: C2 = R2w * Cw + t2w row by row, invz = 1.0f / C2z
+  float ex, ey, F[9];
+  {
+    const orb_pose_t* p1 = P.pose + s1;
+    const orb_pose_t* p2 = P.pose + s2;
+    const float cwx = p1->ow[0], cwy = p1->ow[1], cwz = p1->ow[2];
+    const float c2x = fb_row(p2->rcw, 0, cwx, cwy, cwz, p2->tcw[0]);
+    const float c2y = fb_row(p2->rcw, 1, cwx, cwy, cwz, p2->tcw[1]);
+    const float c2z = fb_row(p2->rcw, 2, cwx, cwy, cwz, p2->tcw[2]);
+    const float invz = __fdiv_rn(1.0f, c2z);
+    ex = P.fx * c2x * invz + P.cx;
+    ey = P.fy * c2y * invz + P.cy;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) F[i] = P.f12[(size_t)p * 9 + i];
+  }
+
+  for (int i = tid; i < n1; i += TB_T) mword[i] = TB_NONE;
+  if (tid < 32) hist[tid] = 0;
+  if (tid < 8) ctl[tid] = 0;
+  if (tid < ORB_MAX_LEVELS) {
+    lvScale[tid] = P.scale[tid];
+    lvSigma2[tid] = P.sigma2[tid];
+  }
+  __syncthreads();
+  {
+    const int common = wave_sum(bb_join_nodes(N1, nn1, N2, nn2, partner, tid));
+    if (lane == 0 && common) atomicAdd(&ctl[2], common);
+  }
+  __syncthreads();
+
+  // ---- matching: a wave per KF1 node, lanes over its (KF1, KF2) feature pairs
+  int tried = 0, undefined = 0;
+  for (;;) {
+    int a = 0;
+    if (lane == 0) a = atomicAdd(&ctl[0], 1);
+    a = __builtin_amdgcn_readfirstlane(a);
+    if (a >= nn1) break;
+    const int fp = __builtin_amdgcn_readfirstlane(partner[a]);
+    if (fp < 0) continue;
+    const int k0 = __builtin_amdgcn_readfirstlane(O1[a]);
+    const int c1 = __builtin_amdgcn_readfirstlane(O1[a + 1]) - k0;
+    const int f0 = __builtin_amdgcn_readfirstlane(O2[fp]);
+    const int c2 = __builtin_amdgcn_readfirstlane(O2[fp + 1]) - f0;
+    for (int t = lane; t < c1; t += 64) {  // the outer loop's tests alone (:768-778)
+      const int idx1 = (int)F1[k0 + t];
+      const bool st1 = UR1 && UR1[idx1] >= 0;
+      tried += PI1[idx1] < 0 && (st1 || !P.onlyStereo);
+    }
+    if (c1 <= 0 || c2 <= 0) continue;
+    const int total = c1 * c2;  // <= stride^2 < 2^31 (orb_k_tri_batch_max_stride)
+    for (int t = lane; t < total; t += 64) {
+      const int i = (int)((unsigned)t / (unsigned)c2), j = t - i * c2;
+      const int idx1 = (int)F1[k0 + i];
+      if (PI1[idx1] >= 0) continue;  // :768-772
+      const bool st1 = UR1 && UR1[idx1] >= 0;
+      if (P.onlyStereo && !st1) continue;
+      const int idx2 = (int)F2[f0 + j];
+      if (PI2[idx2] >= 0) continue;  // :792-797
+      const bool st2 = UR2 && UR2[idx2] >= 0;
+      if (P.onlyStereo && !st2) continue;
+      const int dist = hamming256(load_desc(D1 + (size_t)idx1 * 32),
+                                  load_desc(D2 + (size_t)idx2 * 32));
+      if (dist > 50) continue;  // TH_LOW, and bestDist starts there (:784, :809)
+      const orb_keypoint_t kp2 = K2[idx2];
+      if (kp2.octave < 0 || kp2.octave >= P.nLevels) {  // the reference reads past mvScaleFactors
+        ++undefined;
+        continue;
+      }
+      if (!st1 && !st2) {  // :814-821
+        const float dx = ex - kp2.x, dy = ey - kp2.y;
+        if (dx * dx + dy * dy < 100 * lvScale[kp2.octave]) continue;
+      }
+      const float x1 = K1[idx1].x, y1 = K1[idx1].y;
+      const float la = x1 * F[0] + y1 * F[3] + F[6];  // epipolar line (:147-149)
+      const float lb = x1 * F[1] + y1 * F[4] + F[7];
+      const float lc = x1 * F[2] + y1 * F[5] + F[8];
+      const float den = la * la + lb * lb;
+      if (den == 0) continue;
+      const float num = la * kp2.x + lb * kp2.y + lc;
+      const float dsqr = __fdiv_rn(num * num, den);
+      if (!((double)dsqr < 3.84 * (double)lvSigma2[kp2.octave])) continue;
+      atomicMin(&mword[idx1], ((uint32_t)dist << 20) | (uint32_t)(0xFFFFF - (f0 + j)));
+    }
+  }
+  tried = wave_sum(tried);
+  undefined = wave_sum(undefined);
+  if (lane == 0) {
+    if (tried) atomicAdd(&ctl[1], tried);
+    if (undefined) atomicAdd(&ctl[6], undefined);
+  }
+  __syncthreads();
+
+  // ---- the winners: KF2 index and rotation bin per KF1 keypoint (:830-850)
+  int accepted = 0;
+  for (int i = tid; i < n1; i += TB_T) {
+    const uint32_t key = mword[i];
+    if (key == TB_NONE) continue;
+    ++accepted;
+    const int idx2 = (int)F2[0xFFFFF - (int)(key & 0xFFFFFu)];
+    const int bin = P.checkOri ? rot_bin(K1[i].angle - K2[idx2].angle) : 0;
+    if (P.checkOri) atomicAdd(&hist[bin], 1);
+    mword[i] = (uint32_t)idx2 | ((uint32_t)bin << 24);
+  }
+  for (int i = tid; i < n2; i += TB_T) cnt2[i] = 0;  // the partner table is dead
+  accepted = wave_sum(accepted);
+  if (lane == 0 && accepted) atomicAdd(&ctl[3], accepted);
+  __syncthreads();
+
+  // ---- rotation filter (:867-886) and the row
+  int ind1 = -1, ind2 = -1, ind3 = -1;
+  if (P.checkOri) tb_three_maxima(hist, ind1, ind2, ind3);
+  int removed = 0;
+  for (int i = tid; i < n1; i += TB_T) {
+    const uint32_t e = mword[i];
+    int m = -1;
+    if (e != TB_NONE) {
+      const int b = (int)(e >> 24);
+      if (P.checkOri && b != ind1 && b != ind2 && b != ind3) {
+        ++removed;
+        mword[i] = TB_NONE;
+      } else {
+        m = (int)(e & 0xFFFFFFu);
+        atomicAdd(&cnt2[m], 1);
+      }
+    }
+    M12[i] = m;
+  }
+  removed = wave_sum(removed);
+  if (lane == 0 && removed) atomicAdd(&ctl[4], removed);
+  __syncthreads();
+  int shared = 0;
+  for (int i = tid; i < n1; i += TB_T) {
+    const uint32_t e = mword[i];
+    shared += e != TB_NONE && cnt2[e & 0xFFFFFFu] > 1;
+  }
+  shared = wave_sum(shared);
+  if (lane == 0 && shared) atomicAdd(&ctl[5], shared);
+  __syncthreads();
+  if (tid == 0) {
+    info[p].n_matches = ctl[3] - ctl[4];
+    info[p].n_accepted = ctl[3];
+    info[p].n_common_nodes = ctl[2];
+    info[p].n_tried = ctl[1];
+    info[p].n_shared2 = ctl[5];
+    info[p].n_undefined = ctl[6];
+  }
+}
+
+// dynamic LDS of one k_tri_batch workgroup at `stride` keypoint slots
+static size_t tri_batch_lds(int stride) {
+  return 8 * (((size_t)stride + 3) & ~(size_t)3);
+}
+
+extern "C" int orb_k_tri_batch_max_stride(void) {
+  // 8 B per slot plus the static part within 160 KiB; the match key holds 20
+  // position bits, the match word 24 index bits
+  int s = (int)((ORB_LDS_PER_CU - TB_STATIC_LDS) / 8) & ~3;
+  while (tri_batch_lds(s) + TB_STATIC_LDS > ORB_LDS_PER_CU) s -= 4;
+  return std::min(s, (1 << 15) - 4);
+}
+
+extern "C" hipError_t orb_k_tri_batch(const TriBatchParams* params, int32_t* match12,
+                                      orb_tri_match_info_t* info, hipStream_t s) {
+  const TriBatchParams P = *params;
+  if (P.stride <= 0 || P.stride > orb_k_tri_batch_max_stride() || P.nLevels < 1 ||
+      P.nLevels > ORB_MAX_LEVELS)
+    return hipErrorInvalidValue;
+  const size_t lds = tri_batch_lds(P.stride);
+  if (lds > 65536 - TB_STATIC_LDS) {
+    hipError_t e = hipFuncSetAttribute((const void*)k_tri_batch,
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(k_tri_batch, dim3(P.nProblems), dim3(TB_T), lds, s, P, match12, info);
   return hipGetLastError();
 }
 

@@ -983,6 +983,31 @@ class ORBmatcher {
               d_status, d_x3d, d_new_pairs, d_info, stream),
           "create_new_map_points_batch");
   }
+  // Device-batched SearchForTriangulation (orb_search_for_triangulation_batch;
+  // src/ORBmatcher.cc:718-901 as src/LocalMapping.cc:313-318 calls it) with
+  // mbCheckOrientation, on the keyframe slots of search_by_bow_batch plus the
+  // arrays of create_new_map_points_batch: d_match12 is the row that call
+  // reads.  d_kf_u_right may be null (every keypoint monocular); cam2,
+  // scaleFactors and levelSigma2 are pKF2's.
+  void search_for_triangulation_batch(
+      int n_problems, const int32_t* d_kf1_slot, const int32_t* d_kf2_slot, const BowSlots& kf,
+      const int32_t* d_kf_point_index, const float* d_kf_u_right, const orb_pose_t* d_kf_pose,
+      int kp_stride, const float* d_f12, const orb_camera_t& cam2,
+      const std::vector<float>& scaleFactors, const std::vector<float>& levelSigma2,
+      bool only_stereo, int32_t* d_match12, orb_tri_match_info_t* d_info,
+      void* stream = nullptr) {
+    assert(scaleFactors.size() == levelSigma2.size());
+    check(orb_search_for_triangulation_batch(
+              h_, n_problems, d_kf1_slot, d_kf2_slot, kf.d_keys, kf.d_desc, kf.d_nkeys,
+              d_kf_point_index, kf.d_fv_nodes, kf.d_fv_offs, kf.d_fv_feats, kf.d_n_fv_nodes,
+              d_kf_u_right, d_kf_pose, kp_stride, d_f12, &cam2, scaleFactors.data(),
+              levelSigma2.data(), (int)scaleFactors.size(), only_stereo ? 1 : 0,
+              mbCheckOrientation ? 1 : 0, d_match12, d_info, stream),
+          "search_for_triangulation_batch");
+  }
+  static int search_for_triangulation_batch_max_stride() {
+    return orb_search_for_triangulation_batch_max_stride();
+  }
   static int scene_median_depth_max_stride() { return orb_scene_median_depth_max_stride(); }
   static int create_new_map_points_max_stride() {
     return orb_create_new_map_points_max_stride();

@@ -62,6 +62,13 @@ results table:
       20, minimum, maximum); the median-depth batch over the 64 neighbours;
       against the same call one pair at a time (64 launches) + exact check of
       four problems against tests/newpoints_ref.py
+  G1  LocalMapping::CreateNewMapPoints' matcher, SearchForTriangulation: 64
+      keyframe pairs of about 1,000 keypoints in the slot layout, natural
+      FeatureVectors (scenarios.vocab_nodes), has_mp 0 % / 50 %, one launch,
+      by device events (median of 20, minimum, maximum), also 1 and 16
+      problems; against orb_search_for_triangulation over the same pairs one
+      blocking call at a time (host clock) + exact check of four problems
+      against the oracle and the one-problem entry
   R1  RGB-D: 640x480 (TUM1 intrinsics and distortion, DepthMapFactor 5000),
       1000 features, 256 frames per launch, device-resident: extract ->
       undistort -> ComputeStereoFromRGBD -> closest points + UnprojectStereo ->
@@ -69,7 +76,7 @@ results table:
       same pipeline without the RGB-D stages (monocular matcher), each new
       kernel alone by HIP events with its algorithmic bytes + exact check
 
-Usage: python tools/bench_configs.py [--configs C1,C2,C3,C5,F1,F3,P1,R1,T1,M1,B1,S1,N1] [--steps K]
+Usage: python tools/bench_configs.py [--configs C1,C2,C3,C5,F1,F3,P1,R1,T1,M1,B1,S1,N1,G1] [--steps K]
 The oracle (CPU restatement) is used only for the CPU rows and parity checks.
 """
 import argparse
@@ -1133,6 +1140,116 @@ def n1(args, orb, oracle, torch):
             "exact_vs_restatement": bool(exact)}
 
 
+def g1(args, orb, oracle, torch):
+    import scenarios as S
+    import tri_batch_ref as T
+    P = 64
+    probs = []
+    for i in range(P):
+        k0, k1 = S.keyframe_pair(oracle, 3 + i, rng_seed=1 + i, baseline=(0.5, 0.0, 0.1))
+        rng = np.random.default_rng(16 + i)
+        frac = 0.5 if i % 2 else 0.0       # a fresh keyframe, and one half covered with points
+        pidx = [np.where(rng.random(len(k["keys"])) < frac, np.arange(len(k["keys"])), -1)
+                .astype(np.int32) for k in (k0, k1)]
+        probs.append(T.from_keyframes(oracle, k0, k1, *pidx))
+        host = (S.camera(), k1["scale"], k1["sigma2"])
+    sides = [s for q in probs for s in q[:2]]
+    f12 = np.stack([q[2] for q in probs]).astype(np.float32)
+    stride = max(len(s["desc"]) for s in sides)
+    arr = T.pack_slots(sides, stride)
+
+    def dev(a):
+        return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).cuda()
+    d = {k: dev(v) for k, v in arr.items()}
+    s1, s2 = dev(np.arange(0, 2 * P, 2, dtype=np.int32)), dev(np.arange(1, 2 * P, 2, dtype=np.int32))
+    d_f12 = dev(f12)
+    m12 = torch.full((P * stride,), -7, dtype=torch.int32, device="cuda")
+    info = torch.zeros(P * 6, dtype=torch.int32, device="cuda")
+    m = orb.ORBmatcher(0.6, True)
+    stream = torch.cuda.Stream()
+    sp = stream.cuda_stream
+
+    def batch(n=P):
+        m.search_for_triangulation_batch(
+            n, s1.data_ptr(), s2.data_ptr(), d["keys"].data_ptr(), d["desc"].data_ptr(),
+            d["nkeys"].data_ptr(), d["pidx"].data_ptr(), d["fv_nodes"].data_ptr(),
+            d["fv_offs"].data_ptr(), d["fv_feats"].data_ptr(), d["n_fv_nodes"].data_ptr(),
+            d["u_right"].data_ptr(), d["pose"].data_ptr(), stride, d_f12.data_ptr(), host[0],
+            host[1], host[2], False, m12.data_ptr(), info.data_ptr(), sp)
+
+    def events(fn, reps=20):
+        t = []
+        for _ in range(reps):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            fn()
+            e1.record(stream)
+            torch.cuda.synchronize()
+            t.append(e0.elapsed_time(e1))
+        t.sort()
+        return {"median": t[len(t) // 2], "min": t[0], "max": t[-1]}
+
+    frames = [(orb.Frame(a["keys"], a["desc"], host[1], 1241, 376, u_right=a["u_right"]),
+               (a["pidx"] >= 0).astype(np.uint8),
+               orb.Frame(b["keys"], b["desc"], host[1], 1241, 376, u_right=b["u_right"]),
+               (b["pidx"] >= 0).astype(np.uint8), a, b, f) for a, b, f in probs]
+
+    def one(p):
+        fa, ha, fb, hb, a, b, f = frames[p]
+        return m.SearchForTriangulation(fa, ha, fb, hb, host[2], f, host[0], a["pose"]["ow"],
+                                        b["pose"]["rcw"], b["pose"]["tcw"], a["fv"], b["fv"], False)
+
+    def serial(reps=20):
+        t = []
+        for _ in range(reps):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for p in range(P):
+                one(p)
+            t.append((time.perf_counter() - t0) * 1e3)   # every call ends in a synchronise
+        t.sort()
+        return {"median": t[len(t) // 2], "min": t[0], "max": t[-1]}
+
+    for _ in range(3):
+        batch()
+        one(0)
+    torch.cuda.synchronize()
+    t_batch = {n: events(lambda n=n: batch(n)) for n in (P, 16, 1)}
+    t_serial = serial()
+    batch()
+    torch.cuda.synchronize()
+    rows = m12.cpu().numpy().reshape(P, stride)
+    inf = info.cpu().numpy().view(T.INFO_DTYPE)
+    exact = True
+    for p in (0, 1, P // 2, P - 1):
+        row, want = T.expected(oracle, *probs[p], *host, False, True)
+        exact &= np.array_equal(rows[p, :len(row)], row) and tuple(inf[p]) == want
+        n, r1 = one(p)
+        exact &= n == want[0] and np.array_equal(r1, row)
+    nk = [len(s["desc"]) for s in sides]
+    return {"config": "G1", "library": str(orb.LIB_PATH),
+            "workload": f"SearchForTriangulation, {P} keyframe pairs of {min(nk)}-{max(nk)} "
+                        f"keypoints ({stride} slots), natural FeatureVectors "
+                        f"({int(np.mean([len(s['fv'][0]) for s in sides]))} nodes on average), "
+                        f"has_mp 0 % / 50 % alternating, orientation on",
+            "batch_ms": t_batch[P], "batch16_ms": t_batch[16], "batch1_ms": t_batch[1],
+            "one_per_call_ms": t_serial,
+            "one_per_call_over_batch": t_serial["median"] / t_batch[P]["median"],
+            "timing": "batch: device events around the one launch, median of 20; one per call: "
+                      "host clock around 64 blocking orb_search_for_triangulation calls (14 "
+                      "uploads and 2 downloads each), median of 20; the has_mp downloads and the "
+                      "match12 upload of the integrator's loop are not in it",
+            "n_matches_mean": float(inf["n_matches"].mean()),
+            "n_matches_range": [int(inf["n_matches"].min()), int(inf["n_matches"].max())],
+            "n_tried_mean": float(inf["n_tried"].mean()),
+            "n_shared2_mean": float(inf["n_shared2"].mean()),
+            "max_stride": orb.ORBmatcher.search_for_triangulation_batch_max_stride(),
+            "kernel_resources": "k_tri_batch: 48 VGPRs, 96 SGPRs, no spill, ScratchSize 0, "
+                                "occupancy 8 waves/SIMD, 544 B static LDS (hipcc "
+                                "-Rpass-analysis=kernel-resource-usage, gfx950)",
+            "exact_vs_oracle_and_one_problem_entry": bool(exact)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--configs", default="C1,C2,C3,C5")
@@ -1175,6 +1292,8 @@ def main():
             r = s1(args, orb, oracle, torch)
         elif c == "N1":
             r = n1(args, orb, oracle, torch)
+        elif c == "G1":
+            r = g1(args, orb, oracle, torch)
         else:
             raise SystemExit(f"unknown config {c}")
         print(json.dumps(r), flush=True)
