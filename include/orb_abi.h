@@ -1876,6 +1876,124 @@ int orb_abi_version(void);
 orb_status_t orb_device_count(int* n);
 const char* orb_status_string(orb_status_t s);
 
+/* ------------------------------------------ Optimizer::OptimizeSim3 on the device */
+
+/* Optimizer::OptimizeSim3 (src/Optimizer.cc:1130-1326) for n_problems
+ * independent (pKF1, pKF2, vpMatches1, g2oS12) problems, the last stage of
+ * LoopClosing::ComputeSim3: one free VertexSim3Expmap against two edges per
+ * correspondence (EdgeSim3ProjectXYZ, EdgeInverseSim3ProjectXYZ), both
+ * optimize() calls, both classifications and the nCorrespondences - nBad < 10
+ * gate in one launch, one workgroup per problem.  Every per-problem array is a
+ * device pointer; the call is asynchronous on `stream`, does not synchronise
+ * with the host and uses none of the handle's scratch. */
+typedef struct orb_sim3_opt_result {
+  int32_t status;     /* 0; -1: malformed (below) */
+  int32_t n_corr;     /* nCorrespondences */
+  int32_t n_bad;      /* nBad of the first check */
+  int32_t n_inliers;  /* the return value (0 on the early return) */
+  double q[4];        /* g2oS12 after the call: rotation (x, y, z, w), not normalised */
+  double t[3];        /*   translation */
+  double s;           /*   scale */
+  float R[9];         /* q.toRotationMatrix() narrowed to float, row-major */
+  float t_f[3];       /* t narrowed */
+  float s_f;          /* s narrowed */
+  int32_t _pad;       /* written as 0 */
+} orb_sim3_opt_result_t; /* 136 bytes */
+
+/* Keyframes: the slot layout of orb_sim3_solver_setup_batch (d_kf1_slot,
+ * d_kf2_slot, d_kf_keys, d_kf_nkeys, d_kf_point_index, d_kf_pose, kp_stride,
+ * d_points; the same NOT-checked ranges).  d_kf1_slot / d_kf2_slot may be NULL as
+ * there: problem p then uses slot p (for both keyframes if both are NULL).
+ * Matches: d_match12 + p * kp_stride holds, per i < N (keyframe 1's clamped count), the global point index of
+ * vpMatches1[i] (negative: NULL), d_index2 + p * kp_stride holds
+ * pMP2->GetIndexInKeyFrame(pKF2): the arrays given to the solver, after
+ * SearchBySim3's row has been merged into them.
+ * Start: d_start[p].R, .t, .scale are g2oS12 = Sim3(toMatrix3d(R),
+ * toVector3d(t), s): floats widened to double, Quaterniond(Matrix3d), no
+ * normalisation.  A problem with d_start[p].has_sim3 == 0, or with
+ * d_active[p] == 0 (d_active optional), is skipped: nothing of it is read or
+ * written.  d_result of orb_sim3_solver_iterate_batch may be passed as it is.
+ * Host values: inv_level_sigma2[n_levels] (mvInvLevelSigma2 of both keyframes;
+ * 1 <= n_levels <= 16), cam1 / cam2 (fx, fy, cx, cy are read), th2 (float),
+ * fix_scale.
+ * Skips, in the reference's order (:1185-1220): NULL match, NULL pMP1, either
+ * point bad, i2 < 0.  A kept pair whose i2 is at or above keyframe 2's clamped
+ * count, or with either keypoint's octave outside [0, n_levels), makes the
+ * problem malformed: d_out[p] = {status -1, counts 0, the start value}, its
+ * d_match12 row is not written, and nothing is indexed with the bad value.
+ * Out: d_match12 in place, -1 wherever the reference stores NULL (after the
+ * first optimize(5), also when the gate then returns 0, and after the second
+ * optimize); d_out[p].  On the early return the Sim3 fields hold the start
+ * value (g2oS12 is not assigned there).
+ * Capacity: the compacted pair records (56 bytes each) stay in LDS beside
+ * 39,648 bytes of term tiles and solver state;
+ * orb_optimize_sim3_max_stride() is the largest kp_stride that fits the 160
+ * KiB of one CU (a pure function, callable without a device).  Above it:
+ * ORB_ECAPACITY before anything is launched, nothing written (no scratch tier).
+ * ORB_EINVAL: a null required pointer, n_problems < 0, kp_stride <= 0, n_levels
+ * outside [1, 16].  n_problems == 0: ORB_OK, no launch.
+ *
+ * Pins (the same list stands in tests/sim3opt_ref.py and DESIGN.md 4.12; g2o
+ * and Eigen themselves are not available to the project: unpinned against
+ * their binaries).  Doubles throughout, every expression as written, no
+ * contraction; the Eigen closed forms, LDLT<MatrixXd> rules (here n = 7) and
+ * Levenberg-Marquardt rules are those of orb_pose_optimization.
+ *  O1  P3D1c, P3D2c = Rcw * X + tcw in float (the Sim3 solver's pin P1), then
+ *      widened.
+ *  O2  Jacobians are numeric (base_binary_edge.hpp:131-200): column d =
+ *      (1.0 / (2 * 1e-9)) * (e(+1e-9 e_d) - e(-1e-9 e_d)), each through
+ *      oplusImpl: Sim3(update) * estimate.  _error is restored afterwards.
+ *  O3  constructQuadraticForm of a binary edge whose `to` vertex alone is
+ *      free (:91-113): omega_r = -(Omega e), omega_r *= rho[1], b += B^T omega_r
+ *      ((B_0q r_0) + (B_1q r_1)), A += (B^T (rho[1] Omega)) B ((B_0q w) B_0p +
+ *      (B_1q w) B_1p, w = rho[1] * invSigma2), the zero off-diagonal terms of
+ *      the diagonal Omega dropped; the lower triangle is accumulated.
+ *  O4  The active edges add in insertion order e12(i), e21(i), e12(i'),
+ *      e21(i'), ... over ascending i; a removed pair adds +0.0.
+ *  O5  An edge is classified from the error of the last trial, rejected or
+ *      not; chi2() > th2 compares the double chi2 with the float th2 widened;
+ *      deltaHuber is the float sqrt(th2) widened; Huber's inlier test is <=.
+ *  O6  oplusImpl with fix_scale writes update[6] = 0 into the caller's array:
+ *      column 6 is the difference of two equal evaluations, and the solver's
+ *      x[6] is zeroed before computeScale reads it.
+ *  O7  Sim3(Vector7d) (sim3.h:70-142): branches |sigma| < 1e-5 x theta < 1e-5,
+ *      R = (I + Omega) + Omega^2 or (I + (sin / theta) Omega) + ((1 - cos) /
+ *      (theta theta)) Omega^2, A, B, C as written, W = ((A Omega) + (B Omega^2))
+ *      + (C I), t = W upsilon; Quaterniond(R) is never normalised, nor are
+ *      operator*, map or inverse(); inverse() = (r.conjugate(),
+ *      r.conjugate() * ((-1. / s) * t), 1. / s); project is two divisions by z.
+ *  O8  The second optimize starts at iteration 0: lambda from the 7 diagonals,
+ *      ni = 2; the solver's x is kept across both.
+ *  O9  exp = pinned_exp (fdlibm e_exp.c from IEEE operations alone); sin and
+ *      cos = pinned_sincos_d; sqrt and / are IEEE. */
+orb_status_t orb_optimize_sim3_batch(
+    orb_matcher_t* m, int n_problems, const int32_t* d_kf1_slot, const int32_t* d_kf2_slot,
+    const orb_keypoint_t* d_kf_keys, const int32_t* d_kf_nkeys, const int32_t* d_kf_point_index,
+    const orb_pose_t* d_kf_pose, int kp_stride, const orb_map_point_t* d_points,
+    int32_t* d_match12, const int32_t* d_index2, const orb_sim3_result_t* d_start,
+    const uint8_t* d_active, const float* inv_level_sigma2, int n_levels,
+    const orb_camera_t* cam1, const orb_camera_t* cam2, float th2, int fix_scale,
+    orb_sim3_opt_result_t* d_out, void* stream);
+int orb_optimize_sim3_max_stride(void);
+
+/* One problem with host pointers (synchronises): keys1[n1] / keys2[n2]
+ * (mvKeysUn), point_index1[n1] (GetMapPointMatches() of pKF1), pose1 / pose2,
+ * points[n_points], match12[n1] (in/out) and index2[n1], start (R, t, scale are
+ * read; has_sim3 is ignored), out.  Every non-negative point index must be
+ * below n_points (ORB_EINVAL).  Otherwise as the batch of one. */
+orb_status_t orb_optimize_sim3(
+    orb_matcher_t* m, const orb_keypoint_t* keys1, int n1, const int32_t* point_index1,
+    const orb_pose_t* pose1, const orb_keypoint_t* keys2, int n2, const orb_pose_t* pose2,
+    const orb_map_point_t* points, int n_points, int32_t* match12, const int32_t* index2,
+    const orb_sim3_result_t* start, const float* inv_level_sigma2, int n_levels,
+    const orb_camera_t* cam1, const orb_camera_t* cam2, float th2, int fix_scale,
+    orb_sim3_opt_result_t* out);
+
+/* pinned_exp (pin O9) over n device doubles, for tests of the pin: d_y[i] =
+ * pinned_exp(d_x[i]).  Asynchronous on `stream`. */
+orb_status_t orb_pinned_exp_batch(orb_matcher_t* m, int n, const double* d_x, double* d_y,
+                                  void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -74,6 +74,11 @@ SIM3_RESULT_DTYPE = np.dtype([("has_sim3", "<i4"), ("no_more", "<i4"), ("n_inlie
                               ("R", "<f4", (9,)), ("t", "<f4", (3,)), ("scale", "<f4")])
 assert SIM3_CORR_DTYPE.itemsize == 56 and SIM3_STATE_DTYPE.itemsize == 184
 assert SIM3_RESULT_DTYPE.itemsize == 132
+SIM3_OPT_RESULT_DTYPE = np.dtype([("status", "<i4"), ("n_corr", "<i4"), ("n_bad", "<i4"),
+                                  ("n_inliers", "<i4"), ("q", "<f8", (4,)), ("t", "<f8", (3,)),
+                                  ("s", "<f8"), ("R", "<f4", (9,)), ("t_f", "<f4", (3,)),
+                                  ("s_f", "<f4"), ("_pad", "<i4")])
+assert SIM3_OPT_RESULT_DTYPE.itemsize == 136
 NEW_POINT_INFO_DTYPE = np.dtype([("gated", "<i4"), ("overflow", "<i4"), ("n_new", "<i4"),
                                  ("first_point", "<i4"), ("counts", "<i4", (12,))])
 assert NEW_POINT_INFO_DTYPE.itemsize == 64
@@ -282,6 +287,12 @@ def lib() -> ctypes.CDLL:
                                                      vp, vp, vp, i32, vp, vp, vp, vp, i32, i32,
                                                      i32, vp, vp, vp]),
         "orb_search_for_triangulation_batch_max_stride": (i32, []),
+        "orb_optimize_sim3_batch": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp,
+                                          vp, i32, vp, vp, f32, i32, vp, vp]),
+        "orb_optimize_sim3_max_stride": (i32, []),
+        "orb_optimize_sim3": (i32, [vp, vp, i32, vp, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, i32,
+                                    vp, vp, f32, i32, vp]),
+        "orb_pinned_exp_batch": (i32, [vp, i32, vp, vp, vp]),
         "orb_synth_image": (None, [ctypes.c_uint64, i32, i32, i32, i32, vp, sz]),
         "orb_synth_local_map": (None, [ctypes.c_uint64, vp, vp, i32, i32, i32, i32, vp, vp, vp]),
     }
@@ -297,7 +308,8 @@ def lib() -> ctypes.CDLL:
              "orb_scene_median_depth_max_stride", "orb_scene_median_depth",
              "orb_create_new_map_points_batch", "orb_create_new_map_points_max_stride",
              "orb_create_new_map_points", "orb_search_for_triangulation_batch",
-             "orb_search_for_triangulation_batch_max_stride")
+             "orb_search_for_triangulation_batch_max_stride", "orb_optimize_sim3_batch",
+             "orb_optimize_sim3_max_stride", "orb_optimize_sim3", "orb_pinned_exp_batch")
     for name, (res, args) in sig.items():
         if name in newer and "ORB_AMD_LIB" in os.environ and not hasattr(L, name):
             continue
@@ -356,6 +368,13 @@ def sim3_solver_max_stride() -> int:
     accepts; a pure function of k_sim3_iterate's LDS layout, callable without
     a device."""
     return lib().orb_sim3_solver_max_stride()
+
+
+def optimize_sim3_max_stride() -> int:
+    """orb_optimize_sim3_max_stride(): the largest kp_stride optimize_sim3_batch
+    accepts; a pure function of k_optimize_sim3's LDS layout, callable without
+    a device."""
+    return lib().orb_optimize_sim3_max_stride()
 
 
 class MapView:
@@ -1475,6 +1494,74 @@ class ORBmatcher:
     def sim3_solver_max_stride() -> int:
         """Largest kp_stride the Sim3Solver batch accepts."""
         return lib().orb_sim3_solver_max_stride()
+
+    # ------------------------------------------------- Optimizer::OptimizeSim3
+    def optimize_sim3_batch(self, n_problems, d_kf1_slot, d_kf2_slot, d_kf_keys, d_kf_nkeys,
+                            d_kf_point_index, d_kf_pose, kp_stride, d_points, d_match12, d_index2,
+                            d_start, inv_level_sigma2, cam1, cam2, d_out, th2: float = 10.0,
+                            fix_scale: bool = False, d_active: int = 0, stream: int = 0):
+        """Optimizer::OptimizeSim3 for n_problems (pKF1, pKF2, vpMatches1, g2oS12)
+        problems (orb_optimize_sim3_batch).  d_* are device addresses in the
+        slot layout of sim3_solver_setup_batch; d_match12 is updated in place;
+        d_start holds n_problems SIM3_RESULT_DTYPE records (the solver's
+        d_result serves as it is), d_out n_problems SIM3_OPT_RESULT_DTYPE
+        records.  Asynchronous on `stream`."""
+        ls = np.ascontiguousarray(inv_level_sigma2, np.float32).reshape(-1)
+        c1, c2 = self._camera4(cam1), self._camera4(cam2)
+        _check(lib().orb_optimize_sim3_batch(
+            self._h, n_problems, d_kf1_slot or None, d_kf2_slot or None, d_kf_keys or None,
+            d_kf_nkeys or None, d_kf_point_index or None, d_kf_pose or None, kp_stride,
+            d_points or None, d_match12 or None, d_index2 or None, d_start or None,
+            d_active or None, _ptr(ls) if len(ls) else None, len(ls), ctypes.byref(c1),
+            ctypes.byref(c2), float(th2), int(bool(fix_scale)), d_out or None, stream or None),
+            "optimize_sim3_batch")
+
+    def OptimizeSim3(self, keys1, point_index1, pose1, keys2, pose2, points, match12, index2,
+                     start_R, start_t, start_scale, inv_level_sigma2, cam1, cam2,
+                     th2: float = 10.0, bFixScale: bool = False):
+        """Optimizer::OptimizeSim3 for one problem with host arrays
+        (orb_optimize_sim3).  keys1 / keys2: KEYPOINT_DTYPE (mvKeysUn);
+        point_index1: GetMapPointMatches() of pKF1 as indices into `points`
+        (MAP_POINT_DTYPE); match12: the point index of vpMatches1[i] or
+        negative; index2: GetIndexInKeyFrame(pKF2) per i; the start is g2oS12
+        as float R (9), t (3) and scale.  Returns (nInliers, match12 updated,
+        the SIM3_OPT_RESULT_DTYPE record)."""
+        k1 = np.ascontiguousarray(keys1, KEYPOINT_DTYPE).reshape(-1)
+        k2 = np.ascontiguousarray(keys2, KEYPOINT_DTYPE).reshape(-1)
+        n1 = len(k1)
+        pi1 = np.ascontiguousarray(np.asarray(point_index1, np.int32).reshape(-1)[:n1])
+        m12 = np.ascontiguousarray(np.asarray(match12, np.int32).reshape(-1)[:n1]).copy()
+        i2 = np.ascontiguousarray(np.asarray(index2, np.int32).reshape(-1)[:n1])
+        if not (len(pi1) == n1 and len(m12) == n1 and len(i2) == n1):
+            raise OrbError(ORB_EINVAL, "OptimizeSim3: arrays shorter than keys1")
+        p1, p2 = np.zeros(1, POSE_DTYPE), np.zeros(1, POSE_DTYPE)
+        p1[0], p2[0] = pose1, pose2
+        pts = np.ascontiguousarray(points, MAP_POINT_DTYPE).reshape(-1)
+        st = np.zeros(1, SIM3_RESULT_DTYPE)
+        st["has_sim3"], st["scale"] = 1, np.float32(start_scale)
+        st["R"][0] = np.asarray(start_R, np.float32).reshape(9)
+        st["t"][0] = np.asarray(start_t, np.float32).reshape(3)
+        ls = np.ascontiguousarray(inv_level_sigma2, np.float32).reshape(-1)
+        c1, c2 = self._camera4(cam1), self._camera4(cam2)
+        out = np.zeros(1, SIM3_OPT_RESULT_DTYPE)
+        _check(lib().orb_optimize_sim3(
+            self._h, _ptr(k1) if n1 else None, n1, _ptr(pi1) if n1 else None, _ptr(p1),
+            _ptr(k2) if len(k2) else None, len(k2), _ptr(p2), _ptr(pts) if len(pts) else None,
+            len(pts), _ptr(m12) if n1 else None, _ptr(i2) if n1 else None, _ptr(st),
+            _ptr(ls) if len(ls) else None, len(ls), ctypes.byref(c1), ctypes.byref(c2),
+            float(th2), int(bool(bFixScale)), _ptr(out)), "OptimizeSim3")
+        return int(out["n_inliers"][0]), m12, out[0]
+
+    @staticmethod
+    def optimize_sim3_max_stride() -> int:
+        """Largest kp_stride optimize_sim3_batch accepts."""
+        return lib().orb_optimize_sim3_max_stride()
+
+    def pinned_exp_batch(self, n, d_x, d_y, stream: int = 0):
+        """pinned_exp over n device doubles (orb_pinned_exp_batch; test support
+        for the pin)."""
+        _check(lib().orb_pinned_exp_batch(self._h, n, d_x or None, d_y or None, stream or None),
+               "pinned_exp_batch")
 
     # ----------------------------------------- LocalMapping::CreateNewMapPoints
     def scene_median_depth_batch(self, n_problems, d_slot, d_kf_nkeys, d_kf_point_index,

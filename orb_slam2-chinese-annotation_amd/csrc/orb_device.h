@@ -224,6 +224,59 @@ __device__ __forceinline__ double pinned_log(double x) {
   return k == 0 ? f - s * (f - R) : dk * ln2_hi - ((s * (f - R) - dk * ln2_lo) - f);
 }
 
+// ---------------------------------------------------- pinned exp (double)
+// fdlibm's e_exp.c from IEEE operations alone (g2o::Sim3's std::exp(sigma);
+// DESIGN.md §4.12): x = k ln2 + r with |r| <= 0.5 ln2 as hi - lo, c = r - r^2 P(r^2)
+// with a degree-5 polynomial, exp(r) = 1 - ((lo - r c / (2 - c)) - hi) (k == 0: 1 - (r c / (c - 2) - r)), scaled by
+// 2^k through the exponent field (k < -1021: by 2^(k + 1000), then * 2^-1000).
+// |x| < 2^-28 returns 1 + x; overflow gives +inf, underflow +0, NaN x + x,
+// exp(-inf) = +0.  The same text stands in tests/sim3opt_ref.py.
+__device__ __forceinline__ double pinned_exp(double x) {
+  const double o_threshold = 7.09782712893383973096e+02, u_threshold = -7.45133219101941108420e+02;
+  const double ln2HI = 6.93147180369123816490e-01, ln2LO = 1.90821492927058770002e-10;
+  const double invln2 = 1.44269504088896338700e+00, twom1000 = 9.33263618503218878990e-302;
+  const double P1 = 1.66666666666666019037e-01, P2 = -2.77777777770155933842e-03,
+               P3 = 6.61375632143793436117e-05, P4 = -1.65339022054652515390e-06,
+               P5 = 4.13813679705723846039e-08;
+  const unsigned long long bits = (unsigned long long)__double_as_longlong(x);
+  unsigned int hx = (unsigned int)(bits >> 32);
+  const unsigned int lx = (unsigned int)bits;
+  const int xsb = (int)(hx >> 31) & 1;
+  hx &= 0x7fffffffu;
+  if (hx >= 0x40862E42u) {  // |x| >= 709.78
+    if (hx >= 0x7ff00000u) {
+      if (((hx & 0xfffffu) | lx) != 0) return x + x;  // NaN
+      return xsb == 0 ? x : 0.0;                      // exp(+-inf) = inf, 0
+    }
+    if (x > o_threshold) return __builtin_inf();  // huge * huge
+    if (x < u_threshold) return 0.0;              // twom1000 * twom1000
+  }
+  double hi = 0.0, lo = 0.0;
+  int k = 0;
+  if (hx > 0x3fd62e42u) {    // |x| > 0.5 ln2
+    if (hx < 0x3FF0A2B2u) {  // |x| < 1.5 ln2
+      hi = xsb ? x - (-ln2HI) : x - ln2HI;
+      lo = xsb ? -ln2LO : ln2LO;
+      k = 1 - xsb - xsb;
+    } else {
+      k = (int)(invln2 * x + (xsb ? -0.5 : 0.5));
+      const double t = (double)k;
+      hi = x - t * ln2HI;
+      lo = t * ln2LO;
+    }
+    x = hi - lo;
+  } else if (hx < 0x3e300000u) {  // |x| < 2^-28
+    return 1.0 + x;
+  }
+  const double t = x * x;
+  const double c = x - t * (P1 + t * (P2 + t * (P3 + t * (P4 + t * P5))));
+  if (k == 0) return 1.0 - ((x * c) / (c - 2.0) - x);
+  const double y = 1.0 - ((lo - (x * c) / (2.0 - c)) - hi);
+  const long long yb = __double_as_longlong(y);
+  if (k >= -1021) return __longlong_as_double(yb + ((long long)k << 52));
+  return __longlong_as_double(yb + ((long long)(k + 1000) << 52)) * twom1000;
+}
+
 // Buffer resources: 32-bit per-lane offsets (no 64-bit address VALU) and a
 // hardware range check per dword (a dword load that ends past `bytes` reads
 // as 0, a store past it is dropped).  Build only from wave-uniform values.

@@ -309,6 +309,29 @@ struct Sim3IterParams {
   orb_sim3_result_t* result;
 };
 
+// ------------------------------------------------------ sim3opt_kernels.hip
+// Optimizer::OptimizeSim3 over nProblems (by value)
+struct Sim3OptParams {
+  int nProblems, stride;
+  const int32_t* kf1Slot;  // null: p
+  const int32_t* kf2Slot;
+  const orb_keypoint_t* keys;
+  const int32_t* nkeys;
+  const int32_t* pointIndex;
+  const orb_pose_t* pose;
+  const orb_map_point_t* points;
+  int32_t* match12;        // in/out
+  const int32_t* index2;
+  const orb_sim3_result_t* start;
+  const uint8_t* active;   // null: every problem
+  int nLevels;
+  float invLevelSigma2[ORB_MAX_LEVELS];
+  float k1[4], k2[4];      // fx, fy, cx, cy
+  float th2;
+  int fixScale;
+  orb_sim3_opt_result_t* out;
+};
+
 // ----------------------------------------------------- newpoints_kernels.hip
 // KeyFrame::ComputeSceneMedianDepth over nProblems keyframe slots (by value)
 struct MedianDepthParams {

@@ -253,6 +253,11 @@ hipError_t orb_k_local_map(const LocalMapParams* params, hipStream_t s);
 int orb_k_sim3_max_stride(void);
 hipError_t orb_k_sim3_setup(const Sim3SetupParams* params, hipStream_t s);
 hipError_t orb_k_sim3_iterate(const Sim3IterParams* params, hipStream_t s);
+// ----------------------------------------------------- sim3opt_kernels.hip
+// largest kp_stride whose pair records fit one CU's LDS beside the term tiles
+int orb_k_sim3opt_max_stride(void);
+hipError_t orb_k_optimize_sim3(const Sim3OptParams* params, hipStream_t s);
+hipError_t orb_k_pinned_exp(int n, const double* x, double* y, hipStream_t s);
 // ---------------------------------------------------- newpoints_kernels.hip
 // largest kp_stride whose staged depth keys / statuses and points fit one CU's LDS
 int orb_k_median_depth_max_stride(void);

@@ -949,6 +949,27 @@ class ORBmatcher {
   }
   static int sim3_solver_max_stride() { return orb_sim3_solver_max_stride(); }
 
+  // Optimizer::OptimizeSim3 for n_problems (pKF1, pKF2, vpMatches1, g2oS12)
+  // problems in the solver's slot layout (orb_optimize_sim3_batch;
+  // src/Optimizer.cc:1130-1326).  d_match12 is updated in place; d_start may be
+  // the solver's d_result; d_kf1_slot, d_kf2_slot and d_active may be null.
+  void optimize_sim3_batch(int n_problems, const int32_t* d_kf1_slot, const int32_t* d_kf2_slot,
+                           const KeyPoint* d_kf_keys, const int32_t* d_kf_nkeys,
+                           const int32_t* d_kf_point_index, const orb_pose_t* d_kf_pose,
+                           int kp_stride, const orb_map_point_t* d_points, int32_t* d_match12,
+                           const int32_t* d_index2, const orb_sim3_result_t* d_start,
+                           const uint8_t* d_active, const std::vector<float>& invLevelSigma2,
+                           const orb_camera_t& cam1, const orb_camera_t& cam2, float th2,
+                           bool fix_scale, orb_sim3_opt_result_t* d_out, void* stream = nullptr) {
+    check(orb_optimize_sim3_batch(h_, n_problems, d_kf1_slot, d_kf2_slot, d_kf_keys, d_kf_nkeys,
+                                  d_kf_point_index, d_kf_pose, kp_stride, d_points, d_match12,
+                                  d_index2, d_start, d_active, invLevelSigma2.data(),
+                                  (int)invLevelSigma2.size(), &cam1, &cam2, th2, fix_scale ? 1 : 0,
+                                  d_out, stream),
+          "optimize_sim3_batch");
+  }
+  static int optimize_sim3_max_stride() { return orb_optimize_sim3_max_stride(); }
+
   // LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:245-537) as device
   // batches: KeyFrame::ComputeSceneMedianDepth(q) per keyframe slot
   // (orb_scene_median_depth_batch) and the neighbour loop's gate and body per
@@ -1207,8 +1228,62 @@ class Sim3Solver {
   orb_sim3_result_t last_{};
 };
 
+// The KeyFrame members Optimizer::OptimizeSim3 reads (src/Optimizer.cc:1130-1326):
+// mvKeysUn, GetMapPointMatches() as indices into the shared `points` (-1: null),
+// the pose, mK and mvInvLevelSigma2.
+struct Sim3KeyFrame {
+  const std::vector<KeyPoint>* mvKeysUn = nullptr;
+  const std::vector<int32_t>* mvpMapPoints = nullptr;  // read for pKF1 only
+  orb_pose_t pose{};
+  orb_camera_t mK{};
+};
+
+// g2o::Sim3 as ComputeSim3 builds it: gScm(toMatrix3d(R), toVector3d(t), s) on
+// the way in, the optimised estimate (result) on the way out.
+struct Sim3 {
+  float R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+  float t[3] = {0, 0, 0};
+  float s = 1.f;
+  orb_sim3_opt_result_t result{};  // q, t, s as doubles and the counts of the last call
+};
+
 class Optimizer {
  public:
+  // int Optimizer::OptimizeSim3(pKF1, pKF2, vpMatches1, g2oS12, th2, bFixScale):
+  // vpMatches1[i] is the point index of the match of keypoint i (negative:
+  // NULL) and comes back with -1 wherever the reference stores NULL; index2[i]
+  // is vpMatches1[i]->GetIndexInKeyFrame(pKF2).  g2oS12 is read as R, t, s and
+  // written back narrowed (with the doubles in g2oS12.result).  Both keyframes
+  // share mvInvLevelSigma2.  A malformed problem leaves result.status = -1 and
+  // returns 0.
+  static int OptimizeSim3(ORBmatcher& matcher, const Sim3KeyFrame* pKF1, const Sim3KeyFrame* pKF2,
+                          std::vector<int32_t>& vpMatches1, Sim3& g2oS12, const float th2,
+                          const bool bFixScale, const std::vector<int32_t>& index2,
+                          const std::vector<orb_map_point_t>& points,
+                          const std::vector<float>& mvInvLevelSigma2) {
+    const size_t n1 = pKF1->mvKeysUn->size();
+    assert(pKF1->mvpMapPoints->size() == n1 && vpMatches1.size() == n1 && index2.size() == n1);
+    orb_sim3_result_t start{};
+    start.has_sim3 = 1;
+    std::copy(g2oS12.R, g2oS12.R + 9, start.R);
+    std::copy(g2oS12.t, g2oS12.t + 3, start.t);
+    start.scale = g2oS12.s;
+    check(orb_optimize_sim3(matcher.handle(), pKF1->mvKeysUn->data(), (int)n1,
+                            pKF1->mvpMapPoints->data(), &pKF1->pose, pKF2->mvKeysUn->data(),
+                            (int)pKF2->mvKeysUn->size(), &pKF2->pose, points.data(),
+                            (int)points.size(), vpMatches1.data(), index2.data(), &start,
+                            mvInvLevelSigma2.data(), (int)mvInvLevelSigma2.size(), &pKF1->mK,
+                            &pKF2->mK, th2, bFixScale ? 1 : 0, &g2oS12.result),
+          "OptimizeSim3");
+    const orb_sim3_opt_result_t& r = g2oS12.result;
+    if (r.status == 0 && r.n_corr - r.n_bad >= 10) {  // g2oS12 = vSim3_recov->estimate() (:1323)
+      std::copy(r.R, r.R + 9, g2oS12.R);
+      std::copy(r.t_f, r.t_f + 3, g2oS12.t);
+      g2oS12.s = r.s_f;
+    }
+    return r.status == 0 ? r.n_inliers : 0;
+  }
+
   // int Optimizer::PoseOptimization(Frame* pFrame): returns nInitialCorrespondences - nBad
   // (0 with fewer than 3 correspondences, pose untouched) and writes mTcw and
   // mvbOutlier.  An octave outside mvInvLevelSigma2 leaves info.n_edges = -1.

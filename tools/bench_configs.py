@@ -55,6 +55,12 @@ results table:
       the rounds to completion with the finished ones discarded, one find();
       against the same calls one problem at a time (64 launches) + exact check
       of four problems against tests/sim3_ref.py
+  O1  LoopClosing::ComputeSim3's last stage, Optimizer::OptimizeSim3: 64 loop
+      candidates of about 150 correspondences (25 gross outliers each, a start
+      from a perturbed true Sim3, th2 10) per launch, device-resident, by
+      device events around each launch (median of 20): the time per launch,
+      problems/s, one problem alone + exact check against
+      tests/sim3opt_ref.py; also written to profiles/sim3opt_O1.json
   N1  LocalMapping::CreateNewMapPoints: 64 (current keyframe, neighbour) pairs
       of about 300 SearchForTriangulation matches each (384 keypoint slots,
       mixed stereo / monocular keypoints, 12 % gross outliers), device-resident,
@@ -76,7 +82,7 @@ results table:
       same pipeline without the RGB-D stages (monocular matcher), each new
       kernel alone by HIP events with its algorithmic bytes + exact check
 
-Usage: python tools/bench_configs.py [--configs C1,C2,C3,C5,F1,F3,P1,R1,T1,M1,B1,S1,N1,G1] [--steps K]
+Usage: python tools/bench_configs.py [--configs C1,C2,C3,C5,F1,F3,P1,R1,T1,M1,B1,S1,O1,N1,G1] [--steps K]
 The oracle (CPU restatement) is used only for the CPU rows and parity checks.
 """
 import argparse
@@ -1037,6 +1043,100 @@ def s1(args, orb, oracle, torch):
             "max_stride": orb.sim3_solver_max_stride(), "exact_vs_restatement": bool(exact)}
 
 
+def o1(args, orb, oracle, torch):
+    import sim3opt_cases as OC
+    from sim3opt_ref import OPT_RESULT_DTYPE, result_record
+    P = 64
+    rng = np.random.default_rng(41)
+    cases = [OC.make(5000 + i, int(rng.integers(135, 166)), 25, noise=0.7) for i in range(P)]
+    H = OC.HOSTS["std"]
+    S = max(max(c["n1"], c["n2"]) for c in cases)
+    keys = np.zeros((2 * P, S), orb.KEYPOINT_DTYPE)
+    nkeys = np.zeros(2 * P, np.int32)
+    pidx = np.full((2 * P, S), -1, np.int32)
+    pose = np.zeros(2 * P, orb.POSE_DTYPE)
+    match = np.full((P, S), -1, np.int32)
+    index2 = np.full((P, S), -1, np.int32)
+    start = np.zeros(P, orb.SIM3_RESULT_DTYPE)
+    pts, base = [], 0
+    for i, c in enumerate(cases):
+        for s_, k, o, n in ((2 * i, c["keys1"], c["octave1"], c["n1"]),
+                            (2 * i + 1, c["keys2"], c["octave2"], c["n2"])):
+            keys["x"][s_, :n], keys["y"][s_, :n], keys["octave"][s_, :n] = k[:, 0], k[:, 1], o
+            nkeys[s_] = n
+        pidx[2 * i, :c["n1"]] = np.where(c["point_index1"] >= 0, c["point_index1"] + base, -1)
+        match[i, :c["n1"]] = np.where(c["match12"] >= 0, c["match12"] + base, -1)
+        index2[i, :c["n1"]] = c["index2"]
+        pose["rcw"][2 * i], pose["tcw"][2 * i] = c["pose1"]
+        pose["rcw"][2 * i + 1], pose["tcw"][2 * i + 1] = c["pose2"]
+        start["has_sim3"][i] = 1
+        start["R"][i], start["t"][i], start["scale"][i] = c["start"]
+        p = np.zeros(len(c["pos"]), orb.MAP_POINT_DTYPE)
+        p["pos"] = c["pos"]
+        pts.append(p)
+        base += len(p)
+
+    def dev(a):
+        return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).cuda()
+    slots = np.arange(2 * P, dtype=np.int32)
+    d = dict(kf1=dev(slots[0::2]), kf2=dev(slots[1::2]), keys=dev(keys), nkeys=dev(nkeys),
+             pidx=dev(pidx), pose=dev(pose), points=dev(np.concatenate(pts)), match0=dev(match),
+             match=dev(match), index2=dev(index2), start=dev(start))
+    out = torch.zeros(P * OPT_RESULT_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
+    m = orb.ORBmatcher(0.75, True)
+    stream = torch.cuda.Stream()
+    sp = stream.cuda_stream
+
+    def run(n=P, p0=0):
+        m.optimize_sim3_batch(
+            n, d["kf1"].data_ptr() + 4 * p0, d["kf2"].data_ptr() + 4 * p0, d["keys"].data_ptr(),
+            d["nkeys"].data_ptr(), d["pidx"].data_ptr(), d["pose"].data_ptr(), S,
+            d["points"].data_ptr(), d["match"].data_ptr() + 4 * S * p0,
+            d["index2"].data_ptr() + 4 * S * p0, d["start"].data_ptr() + 132 * p0, H["levels"],
+            H["K1"], H["K2"], out.data_ptr() + OPT_RESULT_DTYPE.itemsize * p0,
+            th2=float(H["th2"]), fix_scale=False, stream=sp)
+
+    def events(fn, reps=20):
+        t = []
+        for _ in range(reps):
+            with torch.cuda.stream(stream):
+                d["match"].copy_(d["match0"])  # the call removes matches in place
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            fn()
+            e1.record(stream)
+            torch.cuda.synchronize()
+            t.append(e0.elapsed_time(e1))
+        t.sort()
+        return {"median": t[len(t) // 2], "min": t[0], "max": t[-1]}
+
+    for _ in range(3):
+        run()
+    t_batch = events(run)
+    t_one = events(lambda: run(1, 0))
+    t_serial = events(lambda: [run(1, p) for p in range(P)])
+    with torch.cuda.stream(stream):
+        d["match"].copy_(d["match0"])
+    run()
+    torch.cuda.synchronize()
+    rec = out.cpu().numpy().view(OPT_RESULT_DTYPE)
+    exact = True
+    for p in (0, 1, P // 2, P - 1):
+        exact &= rec[p].tobytes() == result_record(OC.run_ref(cases[p]))[0].tobytes()
+    r = {"config": "O1", "library": str(orb.LIB_PATH),
+         "workload": f"OptimizeSim3, {P} candidates x {int(rec['n_corr'].mean())} correspondences "
+                     f"on average ({int(rec['n_corr'].min())}-{int(rec['n_corr'].max())}), {S} "
+                     f"keypoint slots, 25 gross outliers each, th2 10, scale free",
+         "launch_ms": t_batch, "problems_per_s": P / (t_batch["median"] * 1e-3),
+         "one_problem_ms": t_one, "serial_ms": t_serial,
+         "serial_over_batch": t_serial["median"] / t_batch["median"],
+         "n_inliers_mean": float(rec["n_inliers"].mean()), "n_bad_mean": float(rec["n_bad"].mean()),
+         "max_stride": orb.optimize_sim3_max_stride(), "exact_vs_restatement": bool(exact)}
+    (ROOT / "profiles").mkdir(exist_ok=True)
+    (ROOT / "profiles" / "sim3opt_O1.json").write_text(json.dumps(r, indent=1) + "\n")
+    return r
+
+
 def n1(args, orb, oracle, torch):
     import newpoints_cases as NC
     from newpoints_ref import MAP_POINT_DTYPE, NEW_POINT_INFO_DTYPE
@@ -1290,6 +1390,8 @@ def main():
             r = b1(args, orb, oracle, torch)
         elif c == "S1":
             r = s1(args, orb, oracle, torch)
+        elif c == "O1":
+            r = o1(args, orb, oracle, torch)
         elif c == "N1":
             r = n1(args, orb, oracle, torch)
         elif c == "G1":
