@@ -1,7 +1,8 @@
 // pose_kernels.hip -- Optimizer::PoseOptimization (src/Optimizer.cc:243-477) on
 // the device: the motion-only optimisation of one SE3 vertex against one unary
 // edge per matched keypoint, with the g2o parts it reaches restated literally
-// (tests/poseopt_ref.py is the same text in numpy).
+// (tests/poseopt_ref.py is the same text in numpy); those it
+// shares with sim3opt_kernels.hip are in g2o_device.h.
 //
 //   k_pose_optimization   one 64-lane workgroup per problem, one launch per call:
 //     1. the problem's edges are compacted once, in ascending keypoint order,
@@ -17,9 +18,8 @@
 //        lanes each own one accumulator (the robust chi2, 6 of b, 21 of H) and
 //        add their row in edge order, +0.0 for the edges that are not active;
 //     4. the 6x6 pivoted LDLT, exp, the quaternion update and the
-//        Levenberg-Marquardt bookkeeping are the same doubles in every lane
-//        (the sums reach the lanes through LDS), with every branch condition
-//        read from lane 0, so the control flow is wave-uniform.
+//        Levenberg-Marquardt driver (g2o_device.h) are the same doubles in
+//        every lane: the sums reach the lanes through LDS.
 //   All four rounds and every trial run inside the kernel; the loops are
 //   bounded by 4 x 10 x 10 trials whatever the input (NaN included).
 //
@@ -27,6 +27,7 @@
 #include <hip/hip_runtime.h>
 
 #include "orb_device.h"
+#include "g2o_device.h"
 #include "orb_kernels.h"
 
 namespace {
@@ -52,134 +53,26 @@ struct PoState {
 };
 static_assert(sizeof(PoState) <= PO_LDS_STATE, "solver state fits its carve");
 
-struct PoEst {  // SE3Quat: _r (x, y, z, w), _t
-  double qx, qy, qz, qw, tx, ty, tz;
+struct PoEst : G2oQuat {  // SE3Quat: _r (x, y, z, w), _t
+  double tx, ty, tz;
 };
-
-__device__ __forceinline__ bool uni(bool c) {  // a condition every lane computed alike, as a scalar
-  return __builtin_amdgcn_readfirstlane((int)c) != 0;
-}
-
-// ---- Eigen closed forms (sums left to right)
-__device__ __forceinline__ void po_normalize_rotation(PoEst& e) {  // se3quat.h:280-285
-  if (uni(e.qw < 0)) {
-    e.qx = -e.qx;
-    e.qy = -e.qy;
-    e.qz = -e.qz;
-    e.qw = -e.qw;
-  }
-  const double n = sqrt(((e.qx * e.qx + e.qy * e.qy) + e.qz * e.qz) + e.qw * e.qw);
-  e.qx = e.qx / n;
-  e.qy = e.qy / n;
-  e.qz = e.qz / n;
-  e.qw = e.qw / n;
-}
-
-// Quaterniond(Matrix3d): m row-major
-__device__ __forceinline__ void po_quat_from_matrix(const double* m, PoEst& e) {
-  double t = (m[0] + m[4]) + m[8];
-  if (uni(t > 0.0)) {
-    t = sqrt(t + 1.0);
-    e.qw = 0.5 * t;
-    t = 0.5 / t;
-    e.qx = (m[7] - m[5]) * t;
-    e.qy = (m[2] - m[6]) * t;
-    e.qz = (m[3] - m[1]) * t;
-    return;
-  }
-  int i = 0;
-  double mii = m[0];
-  if (m[4] > mii) {
-    i = 1;
-    mii = m[4];
-  }
-  if (m[8] > mii) i = 2;
-  i = __builtin_amdgcn_readfirstlane(i);
-  if (i == 0) {  // j = 1, k = 2
-    t = sqrt(((m[0] - m[4]) - m[8]) + 1.0);
-    e.qx = 0.5 * t;
-    t = 0.5 / t;
-    e.qw = (m[7] - m[5]) * t;
-    e.qy = (m[3] + m[1]) * t;
-    e.qz = (m[6] + m[2]) * t;
-  } else if (i == 1) {  // j = 2, k = 0
-    t = sqrt(((m[4] - m[8]) - m[0]) + 1.0);
-    e.qy = 0.5 * t;
-    t = 0.5 / t;
-    e.qw = (m[2] - m[6]) * t;
-    e.qz = (m[7] + m[5]) * t;
-    e.qx = (m[1] + m[3]) * t;
-  } else {  // j = 0, k = 1
-    t = sqrt(((m[8] - m[0]) - m[4]) + 1.0);
-    e.qz = 0.5 * t;
-    t = 0.5 / t;
-    e.qw = (m[3] - m[1]) * t;
-    e.qx = (m[2] + m[6]) * t;
-    e.qy = (m[5] + m[7]) * t;
-  }
-}
-
-// Eigen q * v = v + w (2 q x v) + q x (2 q x v)
-__device__ __forceinline__ void po_rotate(const PoEst& e, double x, double y, double z,
-                                          double& rx, double& ry, double& rz) {
-  double ux = e.qy * z - e.qz * y, uy = e.qz * x - e.qx * z, uz = e.qx * y - e.qy * x;
-  ux = ux + ux;
-  uy = uy + uy;
-  uz = uz + uz;
-  rx = (x + e.qw * ux) + (e.qy * uz - e.qz * uy);
-  ry = (y + e.qw * uy) + (e.qz * ux - e.qx * uz);
-  rz = (z + e.qw * uz) + (e.qx * uy - e.qy * ux);
-}
-
-__device__ __forceinline__ void po_to_matrix(const PoEst& e, double* m) {
-  const double tx = 2.0 * e.qx, ty = 2.0 * e.qy, tz = 2.0 * e.qz;
-  const double twx = tx * e.qw, twy = ty * e.qw, twz = tz * e.qw;
-  const double txx = tx * e.qx, txy = ty * e.qx, txz = tz * e.qx;
-  const double tyy = ty * e.qy, tyz = tz * e.qy, tzz = tz * e.qz;
-  m[0] = 1.0 - (tyy + tzz);
-  m[1] = txy - twz;
-  m[2] = txz + twy;
-  m[3] = txy + twz;
-  m[4] = 1.0 - (txx + tzz);
-  m[5] = tyz - twx;
-  m[6] = txz - twy;
-  m[7] = tyz + twx;
-  m[8] = 1.0 - (txx + tyy);
-}
+static_assert(sizeof(PoEst) == 56, "PoEst is seven doubles");
 
 // SE3Quat::exp (se3quat.h:223-257)
 __device__ __forceinline__ PoEst po_exp(const double* u) {
-  const double o0 = u[0], o1 = u[1], o2 = u[2];
-  const double theta = sqrt((o0 * o0 + o1 * o1) + o2 * o2);
-  const double Om[9] = {0.0, -o2, o1, o2, 0.0, -o0, -o1, o0, 0.0};  // se3_ops.hpp:27-38
   const double eye[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0};
-  double Om2[9], R[9], V[9];
+  double theta, Om[9], Om2[9], R[9], V[9], s, c;
+  if (g2o_rodrigues(u, theta, Om, Om2, R, s, c)) {
 #pragma unroll
-  for (int i = 0; i < 3; ++i)
-#pragma unroll
-    for (int j = 0; j < 3; ++j)
-      Om2[i * 3 + j] =
-          (Om[i * 3] * Om[j] + Om[i * 3 + 1] * Om[3 + j]) + Om[i * 3 + 2] * Om[6 + j];
-  if (uni(theta < 0.00001)) {
-#pragma unroll
-    for (int i = 0; i < 9; ++i) {
-      R[i] = (eye[i] + Om[i]) + Om2[i];
-      V[i] = R[i];
-    }
+    for (int i = 0; i < 9; ++i) V[i] = R[i];
   } else {
-    double s, c;
-    pinned_sincos_d(theta, &s, &c);
-    const double a = s / theta, b = (1.0 - c) / (theta * theta);
-    const double d = (theta - s) / ((theta * theta) * theta);
+    const double b = (1.0 - c) / (theta * theta), d = (theta - s) / ((theta * theta) * theta);
 #pragma unroll
-    for (int i = 0; i < 9; ++i) {
-      R[i] = (eye[i] + a * Om[i]) + b * Om2[i];
-      V[i] = (eye[i] + b * Om[i]) + d * Om2[i];
-    }
+    for (int i = 0; i < 9; ++i) V[i] = (eye[i] + b * Om[i]) + d * Om2[i];
   }
   PoEst e;
-  po_quat_from_matrix(R, e);
-  po_normalize_rotation(e);
+  g2o_quat_from_matrix(R, e);
+  g2o_normalize_rotation(e);
   e.tx = (V[0] * u[3] + V[1] * u[4]) + V[2] * u[5];
   e.ty = (V[3] * u[3] + V[4] * u[4]) + V[5] * u[5];
   e.tz = (V[6] * u[3] + V[7] * u[4]) + V[8] * u[5];
@@ -190,118 +83,14 @@ __device__ __forceinline__ PoEst po_exp(const double* u) {
 __device__ __forceinline__ PoEst po_mul(const PoEst& a, const PoEst& b) {
   PoEst r;
   double rx, ry, rz;
-  po_rotate(a, b.tx, b.ty, b.tz, rx, ry, rz);
+  g2o_rotate(a, b.tx, b.ty, b.tz, rx, ry, rz);
   r.tx = a.tx + rx;
   r.ty = a.ty + ry;
   r.tz = a.tz + rz;
-  r.qx = ((a.qw * b.qx + a.qx * b.qw) + a.qy * b.qz) - a.qz * b.qy;
-  r.qy = ((a.qw * b.qy + a.qy * b.qw) + a.qz * b.qx) - a.qx * b.qz;
-  r.qz = ((a.qw * b.qz + a.qz * b.qw) + a.qx * b.qy) - a.qy * b.qx;
-  r.qw = ((a.qw * b.qw - a.qx * b.qx) - a.qy * b.qy) - a.qz * b.qz;
-  po_normalize_rotation(r);
+  g2o_quat_mul(a, b, r);
+  g2o_normalize_rotation(r);
   return r;
 }
-
-// LinearSolverDense::solve (linear_solver_dense.h:104-112) with Eigen's
-// unblocked LDLT on the lower triangle of H + lambda I.  H is S.acc[7..], b is
-// S.acc[1..6].  Every lane runs it on its own registers: the loops are unrolled
-// so that every index is static, and a data-dependent pivot row c is reached by
-// a wave-uniform branch per candidate.  Returns isPositive(); x keeps its
-// value when the factorisation reports a negative pivot.
-#define PO_SWAP(a, b)     \
-  do {                    \
-    const double t_ = a;  \
-    a = b;                \
-    b = t_;               \
-  } while (0)
-__device__ __forceinline__ bool po_ldlt_solve(const PoState& S, double lam, double* x) {
-  double M[6][6];
-#pragma unroll
-  for (int r = 0; r < 6; ++r)
-#pragma unroll
-    for (int c = 0; c <= r; ++c) M[r][c] = S.acc[7 + r * (r + 1) / 2 + c];
-#pragma unroll
-  for (int j = 0; j < 6; ++j) M[j][j] = M[j][j] + lam;  // setLambda (block_solver.hpp:564-589)
-  int tr[6];
-  bool positive = true;
-#pragma unroll
-  for (int k = 0; k < 6; ++k) {
-    int idx = k;
-    double best = fabs(M[k][k]);
-#pragma unroll
-    for (int i = k + 1; i < 6; ++i) {
-      const double a = fabs(M[i][i]);
-      if (a > best) {
-        best = a;
-        idx = i;
-      }
-    }
-    idx = __builtin_amdgcn_readfirstlane(idx);
-    tr[k] = idx;
-#pragma unroll
-    for (int c = k + 1; c < 6; ++c) {
-      if (idx == c) {
-#pragma unroll
-        for (int j = 0; j < k; ++j) PO_SWAP(M[k][j], M[c][j]);
-#pragma unroll
-        for (int r = c + 1; r < 6; ++r) PO_SWAP(M[r][k], M[r][c]);
-        PO_SWAP(M[k][k], M[c][c]);
-#pragma unroll
-        for (int i = k + 1; i < c; ++i) PO_SWAP(M[i][k], M[c][i]);
-      }
-    }
-    if (k > 0) {
-      double temp[6];
-#pragma unroll
-      for (int j = 0; j < k; ++j) temp[j] = M[j][j] * M[k][j];
-#pragma unroll
-      for (int i = k; i < 6; ++i) {
-        double s = M[i][0] * temp[0];
-#pragma unroll
-        for (int j = 1; j < k; ++j) s = s + M[i][j] * temp[j];
-        M[i][k] = M[i][k] - s;
-      }
-    }
-    const double akk = M[k][k];
-    if (uni(fabs(akk) > 0.0)) {
-#pragma unroll
-      for (int i = k + 1; i < 6; ++i) M[i][k] = M[i][k] / akk;
-    }
-    if (akk < 0.0) positive = false;
-  }
-  if (!uni(positive)) return false;
-  double y[6];
-#pragma unroll
-  for (int j = 0; j < 6; ++j) y[j] = S.acc[1 + j];  // b (its lanes add the negated terms)
-#pragma unroll
-  for (int k = 0; k < 6; ++k)
-#pragma unroll
-    for (int c = k + 1; c < 6; ++c)
-      if (tr[k] == c) PO_SWAP(y[k], y[c]);
-#pragma unroll
-  for (int i = 0; i < 6; ++i)
-#pragma unroll
-    for (int r = i + 1; r < 6; ++r) y[r] = y[r] - y[i] * M[r][i];
-  const double tol = 1.0 / 1.7976931348623157e308;
-#pragma unroll
-  for (int i = 0; i < 6; ++i) y[i] = fabs(M[i][i]) > tol ? y[i] / M[i][i] : 0.0;
-#pragma unroll
-  for (int i = 4; i >= 0; --i) {
-    double s = M[i + 1][i] * y[i + 1];
-#pragma unroll
-    for (int j = i + 2; j < 6; ++j) s = s + M[j][i] * y[j];
-    y[i] = y[i] - s;
-  }
-#pragma unroll
-  for (int k = 5; k >= 0; --k)
-#pragma unroll
-    for (int c = k + 1; c < 6; ++c)
-      if (tr[k] == c) PO_SWAP(y[k], y[c]);
-#pragma unroll
-  for (int j = 0; j < 6; ++j) x[j] = y[j];
-  return true;
-}
-#undef PO_SWAP
 
 struct PoCam {
   double fx, fy, cx, cy, bf;
@@ -313,7 +102,7 @@ struct PoCam {
 __device__ __forceinline__ double po_error(const PoEdge& r, bool stereo, const PoEst& est,
                                            const PoCam& cam, double& x, double& y, double& z,
                                            double& e0, double& e1, double& e2) {
-  po_rotate(est, (double)r.X[0], (double)r.X[1], (double)r.X[2], x, y, z);
+  g2o_rotate(est, (double)r.X[0], (double)r.X[1], (double)r.X[2], x, y, z);
   x = x + est.tx;  // SE3Quat::map (se3quat.h:217-220)
   y = y + est.ty;
   z = z + est.tz;
@@ -358,16 +147,8 @@ __device__ void po_pass(const PoEdge* recs, int E, const PoEst& est, const PoCam
         const bool stereo = r.meta & PO_STEREO;
         double x, y, z, e0, e1, e2;
         const double chi2 = po_error(r, stereo, est, cam, x, y, z, e0, e1, e2);
-        // RobustKernelHuber::robustify (robust_kernel_impl.cpp:78-91)
         double rho0 = chi2, rho1 = 1.0;
-        if (robust) {
-          const double delta = stereo ? deltaStereo : deltaMono, dsqr = delta * delta;
-          if (!(chi2 <= dsqr)) {
-            const double sq = sqrt(chi2);
-            rho0 = (2 * sq) * delta - dsqr;
-            rho1 = delta / sq;
-          }
-        }
+        if (robust) g2o_huber(chi2, stereo ? deltaStereo : deltaMono, rho0, rho1);
         tv[0] = rho0;
         if constexpr (FULL) {
           // linearizeOplus (.cpp:266-288, :335-364); row 2 only for stereo
@@ -529,85 +310,32 @@ __global__ __launch_bounds__(64) void k_pose_optimization(
     double R[9];
 #pragma unroll
     for (int i = 0; i < 9; ++i) R[i] = (double)pin.rcw[i];
-    po_quat_from_matrix(R, est0);
-    po_normalize_rotation(est0);
+    g2o_quat_from_matrix(R, est0);
+    g2o_normalize_rotation(est0);
     est0.tx = (double)pin.tcw[0];
     est0.ty = (double)pin.tcw[1];
     est0.tz = (double)pin.tcw[2];
   }
-  PoEst est = est0, last = est0;
+  PoEst est = est0, last = est0;  // last: where the edges' _error was last computed
   double x[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};  // BlockSolver::_x
-  bool robust = true;
+  bool robust = true, lastIsEst = true;
   int nBad = 0, lmIters = 0, rejected = 0;
+  auto full_pass = [&] {
+    ++lmIters;
+    po_pass<true>(recs, E, est, cam, robust, deltaMono, deltaStereo, tile, S);
+  };
+  auto trial_pass = [&](const double* step) {
+    last = po_mul(po_exp(step), est);  // oplusImpl (.h:73-76)
+    po_pass<false>(recs, E, last, cam, robust, deltaMono, deltaStereo, tile, S);
+  };
+  auto accept = [&] { est = last; lastIsEst = true; };
+  auto reject = [&] { ++rejected; lastIsEst = false; };
   for (int it = 0; it < 4; ++it) {
     est = est0;  // :397
     last = est0;
-    bool lastIsEst = true;
-    if (E - nBad > 0) {  // (optimize() returns at once without active vertices)
-      double lam = 0.0, ni = 2.0;
-      int nbadSteps = 0;
-      for (int i = 0; i < 10; ++i) {  // optimize(10): OptimizationAlgorithmLevenberg::solve
-        ++lmIters;
-        po_pass<true>(recs, E, est, cam, robust, deltaMono, deltaStereo, tile, S);
-        double cur = S.acc[0];
-        const double ini = cur;
-        double bv[6];
-#pragma unroll
-        for (int j = 0; j < 6; ++j) bv[j] = S.acc[1 + j];
-        if (i == 0) {  // computeLambdaInit (:166-180)
-          double md = 0.0;
-#pragma unroll
-          for (int j = 0; j < 6; ++j) {
-            const double a = fabs(S.acc[7 + j * (j + 1) / 2 + j]);
-            md = a < md ? md : a;  // std::max(fabs(h), maxDiagonal)
-          }
-          lam = 1e-5 * md;
-          ni = 2.0;
-          nbadSteps = 0;
-        }
-        double rho = 0.0;
-        int qmax = 0;
-        bool again;
-        do {
-          const bool ok2 = po_ldlt_solve(S, lam, x);
-          const PoEst trial = po_mul(po_exp(x), est);  // oplusImpl (.h:73-76)
-          po_pass<false>(recs, E, trial, cam, robust, deltaMono, deltaStereo, tile, S);
-          last = trial;
-          double tmp = S.acc[0];
-          __syncthreads();
-          if (!ok2) tmp = 1.7976931348623157e308;
-          double scale = 0.0;  // computeScale (:182-189)
-#pragma unroll
-          for (int j = 0; j < 6; ++j) scale = scale + x[j] * (lam * x[j] + bv[j]);
-          scale = scale + 1e-3;
-          rho = (cur - tmp) / scale;
-          if (uni(rho > 0 && fabs(tmp) <= 1.7976931348623157e308)) {  // g2o_isfinite
-            const double y = 2 * rho - 1;
-            double alpha = 1.0 - (y * y) * y;
-            alpha = (2.0 / 3.0) < alpha ? (2.0 / 3.0) : alpha;          // std::min(alpha, upper)
-            const double sf = (1.0 / 3.0) < alpha ? alpha : (1.0 / 3.0);  // std::max(lower, alpha)
-            lam = lam * sf;
-            ni = 2.0;
-            cur = tmp;
-            est = trial;
-            lastIsEst = true;
-          } else {
-            lam = lam * ni;
-            ni = ni * 2;
-            ++rejected;  // pop(): the vertex goes back, the edges keep their _error
-            lastIsEst = false;
-          }
-          ++qmax;
-          again = uni(rho < 0 && qmax < 10);
-        } while (again);
-        if (uni(qmax == 10 || rho == 0)) break;
-        if (uni((ini - cur) * 1e3 < ini))
-          ++nbadSteps;
-        else
-          nbadSteps = 0;
-        if (nbadSteps >= 3) break;
-      }
-    }
+    lastIsEst = true;
+    if (E - nBad > 0)  // (optimize() returns at once without active vertices)
+      g2o_lm_optimize<6>(S.acc, 10, x, full_pass, trial_pass, accept, reject);  // optimize(10)
     // ---- classification (:402-465): an active edge from its last computed
     // error, a level-1 edge recomputed at the final estimate (:411-414)
     nBad = 0;
@@ -639,7 +367,7 @@ __global__ __launch_bounds__(64) void k_pose_optimization(
     // Converter::toCvMat (src/Converter.cc:51-73), Frame::UpdatePoseMatrices
     // (src/Frame.cc:294-300; float products summed left to right, App. A)
     double R[9];
-    po_to_matrix(est, R);
+    g2o_to_matrix(est, R);
     orb_pose_t o;
 #pragma unroll
     for (int i = 0; i < 9; ++i) o.rcw[i] = (float)R[i];

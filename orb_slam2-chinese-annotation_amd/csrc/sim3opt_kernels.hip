@@ -3,7 +3,7 @@
 // correspondence (EdgeSim3ProjectXYZ, EdgeInverseSim3ProjectXYZ) whose other
 // vertex is fixed, with the g2o parts it reaches restated literally (DESIGN.md
 // §4.12; tests/sim3opt_ref.py is the same text in numpy).  The architecture is
-// k_pose_optimization's (§4.5):
+// k_pose_optimization's (§4.5), and what the two share is in g2o_device.h:
 //
 //   k_optimize_sim3   one 64-lane workgroup per problem, one launch per call:
 //     1. the kept pairs are compacted once, in ascending i1, by ballot prefix
@@ -21,8 +21,7 @@
 //     4. 36 lanes each own one accumulator and add their two rows in insertion
 //        order e12(i), e21(i), e12(i'), ..., +0.0 for a removed pair;
 //     5. the 7x7 pivoted LDLT, the Sim3 exponential, s * estimate and the
-//        Levenberg-Marquardt bookkeeping are the same doubles in every lane,
-//        with every branch condition read from lane 0.
+//        Levenberg-Marquardt driver are the same doubles in every lane.
 //   Both optimize() calls, every trial, both classifications and the gate run
 //   inside the kernel; the loops are bounded by (5 + 10) x 10 trials whatever
 //   the input (NaN included).
@@ -31,6 +30,7 @@
 #include <hip/hip_runtime.h>
 
 #include "orb_device.h"
+#include "g2o_device.h"
 #include "orb_kernels.h"
 
 namespace {
@@ -53,9 +53,10 @@ constexpr int SO_PITCH = ORB_WAVE + 1;  // doubles per term row: lane t's row st
 constexpr int SO_LDS_TILE = (SO_TERMS * SO_PITCH * 8 + 15) / 16 * 16;  // 18,720
 constexpr int SO_NEST = 15;  // the centre, then +delta and -delta along each of 7 axes
 
-struct SoEst {  // g2o::Sim3: r (x, y, z, w), t, s
-  double qx, qy, qz, qw, tx, ty, tz, s;
+struct SoEst : G2oQuat {  // g2o::Sim3: r (x, y, z, w), t, s
+  double tx, ty, tz, s;
 };
+static_assert(sizeof(SoEst) == 64, "SoEst is eight doubles");
 struct SoState {
   double acc[SO_TERMS];  // the sums of the last pass (acc[0] of the last pass of either kind)
   SoEst fwd[SO_NEST];    // the estimates an edge is evaluated at
@@ -64,110 +65,15 @@ struct SoState {
 constexpr int SO_LDS_STATE = (sizeof(SoState) + 15) / 16 * 16;  // 2,208
 constexpr size_t SO_LDS_FIXED = 2 * (size_t)SO_LDS_TILE + SO_LDS_STATE;
 
-__device__ __forceinline__ bool uni(bool c) {  // a condition every lane computed alike, as a scalar
-  return __builtin_amdgcn_readfirstlane((int)c) != 0;
-}
-
-// ---- Eigen closed forms (sums left to right), as pose_kernels.hip pins them
-// Quaterniond(Matrix3d): m row-major; never normalised here
-__device__ __forceinline__ void so_quat_from_matrix(const double* m, SoEst& e) {
-  double t = (m[0] + m[4]) + m[8];
-  if (uni(t > 0.0)) {
-    t = sqrt(t + 1.0);
-    e.qw = 0.5 * t;
-    t = 0.5 / t;
-    e.qx = (m[7] - m[5]) * t;
-    e.qy = (m[2] - m[6]) * t;
-    e.qz = (m[3] - m[1]) * t;
-    return;
-  }
-  int i = 0;
-  double mii = m[0];
-  if (m[4] > mii) {
-    i = 1;
-    mii = m[4];
-  }
-  if (m[8] > mii) i = 2;
-  i = __builtin_amdgcn_readfirstlane(i);
-  if (i == 0) {  // j = 1, k = 2
-    t = sqrt(((m[0] - m[4]) - m[8]) + 1.0);
-    e.qx = 0.5 * t;
-    t = 0.5 / t;
-    e.qw = (m[7] - m[5]) * t;
-    e.qy = (m[3] + m[1]) * t;
-    e.qz = (m[6] + m[2]) * t;
-  } else if (i == 1) {  // j = 2, k = 0
-    t = sqrt(((m[4] - m[8]) - m[0]) + 1.0);
-    e.qy = 0.5 * t;
-    t = 0.5 / t;
-    e.qw = (m[2] - m[6]) * t;
-    e.qz = (m[7] + m[5]) * t;
-    e.qx = (m[1] + m[3]) * t;
-  } else {  // j = 0, k = 1
-    t = sqrt(((m[8] - m[0]) - m[4]) + 1.0);
-    e.qz = 0.5 * t;
-    t = 0.5 / t;
-    e.qw = (m[3] - m[1]) * t;
-    e.qx = (m[2] + m[6]) * t;
-    e.qy = (m[5] + m[7]) * t;
-  }
-}
-
-// Eigen q * v = v + w (2 q x v) + q x (2 q x v)
-__device__ __forceinline__ void so_rotate(double qx, double qy, double qz, double qw, double x,
-                                          double y, double z, double& rx, double& ry, double& rz) {
-  double ux = qy * z - qz * y, uy = qz * x - qx * z, uz = qx * y - qy * x;
-  ux = ux + ux;
-  uy = uy + uy;
-  uz = uz + uz;
-  rx = (x + qw * ux) + (qy * uz - qz * uy);
-  ry = (y + qw * uy) + (qz * ux - qx * uz);
-  rz = (z + qw * uz) + (qx * uy - qy * ux);
-}
-
-__device__ __forceinline__ void so_to_matrix(const SoEst& e, double* m) {
-  const double tx = 2.0 * e.qx, ty = 2.0 * e.qy, tz = 2.0 * e.qz;
-  const double twx = tx * e.qw, twy = ty * e.qw, twz = tz * e.qw;
-  const double txx = tx * e.qx, txy = ty * e.qx, txz = tz * e.qx;
-  const double tyy = ty * e.qy, tyz = tz * e.qy, tzz = tz * e.qz;
-  m[0] = 1.0 - (tyy + tzz);
-  m[1] = txy - twz;
-  m[2] = txz + twy;
-  m[3] = txy + twz;
-  m[4] = 1.0 - (txx + tzz);
-  m[5] = tyz - twx;
-  m[6] = txz - twy;
-  m[7] = tyz + twx;
-  m[8] = 1.0 - (txx + tyy);
-}
-
 // Sim3(const Vector7d&) (sim3.h:70-142)
 __device__ __forceinline__ SoEst so_exp(const double* u) {
-  const double o0 = u[0], o1 = u[1], o2 = u[2], sigma = u[6];
-  const double theta = sqrt((o0 * o0 + o1 * o1) + o2 * o2);
-  const double Om[9] = {0.0, -o2, o1, o2, 0.0, -o0, -o1, o0, 0.0};  // skew (se3_ops.hpp:27-38)
+  const double sigma = u[6];
   const double eye[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0};
-  double Om2[9], R[9];
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-#pragma unroll
-    for (int j = 0; j < 3; ++j)
-      Om2[i * 3 + j] =
-          (Om[i * 3] * Om[j] + Om[i * 3 + 1] * Om[3 + j]) + Om[i * 3 + 2] * Om[6 + j];
+  double theta, Om[9], Om2[9], R[9], sn, cs;
   SoEst e;
   e.s = pinned_exp(sigma);
-  const double eps = 0.00001;
-  const bool smallS = uni(fabs(sigma) < eps), smallT = uni(theta < eps);
-  double sn = 0.0, cs = 0.0;
-  if (smallT) {
-#pragma unroll
-    for (int i = 0; i < 9; ++i) R[i] = (eye[i] + Om[i]) + Om2[i];
-  } else {
-    pinned_sincos_d(theta, &sn, &cs);
-    const double a = sn / theta, b = (1 - cs) / (theta * theta);
-#pragma unroll
-    for (int i = 0; i < 9; ++i) R[i] = (eye[i] + a * Om[i]) + b * Om2[i];
-  }
+  const bool smallS = uni(fabs(sigma) < 0.00001);
+  const bool smallT = g2o_rodrigues(u, theta, Om, Om2, R, sn, cs);
   double A, B, C;
   if (smallS) {
     C = 1;
@@ -193,7 +99,7 @@ __device__ __forceinline__ SoEst so_exp(const double* u) {
       B = (C - ((b - 1) * sigma + a * theta) / (c)) * 1. / (theta2);
     }
   }
-  so_quat_from_matrix(R, e);
+  g2o_quat_from_matrix(R, e);
   double W[9];
 #pragma unroll
   for (int i = 0; i < 9; ++i) W[i] = (A * Om[i] + B * Om2[i]) + C * eye[i];
@@ -206,12 +112,9 @@ __device__ __forceinline__ SoEst so_exp(const double* u) {
 // Sim3::operator* (sim3.h:266-272)
 __device__ __forceinline__ SoEst so_mul(const SoEst& a, const SoEst& b) {
   SoEst r;
-  r.qx = ((a.qw * b.qx + a.qx * b.qw) + a.qy * b.qz) - a.qz * b.qy;
-  r.qy = ((a.qw * b.qy + a.qy * b.qw) + a.qz * b.qx) - a.qx * b.qz;
-  r.qz = ((a.qw * b.qz + a.qz * b.qw) + a.qx * b.qy) - a.qy * b.qx;
-  r.qw = ((a.qw * b.qw - a.qx * b.qx) - a.qy * b.qy) - a.qz * b.qz;
+  g2o_quat_mul(a, b, r);
   double rx, ry, rz;
-  so_rotate(a.qx, a.qy, a.qz, a.qw, b.tx, b.ty, b.tz, rx, ry, rz);
+  g2o_rotate(a, b.tx, b.ty, b.tz, rx, ry, rz);
   r.tx = a.s * rx + a.tx;
   r.ty = a.s * ry + a.ty;
   r.tz = a.s * rz + a.tz;
@@ -227,7 +130,7 @@ __device__ __forceinline__ SoEst so_inverse(const SoEst& a) {
   r.qz = -a.qz;
   r.qw = a.qw;
   const double c = -1. / a.s;
-  so_rotate(r.qx, r.qy, r.qz, r.qw, c * a.tx, c * a.ty, c * a.tz, r.tx, r.ty, r.tz);
+  g2o_rotate(r, c * a.tx, c * a.ty, c * a.tz, r.tx, r.ty, r.tz);
   r.s = 1. / a.s;
   return r;
 }
@@ -237,7 +140,7 @@ __device__ __forceinline__ SoEst so_inverse(const SoEst& a) {
 __device__ __forceinline__ void so_error(const SoEst& e, const float* X, const float* obs,
                                          const double* K, double& e0, double& e1) {
   double x, y, z;
-  so_rotate(e.qx, e.qy, e.qz, e.qw, (double)X[0], (double)X[1], (double)X[2], x, y, z);
+  g2o_rotate(e, (double)X[0], (double)X[1], (double)X[2], x, y, z);
   x = e.s * x + e.tx;  // Sim3::map (sim3.h:144-146)
   y = e.s * y + e.ty;
   z = e.s * z + e.tz;
@@ -255,14 +158,8 @@ __device__ __forceinline__ void so_edge_terms(const SoEst* ests, const float* X,
   so_error(ests[0], X, obs, K, e0, e1);
   const double s = (double)inv;
   const double chi2 = e0 * (s * e0) + e1 * (s * e1);  // BaseEdge::chi2
-  // RobustKernelHuber::robustify (robust_kernel_impl.cpp:78-91)
-  double rho0 = chi2, rho1 = 1.0;
-  const double dsqr = delta * delta;
-  if (!(chi2 <= dsqr)) {
-    const double sq = sqrt(chi2);
-    rho0 = (2 * sq) * delta - dsqr;
-    rho1 = delta / sq;
-  }
+  double rho0, rho1;
+  g2o_huber(chi2, delta, rho0, rho1);
   tile[col] = rho0;
   if constexpr (FULL) {
     // linearizeOplus (base_binary_edge.hpp:131-200), the free vertex j alone
@@ -374,106 +271,6 @@ __device__ void so_pass(const SoRec* recs, int E, const double* K1, const double
   __syncthreads();
 }
 
-// LinearSolverDense::solve (linear_solver_dense.h:104-112) with Eigen's
-// unblocked LDLT on the lower triangle of H + lambda I, n = 7: the rules of
-// pose_kernels.hip's po_ldlt_solve.  H is S.acc[8..], b is S.acc[1..7].
-// Returns isPositive(); x keeps its value when a pivot is negative.
-#define SO_SWAP(a, b)     \
-  do {                    \
-    const double t_ = a;  \
-    a = b;                \
-    b = t_;               \
-  } while (0)
-__device__ __forceinline__ bool so_ldlt_solve(const SoState& S, double lam, double* x) {
-  constexpr int N = 7;
-  double M[N][N];
-#pragma unroll
-  for (int r = 0; r < N; ++r)
-#pragma unroll
-    for (int c = 0; c <= r; ++c) M[r][c] = S.acc[8 + r * (r + 1) / 2 + c];
-#pragma unroll
-  for (int j = 0; j < N; ++j) M[j][j] = M[j][j] + lam;  // setLambda (block_solver.hpp:564-589)
-  int tr[N];
-  bool positive = true;
-#pragma unroll
-  for (int k = 0; k < N; ++k) {
-    int idx = k;
-    double best = fabs(M[k][k]);
-#pragma unroll
-    for (int i = k + 1; i < N; ++i) {
-      const double a = fabs(M[i][i]);
-      if (a > best) {
-        best = a;
-        idx = i;
-      }
-    }
-    idx = __builtin_amdgcn_readfirstlane(idx);
-    tr[k] = idx;
-#pragma unroll
-    for (int c = k + 1; c < N; ++c) {
-      if (idx == c) {
-#pragma unroll
-        for (int j = 0; j < k; ++j) SO_SWAP(M[k][j], M[c][j]);
-#pragma unroll
-        for (int r = c + 1; r < N; ++r) SO_SWAP(M[r][k], M[r][c]);
-        SO_SWAP(M[k][k], M[c][c]);
-#pragma unroll
-        for (int i = k + 1; i < c; ++i) SO_SWAP(M[i][k], M[c][i]);
-      }
-    }
-    if (k > 0) {
-      double temp[N];
-#pragma unroll
-      for (int j = 0; j < k; ++j) temp[j] = M[j][j] * M[k][j];
-#pragma unroll
-      for (int i = k; i < N; ++i) {
-        double s = M[i][0] * temp[0];
-#pragma unroll
-        for (int j = 1; j < k; ++j) s = s + M[i][j] * temp[j];
-        M[i][k] = M[i][k] - s;
-      }
-    }
-    const double akk = M[k][k];
-    if (uni(fabs(akk) > 0.0)) {
-#pragma unroll
-      for (int i = k + 1; i < N; ++i) M[i][k] = M[i][k] / akk;
-    }
-    if (akk < 0.0) positive = false;
-  }
-  if (!uni(positive)) return false;
-  double y[N];
-#pragma unroll
-  for (int j = 0; j < N; ++j) y[j] = S.acc[1 + j];
-#pragma unroll
-  for (int k = 0; k < N; ++k)
-#pragma unroll
-    for (int c = k + 1; c < N; ++c)
-      if (tr[k] == c) SO_SWAP(y[k], y[c]);
-#pragma unroll
-  for (int i = 0; i < N; ++i)
-#pragma unroll
-    for (int r = i + 1; r < N; ++r) y[r] = y[r] - y[i] * M[r][i];
-  const double tol = 1.0 / 1.7976931348623157e308;
-#pragma unroll
-  for (int i = 0; i < N; ++i) y[i] = fabs(M[i][i]) > tol ? y[i] / M[i][i] : 0.0;
-#pragma unroll
-  for (int i = N - 2; i >= 0; --i) {
-    double s = M[i + 1][i] * y[i + 1];
-#pragma unroll
-    for (int j = i + 2; j < N; ++j) s = s + M[j][i] * y[j];
-    y[i] = y[i] - s;
-  }
-#pragma unroll
-  for (int k = N - 1; k >= 0; --k)
-#pragma unroll
-    for (int c = k + 1; c < N; ++c)
-      if (tr[k] == c) SO_SWAP(y[k], y[c]);
-#pragma unroll
-  for (int j = 0; j < N; ++j) x[j] = y[j];
-  return true;
-}
-#undef SO_SWAP
-
 __device__ __forceinline__ void so_write_result(orb_sim3_opt_result_t* out, int status, int nCorr,
                                                 int nBad, int nIn, const SoEst& e) {
   orb_sim3_opt_result_t r;
@@ -490,7 +287,7 @@ __device__ __forceinline__ void so_write_result(orb_sim3_opt_result_t* out, int 
   r.t[2] = e.tz;
   r.s = e.s;
   double R[9];
-  so_to_matrix(e, R);
+  g2o_to_matrix(e, R);
 #pragma unroll
   for (int i = 0; i < 9; ++i) r.R[i] = (float)R[i];
   r.t_f[0] = (float)e.tx;
@@ -579,7 +376,7 @@ __global__ __launch_bounds__(64) void k_optimize_sim3(const Sim3OptParams P) {
     double R[9];
 #pragma unroll
     for (int i = 0; i < 9; ++i) R[i] = (double)st->R[i];
-    so_quat_from_matrix(R, est);
+    g2o_quat_from_matrix(R, est);
     est.tx = (double)st->t[0];
     est.ty = (double)st->t[1];
     est.tz = (double)st->t[2];
@@ -601,75 +398,25 @@ __global__ __launch_bounds__(64) void k_optimize_sim3(const Sim3OptParams P) {
   const double delta = (double)(float)sqrt((double)P.th2);  // const float deltaHuber = sqrt(th2) (:1179)
   const bool fixScale = P.fixScale != 0;
 
-  SoEst last = est;
+  SoEst last = est;  // where the edges' _error was last computed
   double x[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};  // BlockSolver::_x
+  auto full_pass = [&] {
+    so_setup<true>(est, fixScale, S);
+    so_pass<true>(recs, E, K1, K2, delta, tile12, tile21, S);
+  };
+  auto trial_pass = [&](double* step) {
+    if (fixScale) step[6] = 0;  // oplusImpl writes into the solver's array (pin O6)
+    last = so_mul(so_exp(step), est);
+    so_setup<false>(last, fixScale, S);
+    so_pass<false>(recs, E, K1, K2, delta, tile12, tile21, S);
+  };
+  auto accept = [&] { est = last; };
+  auto reject = [] {};
   int nBad = 0, nIn = 0;
   for (int round = 0; round < 2; ++round) {
     const int iters = round == 0 ? 5 : (nBad > 0 ? 10 : 5);  // :1266, :1289-1301
-    if (E - nBad > 0) {  // (optimize() returns at once without active vertices)
-      double lam = 0.0, ni = 2.0;
-      int nbadSteps = 0;
-      for (int i = 0; i < iters; ++i) {  // OptimizationAlgorithmLevenberg::solve
-        so_setup<true>(est, fixScale, S);
-        so_pass<true>(recs, E, K1, K2, delta, tile12, tile21, S);
-        double cur = S.acc[0];
-        const double ini = cur;
-        double bv[7];
-#pragma unroll
-        for (int j = 0; j < 7; ++j) bv[j] = S.acc[1 + j];
-        if (i == 0) {  // computeLambdaInit (:166-180)
-          double md = 0.0;
-#pragma unroll
-          for (int j = 0; j < 7; ++j) {
-            const double a = fabs(S.acc[8 + j * (j + 1) / 2 + j]);
-            md = a < md ? md : a;  // std::max(fabs(h), maxDiagonal)
-          }
-          lam = 1e-5 * md;
-          ni = 2.0;
-          nbadSteps = 0;
-        }
-        double rho = 0.0;
-        int qmax = 0;
-        bool again;
-        do {
-          const bool ok2 = so_ldlt_solve(S, lam, x);
-          if (fixScale) x[6] = 0;  // oplusImpl writes into the solver's array (pin O6)
-          const SoEst trial = so_mul(so_exp(x), est);
-          so_setup<false>(trial, fixScale, S);
-          so_pass<false>(recs, E, K1, K2, delta, tile12, tile21, S);
-          last = trial;
-          double tmp = S.acc[0];
-          __syncthreads();
-          if (!ok2) tmp = 1.7976931348623157e308;
-          double scale = 0.0;  // computeScale (:182-189)
-#pragma unroll
-          for (int j = 0; j < 7; ++j) scale = scale + x[j] * (lam * x[j] + bv[j]);
-          scale = scale + 1e-3;
-          rho = (cur - tmp) / scale;
-          if (uni(rho > 0 && fabs(tmp) <= 1.7976931348623157e308)) {  // g2o_isfinite
-            const double y = 2 * rho - 1;
-            double alpha = 1.0 - (y * y) * y;
-            alpha = (2.0 / 3.0) < alpha ? (2.0 / 3.0) : alpha;          // std::min(alpha, upper)
-            const double sf = (1.0 / 3.0) < alpha ? alpha : (1.0 / 3.0);  // std::max(lower, alpha)
-            lam = lam * sf;
-            ni = 2.0;
-            cur = tmp;
-            est = trial;
-          } else {
-            lam = lam * ni;
-            ni = ni * 2;  // pop(): the vertex goes back, the edges keep their _error
-          }
-          ++qmax;
-          again = uni(rho < 0 && qmax < 10);
-        } while (again);
-        if (uni(qmax == 10 || rho == 0)) break;
-        if (uni((ini - cur) * 1e3 < ini))
-          ++nbadSteps;
-        else
-          nbadSteps = 0;
-        if (nbadSteps >= 3) break;
-      }
-    }
+    if (E - nBad > 0)  // (optimize() returns at once without active vertices)
+      g2o_lm_optimize<7>(S.acc, iters, x, full_pass, trial_pass, accept, reject);
     // ---- the check (:1268-1287, :1303-1319): every remaining pair from the
     // errors of the last trial
     so_setup<false>(last, fixScale, S);

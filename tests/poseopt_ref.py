@@ -232,14 +232,16 @@ def pose_from_se3quat(est):
 # ------------------------------------------------------------ LDLT<MatrixXd>
 def ldlt_solve(H, b, x_prev, pivots=None, trace=None, variants=()):
     """LinearSolverDense::solve (linear_solver_dense.h:104-112) on the lower
-    triangle of the 6x6 H: returns (ok, x); x = x_prev when !isPositive().
-    trace["pivots"] collects the (k, idx) pairs, trace["pivot_sequences"] the
-    whole transposition lists, trace["pivot_ties"] counts the
-    steps whose largest |diagonal| is held by more than one remaining entry.
+    triangle of the n x n H, n = len(b) (6 here, 7 for tests/sim3opt_ref.py):
+    returns (ok, x); x = x_prev when !isPositive().
+    trace["pivots"] collects the (k, idx) pairs, trace["pivot_sequences"] (when
+    the trace has that key) the whole transposition lists, trace["pivot_ties"]
+    counts the steps whose largest |diagonal| is held by more than one
+    remaining entry.
     variants (NOT the reference): "tie_last" takes the last of equal
     magnitudes, "no_pivot" never swaps, "half_swap_<k><idx>" leaves the two
     diagonal entries where they were in the swap of that one (k, idx)."""
-    n = 6
+    n = len(b)
     m = [list(r) for r in H]
     tr = [0] * n
     positive = True
@@ -279,7 +281,7 @@ def ldlt_solve(H, b, x_prev, pivots=None, trace=None, variants=()):
             positive = False
     if pivots is not None:
         pivots[:] = tr
-    if trace is not None:
+    if trace is not None and "pivot_sequences" in trace:
         trace["pivot_sequences"].add(tuple(tr))
     if not positive:
         return False, list(x_prev)

@@ -51,8 +51,8 @@ import math
 
 import numpy as np
 
-from poseopt_ref import (DBL_MAX, _div, _mat3mul, _sqrt, huber, pinned_sincos_d, quat_from_matrix,
-                         quat_mul, quat_rotate, quat_to_matrix)
+from poseopt_ref import (DBL_MAX, _div, _mat3mul, _sqrt, huber, ldlt_solve, pinned_sincos_d,
+                         quat_from_matrix, quat_mul, quat_rotate, quat_to_matrix)
 from sim3_ref import _bits, _from_bits
 
 f32, f64 = np.float32, np.float64
@@ -226,65 +226,6 @@ def edge_error(est, X, obs, K):
 def _chi2(e0, e1, s):
     with np.errstate(all="ignore"):
         return e0 * (s * e0) + e1 * (s * e1)
-
-
-# ------------------------------------------------------------ LDLT<MatrixXd>
-def ldlt_solve_n(H, b, x_prev, trace=None, variants=()):
-    """poseopt_ref.ldlt_solve's rules on the lower triangle of an n x n H."""
-    n = len(b)
-    m = [list(r) for r in H]
-    tr = [0] * n
-    positive = True
-    for k in range(n):
-        idx, best = k, abs(m[k][k])
-        for i in range(k + 1, n):
-            if abs(m[i][i]) > best or ("tie_last" in variants and abs(m[i][i]) == best):
-                idx, best = i, abs(m[i][i])
-        tr[k] = idx
-        if trace is not None:
-            trace["pivots"].add((k, idx))
-            if [abs(m[i][i]) for i in range(k, n)].count(best) > 1:
-                trace["pivot_ties"] += 1
-        if idx != k:
-            for j in range(k):
-                m[k][j], m[idx][j] = m[idx][j], m[k][j]
-            for r in range(idx + 1, n):
-                m[r][k], m[r][idx] = m[r][idx], m[r][k]
-            m[k][k], m[idx][idx] = m[idx][idx], m[k][k]
-            for i in range(k + 1, idx):
-                m[i][k], m[idx][i] = m[idx][i], m[i][k]
-        if k > 0:
-            temp = [m[j][j] * m[k][j] for j in range(k)]
-            for i in range(k, n):
-                s = m[i][0] * temp[0]
-                for j in range(1, k):
-                    s = s + m[i][j] * temp[j]
-                m[i][k] = m[i][k] - s
-        akk = m[k][k]
-        if abs(akk) > 0.0:
-            for i in range(k + 1, n):
-                m[i][k] = _div(m[i][k], akk)
-        if akk < 0.0:
-            positive = False
-    if not positive:
-        return False, list(x_prev)
-    y = list(b)
-    for k in range(n):
-        y[k], y[tr[k]] = y[tr[k]], y[k]
-    for i in range(n):
-        for r in range(i + 1, n):
-            y[r] = y[r] - y[i] * m[r][i]
-    tol = 1.0 / DBL_MAX
-    for i in range(n):
-        y[i] = _div(y[i], m[i][i]) if abs(m[i][i]) > tol else 0.0
-    for i in range(n - 2, -1, -1):
-        s = m[i + 1][i] * y[i + 1]
-        for j in range(i + 2, n):
-            s = s + m[j][i] * y[j]
-        y[i] = y[i] - s
-    for k in range(n - 1, -1, -1):
-        y[k], y[tr[k]] = y[tr[k]], y[k]
-    return True, y
 
 
 def _seq(a12, a21, act, e21_first=False):
@@ -476,7 +417,7 @@ def optimize_sim3(keys1_xy, octave1, point_index1, pose1, keys2_xy, octave2, pos
                     Hl = [list(r) for r in H]
                     for j in range(7):
                         Hl[j][j] = H[j][j] + lam
-                    ok2, x = ldlt_solve_n(Hl, b, x, trace, variants)
+                    ok2, x = ldlt_solve(Hl, b, x, None, trace, variants)
                     if not ok2:
                         trace["not_positive"] += 1
                     oplus(est, x)  # pin O6: the solver's array

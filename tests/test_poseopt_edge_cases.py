@@ -74,7 +74,7 @@ def test_directed_census_table():
 
 # What the 45 seeded problems of poseopt_cases.SHARED reach: the reason the
 # directed cases exist.  Two pivot sequences, which differ in the last swap: 2 of
-# the 15 swap branches of po_ldlt_solve, never the no-swap path at k = 0; the
+# the 15 swap branches of g2o_ldlt_solve, never the no-swap path at k = 0; the
 # trace branch of Quaterniond(Matrix3d) only, no sign flip, quadrant 0 only.
 NATURAL = dict(pivot_sequences=[(1, 1, 2, 3, 4, 5), (1, 1, 2, 3, 5, 5)],
                pivots=[(0, 1), (1, 1), (2, 2), (3, 3), (4, 4), (4, 5), (5, 5)],

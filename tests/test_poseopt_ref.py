@@ -110,35 +110,42 @@ def test_pinned_sincos_matches_libm():
     assert all(math.isnan(v) for v in ref.pinned_sincos_d(math.inf))
 
 
-def test_ldlt_against_numpy_solve():
+@pytest.mark.parametrize("n", [6, 7])
+def test_ldlt_against_numpy_solve(n):
     rng = np.random.default_rng(7)
     for _ in range(20):
-        A = rng.normal(0, 1, (6, 9))
-        H = A @ A.T + 0.1 * np.eye(6)      # (test data only: the restatement never uses @)
-        b = rng.normal(0, 1, 6)
-        lower = np.tril(H) + np.triu(np.full((6, 6), np.nan), 1)   # the upper triangle is never read
-        ok, x = ref.ldlt_solve(lower.tolist(), b.tolist(), [9.0] * 6)
+        A = rng.normal(0, 1, (n, 9))
+        H = A @ A.T + 0.1 * np.eye(n)      # (test data only: the restatement never uses @)
+        b = rng.normal(0, 1, n)
+        lower = np.tril(H) + np.triu(np.full((n, n), np.nan), 1)   # the upper triangle is never read
+        ok, x = ref.ldlt_solve(lower.tolist(), b.tolist(), [9.0] * n)
         assert ok
         want = np.linalg.solve(H, b)
         assert np.abs(np.array(x) - want).max() <= 1e-10 * max(1.0, np.abs(want).max())
 
 
-def test_ldlt_pivot_order_and_sign():
+@pytest.mark.parametrize("d, want_piv, want_x", [
     # diagonal 3 1 6 2 5 4: the pivots are taken in the order 6 5 4 3 2 1
-    d = [3.0, 1.0, 6.0, 2.0, 5.0, 4.0]
-    H = [[d[i] if i == j else 0.0 for j in range(6)] for i in range(6)]
-    piv = [0] * 6
-    ok, x = ref.ldlt_solve(H, [6.0, 5.0, 4.0, 3.0, 2.0, 1.0], [0.0] * 6, piv)
-    assert ok and piv == [2, 4, 5, 5, 5, 5]
-    assert x == [2.0, 5.0, 4.0 / 6.0, 1.5, 0.4, 0.25]
+    ([3.0, 1.0, 6.0, 2.0, 5.0, 4.0], [2, 4, 5, 5, 5, 5], [2.0, 5.0, 4.0 / 6.0, 1.5, 0.4, 0.25]),
+    # diagonal 3 1 6 2 5 4 7: in the order 7 6 5 4 3 2 1
+    ([3.0, 1.0, 6.0, 2.0, 5.0, 4.0, 7.0], [6, 2, 4, 5, 6, 5, 6],
+     [7.0 / 3.0, 6.0, 5.0 / 6.0, 2.0, 0.6, 0.5, 1.0 / 7.0]),
+], ids=["6", "7"])
+def test_ldlt_pivot_order_and_sign(d, want_piv, want_x):
+    n = len(d)
+    H = [[d[i] if i == j else 0.0 for j in range(n)] for i in range(n)]
+    piv = [0] * n
+    ok, x = ref.ldlt_solve(H, [float(n - i) for i in range(n)], [0.0] * n, piv)
+    assert ok and piv == want_piv
+    assert x == want_x
     # equal magnitudes: the first one wins
-    H2 = [[2.0 if i == j else 0.0 for j in range(6)] for i in range(6)]
-    ref.ldlt_solve(H2, [1.0] * 6, [0.0] * 6, piv)
-    assert piv == [0, 1, 2, 3, 4, 5]
+    H2 = [[2.0 if i == j else 0.0 for j in range(n)] for i in range(n)]
+    ref.ldlt_solve(H2, [1.0] * n, [0.0] * n, piv)
+    assert piv == list(range(n))
     # a negative pivot: not positive, x keeps its previous value
     H[1][1] = -1.0
-    ok, x = ref.ldlt_solve(H, [1.0] * 6, [7.0] * 6)
-    assert not ok and x == [7.0] * 6
+    ok, x = ref.ldlt_solve(H, [1.0] * n, [7.0] * n)
+    assert not ok and x == [7.0] * n
 
 
 def test_quaternion_matrix_round_trip():
