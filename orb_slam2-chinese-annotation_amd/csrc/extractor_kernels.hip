@@ -1101,10 +1101,11 @@ __global__ __launch_bounds__(64 * FC_WAVES) __attribute__((amdgpu_waves_per_eu(F
 void k_fast_cells(
     const uint8_t* __restrict__ img0, long long img0Pitch, int img0Stride,
     const uint8_t* __restrict__ arena, long long arenaPitch, OrbPlanDesc plan,
-    const OrbCellDesc* __restrict__ cells, uint32_t* __restrict__ cellKeys,
-    int32_t* __restrict__ cellCount, int tileElems, int cellBeg, int cellEnd,
-    int32_t* __restrict__ errFlag) {
+    const OrbCellDesc* __restrict__ cells, const OrbCellClass* __restrict__ classes,
+    uint32_t* __restrict__ cellKeys, int32_t* __restrict__ cellCount, int tileElems, int cellBeg,
+    int cellEnd, int32_t* __restrict__ errFlag) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  static_assert(FC_CONST_PITCH == ORB_FC_CONST_PITCH, "the class table's mP48 is this pitch's");
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   int bx, img;
@@ -1122,21 +1123,37 @@ void k_fast_cells(
   // ---- staging: lane r loads ROI row r, bytes [x0 - LPAD, x0 - LPAD + P)
   // of level row y0 + r, as four 16-byte loads from the 4-aligned byte at or
   // below its start (any caller stride), realigned in registers
+  //
+  // A cell's descriptor is read as three dwords (12-byte entries of a 4-aligned
+  // table, a wave-uniform index: scalar loads): level | y0 << 16, y1 | x0 << 16,
+  // x1 | class << 16; every field is non-negative.  The level's buffer resource
+  // and pitch stay in SGPRs from cell to cell and are rebuilt, from the class
+  // entry, only where the next cell is on another level.
+  const uint32_t* cellW = reinterpret_cast<const uint32_t*>(cells);
   uint32_t raw[16], rsh = 0;
-  auto issue = [&](const OrbCellDesc& q) {
-    const int ql = q.level, qR = q.y1 - q.y0;
-    const uint8_t* lvl;
-    int pitch;
-    if (ql == 0) {
-      lvl = img0 + (long long)img * img0Pitch;
-      pitch = img0Stride;
-    } else {
-      lvl = arena + (long long)img * arenaPitch + plan.lv[ql].arenaOff;
-      pitch = plan.lv[ql].pitch;
+  ImgRsrc im = {};
+  int lvPitch = 0, lvCur = -1;
+  auto issue = [&](uint32_t w0, uint32_t w1, uint32_t w2) {
+    const int ql = (int)(w0 & 0xFFFFu), qy0 = (int)(w0 >> 16), qy1 = (int)(w1 & 0xFFFFu),
+              qx0 = (int)(w1 >> 16);
+    if (ql != lvCur) {
+      const OrbCellClass& qc = classes[w2 >> 16];
+      const uint8_t* lvl;
+      if (ql == 0) {
+        lvl = img0 + (long long)img * img0Pitch;
+        lvPitch = img0Stride;
+      } else {
+        lvl = arena + (long long)img * arenaPitch +
+              (long long)(((unsigned long long)qc.arenaHi << 32) | qc.arenaLo);
+        lvPitch = qc.pitch;
+      }
+      im = img_rsrc(lvl, (uint32_t)(qc.h1 * lvPitch + qc.w));
+      lvCur = ql;
     }
-    const ImgRsrc im = img_rsrc(lvl, (uint32_t)((plan.lv[ql].h - 1) * pitch + plan.lv[ql].w));
-    const int r = min(lane, max(qR - 1, 0));
-    const uint32_t o = (uint32_t)((q.y0 + r) * pitch + q.x0 - FAST_LPAD) + im.sh;
+    const int r = min(lane, max(qy1 - qy0 - 1, 0));
+    // row x pitch: a 24-bit multiply (rows < 2^12; pitch < 2^24, host-checked)
+    const uint32_t o = __umul24((uint32_t)(qy0 + r), (uint32_t)lvPitch) +
+                       ((uint32_t)(qx0 - FAST_LPAD) + im.sh);
     rsh = o & 3u;
     const uint32_t a0 = o & ~3u;
 #pragma unroll
@@ -1150,17 +1167,34 @@ void k_fast_cells(
   };
   int ci = cell_of(0);
   if (ci >= cellEnd) return;
-  OrbCellDesc ncd = cells[ci];
-  issue(ncd);
+  uint32_t nw0 = cellW[3 * ci], nw1 = cellW[3 * ci + 1], nw2 = cellW[3 * ci + 2];
+  issue(nw0, nw1, nw2);
+  // the image's first key slot and count (slot = img * ncells + cell; a cell's
+  // keys at slot * keyCap, ncells * keyCap < 2^31 host-checked)
+  uint32_t* const imgKeys = cellKeys + (long long)img * plan.ncells * plan.keyCap;
+  int32_t* const imgCount = cellCount + (long long)img * plan.ncells;
+  const int ti = min(max(plan.iniTh, 0), 255), tm = min(max(plan.minTh, 0), 255);
   for (int jc = 0; jc < FC_CPW && ci < cellEnd; ++jc) {
-  const OrbCellDesc cd = ncd;
-  const int R = cd.y1 - cd.y0, C = cd.x1 - cd.x0;
-  const long long slot = (long long)img * plan.ncells + ci;
-  const bool tiny = R < 7 || C < 7;
-  const int P = PT ? PT : fc_pitch(C);
+  // ---- the cell's class (orb_plan.h): what depends on (level, rows, cols)
+  // only, one scalar read of the planner's entry instead of arithmetic per cell
+  const uint32_t cw0 = nw0, cw1 = nw1;
+  const OrbCellClass& kc = classes[nw2 >> 16];
+  const int R = kc.R;
+  const bool tiny = kc.tiny != 0;
+  const int P = PT ? PT : kc.P;
+  const int iw = kc.iw, ih = kc.ih, nK = kc.nK, lastMask = kc.lastMask, nG = kc.nG, kInc = kc.kInc;
+  const int dOff = PT ? kc.dOff48 : kc.dOff, wrapOff = PT ? kc.wrapOff48 : kc.wrapOff;
+  const uint32_t mP = PT ? kc.mP48 : kc.mP, mW = kc.mW;
+  // the lane's first pixel group (group k0 of interior row rr0) and its tile
+  // byte: lane / nK by the class's multiply-shift (exact, host-checked)
+  const int rr0 = (int)(__umul24((uint32_t)lane, kc.mK) >> ORB_QUOT_SHIFT);
+  const int k0 = lane - (int)__umul24((uint32_t)rr0, (uint32_t)nK);
+  const int off0 = (int)__umul24((uint32_t)(rr0 + 3), (uint32_t)P) + 8 + 8 * k0;  // interior column 8 k0
+  const int slotOff = ci;
   if (!tiny && lane < R) {
     const int nS = P >> 2;  // dwords per row (<= 14, host-checked): the row, no further
-    uint2* dst = reinterpret_cast<uint2*>(tile + lane * P);
+    const uint32_t rowOff = __umul24((uint32_t)lane, (uint32_t)P);
+    uint2* dst = reinterpret_cast<uint2*>(tile + rowOff);
 #pragma unroll
     for (int k = 0; k < 7; ++k) {
       if (2 * k < nS)
@@ -1168,32 +1202,29 @@ void k_fast_cells(
                             __builtin_amdgcn_alignbyte(raw[2 * k + 2], raw[2 * k + 1], rsh));
     }
   }
-  // strengths start at 0 over the whole map: the halo and the columns past the
+  // strengths start at 0 over the rows NMS reads, 2 .. R - 3 of this cell (the
+  // interior rows and one above and below: bytes [2 P, (R - 2) P), 2 P a multiple
+  // of 16), not over the launch's whole map: the halo and the columns past the
   // interior are never scored, so NMS reads 0 there without bounds tests
-  {
-    uint4* sc16 = reinterpret_cast<uint4*>(tile + tileElems);
-    for (int i = lane; i < (tileElems >> 4); i += 64) sc16[i] = make_uint4(0u, 0u, 0u, 0u);
+  // (a row per lane beside the staging stores was measured: one more LDS
+  // instruction per cell and 14 % more bank conflicts than this linear clear)
+  if (!tiny) {
+    uint4* sc16 = reinterpret_cast<uint4*>(sc + 2 * P);
+    const int n16 = ((R - 4) * P + 15) >> 4;
+    for (int i = lane; i < n16; i += 64) sc16[i] = make_uint4(0u, 0u, 0u, 0u);
   }
   const int ciNext = jc + 1 < FC_CPW ? cell_of(jc + 1) : cellEnd;
   if (ciNext < cellEnd) {
-    ncd = cells[ciNext];
-    issue(ncd);
+    nw0 = cellW[3 * ciNext];
+    nw1 = cellW[3 * ciNext + 1];
+    nw2 = cellW[3 * ciNext + 2];
+    issue(nw0, nw1, nw2);
   }
   if (tiny) {
-    if (lane == 0) cellCount[slot] = 0;
+    if (lane == 0) imgCount[slotOff] = 0;
     ci = ciNext;
     continue;
   }
-  const int iw = C - 6, ih = R - 6;
-  const int nK = (iw + 7) >> 3;  // 8-pixel groups per interior row
-  const int nvLast = iw - 8 * (nK - 1);
-  const int ti = min(max(plan.iniTh, 0), 255), tm = min(max(plan.minTh, 0), 255);
-  // quotients q = (int)((x + 0.5) * (1 / d)) for x < 2^13, d <= 88 are exact
-  // with the hardware reciprocal (<= 1 ulp): (x + 0.5) / d sits >= 0.5 / d
-  // (>= 0.0057) from an integer, the reciprocal and product err < 2e-5.  An
-  // IEEE division (this library's default for 1.0f / x) costs ~11 VALU each
-  const float invK = __builtin_amdgcn_rcpf((float)nK), invP = __builtin_amdgcn_rcpf((float)P),
-              invW = __builtin_amdgcn_rcpf((float)iw);
   wave_lds_sync();
 
   int nq = 0, nc = 0;  // wave-uniform queue / corner counts
@@ -1236,12 +1267,7 @@ void k_fast_cells(
   auto fast_pass = [&](int t, bool fresh) {
     h16x2 T;
     T.x = T.y = __builtin_bit_cast(_Float16, (uint16_t)(t + 1));
-    const int nG = ih * nK;
-    const int rr0 = (int)(((float)lane + 0.5f) * invK);
-    int k = lane - rr0 * nK;
-    int off = (rr0 + 3) * P + 8 + 8 * k;  // byte of interior column 8k
-    const int rInc = (int)(64.5f * invK), kInc = 64 - rInc * nK;  // wave-uniform, = 64 / nK
-    const int dOff = rInc * P + 8 * kInc, wrapOff = P - 8 * nK;
+    int k = k0, off = off0;
     for (int g0 = 0; g0 < nG; g0 += 64) {
       const bool valid = g0 + lane < nG;
       const bool last = k == nK - 1;
@@ -1274,13 +1300,14 @@ void k_fast_cells(
       // the lane's interior pixels.
       // gather the sign bytes (bytes 1, 3 of each rp[i]: pixels 0..7), move the
       // sign bits to bit 0 (pixels 0-3) / bit 4 (pixels 4-7) of each byte, and
-      // collect them into bits 24..31 with one multiply (no carries: every
-      // partial product lands on its own bit); a set sign bit = no pass
+      // collect them with one byte dot product, byte i weighted 2^i: bit i of
+      // the sum is pixel i, bit 4 + i pixel 4 + i (no carries: every term is
+      // its own bit); a set sign bit = no pass
       const uint32_t X = __builtin_amdgcn_perm(rp[1], rp[0], 0x07050301u);
       const uint32_t Y = __builtin_amdgcn_perm(rp[3], rp[2], 0x07050301u);
       const uint32_t fails = ((X >> 7) & 0x01010101u) | ((Y >> 3) & 0x10101010u);
-      uint32_t mk = ~((fails * 0x01020408u) >> 24) &
-                    (valid ? (last ? (1u << nvLast) - 1u : 0xFFu) : 0u);
+      uint32_t mk = ~__builtin_amdgcn_udot4(fails, 0x08040201u, 0u, false) &
+                    (valid ? (last ? (uint32_t)lastMask : 0xFFu) : 0u);
       const int cnt = __builtin_popcount(mk);
       int incl = wave_incl_scan(cnt);
       // opaque: otherwise hipcc forms incl - cnt from the scan's partial DPP
@@ -1311,11 +1338,11 @@ void k_fast_cells(
   // has nb > t && nb >= m (outside counts as 0).  The corner list (or, dense,
   // the window) is in row-major order, so each survivor's key goes straight to
   // its output position
-  uint32_t* out = cellKeys + slot * plan.keyCap;
+  uint32_t* out = imgKeys + slotOff * plan.keyCap;
   auto nms_emit = [&](int t) -> int {
     const bool dense = nc > FC_CCAP;
     const int nItems = dense ? ih * iw : nc;
-    const uint32_t kx0 = (uint32_t)(cd.x0 + 3), ky0 = (uint32_t)(cd.y0 + 3);
+    const uint32_t kx0 = (cw1 >> 16) + 3u, ky0 = (cw0 >> 16) + 3u;  // x0 + 3, y0 + 3
     int nOut = 0;
     for (int j0 = 0; j0 < nItems; j0 += 64) {
       const int j = j0 + lane;
@@ -1323,15 +1350,19 @@ void k_fast_cells(
       int x = 0, y = 0, m = 0;
       if (j < nItems) {
         int off;
+        // j / iw and off / P by the class's multiply-shifts; every product is a
+        // 24-bit multiply (orb_cell_class_ok bounds the operands)
         if (dense) {
-          y = (int)(((float)j + 0.5f) * invW);
-          x = j - y * iw;
-          off = (y + 3) * P + (x + 8);
+          y = (int)(__umul24((uint32_t)j, mW) >> ORB_QUOT_SHIFT);
+          x = j - (int)__umul24((uint32_t)y, (uint32_t)iw);
+          off = (int)__umul24((uint32_t)(y + 3), (uint32_t)P) + (x + 8);
         } else {
           off = corners[j];
-          const int ry = (int)(((float)off + 0.5f) * invP);
+          const int ry = (int)(__umul24((uint32_t)off, mP) >> ORB_QUOT_SHIFT);
           y = ry - 3;
-          x = off - ry * P - 8;
+          // (ry * -P as a signed 24-bit product: from off - ry * P the compiler
+          // makes a full 32-bit multiply by the constant -P)
+          x = off - 8 + __mul24(ry, -P);
         }
         int oq = off - P - 1;  // 3x3 window from its top-left byte (opaque: see fast_score_u8)
         if (PT) __asm__ volatile("" : "+v"(oq));
@@ -1340,9 +1371,12 @@ void k_fast_cells(
         // neighbours outside the interior read 0 (the map is cleared per cell)
         const int nb[8] = {cq[0], cq[1], cq[2], cq[P], cq[P + 2], cq[2 * P], cq[2 * P + 1],
                            cq[2 * P + 2]};
-        ok = m > t && m >= 2;
+        // with m > t a neighbour nb >= m is above t as well: the rule
+        // "no neighbour with nb > t && nb >= m" is max nb < m
+        int nbMax = nb[0];
 #pragma unroll
-        for (int k = 0; k < 8; ++k) ok = ok && !(nb[k] > t && nb[k] >= m);
+        for (int k = 1; k < 8; ++k) nbMax = max(nbMax, nb[k]);
+        ok = m > t && m >= 2 && nbMax < m;
       }
       const unsigned long long bal = __ballot(ok);
       const int pos = nOut + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32),
@@ -1361,7 +1395,7 @@ void k_fast_cells(
     fast_pass(tm, false);
     n = nms_emit(tm);
   }
-  if (lane == 0) cellCount[slot] = n;
+  if (lane == 0) imgCount[slotOff] = n;
   ci = ciNext;
   wave_lds_sync();  // the next cell's staging overwrites the tile
   }  // cell loop
@@ -2900,8 +2934,11 @@ hipError_t orb_k_fast_band(const uint8_t* img0, long long img0Pitch, int img0Str
 // k_fast_cells stages one ROI row per lane (every ORB-SLAM2 configuration;
 // the larger cells of tiny levels go to k_fast_band)
 bool orb_k_fast_cells_fits(const OrbPlanDesc* plan) {
-  // lane = ROI row (<= 64 rows); a row's P <= 56 bytes (+3 realign) in four 16-byte loads
-  return plan->maxCellRows <= 64 && ((plan->maxCellCols + 20) & ~7) <= 56;
+  // lane = ROI row (<= 64 rows); a row's P <= 56 bytes (+3 realign) in four 16-byte loads;
+  // every cell class's quotient multipliers and 24-bit products checked by the
+  // planner (orb_cell_class_ok); a cell's key slot offset within an image in 31 bits
+  return plan->maxCellRows <= 64 && ((plan->maxCellCols + 20) & ~7) <= 56 &&
+         plan->cellClassesOk && (long long)plan->ncells * plan->keyCap < (1LL << 31);
 }
 
 size_t orb_k_fast_cells_lds(int maxRows, int maxCols) {
@@ -2912,10 +2949,13 @@ size_t orb_k_fast_cells_lds(int maxRows, int maxCols) {
 // resize chain, which levels >= 1 wait for)
 hipError_t orb_k_fast_cells(const uint8_t* img0, long long img0Pitch, int img0Stride,
                             const uint8_t* arena, long long arenaPitch, const OrbPlanDesc* plan,
-                            const OrbCellDesc* cells, uint32_t* cellKeys, int32_t* cellCount,
-                            int32_t* errFlag, int cellBeg, int cellEnd, int nimg, hipStream_t s) {
+                            const OrbCellDesc* cells, const OrbCellClass* classes,
+                            uint32_t* cellKeys, int32_t* cellCount, int32_t* errFlag, int cellBeg,
+                            int cellEnd, int nimg, hipStream_t s) {
   if (cellEnd <= cellBeg) return hipSuccess;
-  if (!orb_k_fast_cells_fits(plan)) return hipErrorInvalidValue;
+  // (level 0's pitch is the caller's stride: the kernel's row x pitch is a 24-bit multiply)
+  if (!orb_k_fast_cells_fits(plan) || img0Stride < 0 || img0Stride >= (1 << 24))
+    return hipErrorInvalidValue;
   // LDS sized for the largest cell of the levels this launch covers (level 0's
   // side launch gets the smaller slices of its 38-row cells)
   int mr = 7, mc = 7;
@@ -2938,11 +2978,11 @@ hipError_t orb_k_fast_cells(const uint8_t* img0, long long img0Pitch, int img0St
   dim3 grid((n + FC_WAVES * FC_CPW - 1) / (FC_WAVES * FC_CPW), nimg), block(64 * FC_WAVES);
   if (p56)
     hipLaunchKernelGGL(k_fast_cells<FC_CONST_PITCH>, grid, block, lds, s, img0, img0Pitch, img0Stride, arena,
-                       arenaPitch, *plan, cells, cellKeys, cellCount, tileElems, cellBeg, cellEnd,
+                       arenaPitch, *plan, cells, classes, cellKeys, cellCount, tileElems, cellBeg, cellEnd,
                        errFlag);
   else
     hipLaunchKernelGGL(k_fast_cells<0>, grid, block, lds, s, img0, img0Pitch, img0Stride, arena,
-                       arenaPitch, *plan, cells, cellKeys, cellCount, tileElems, cellBeg, cellEnd,
+                       arenaPitch, *plan, cells, classes, cellKeys, cellCount, tileElems, cellBeg, cellEnd,
                        errFlag);
   return hipGetLastError();
 }

@@ -39,7 +39,8 @@ bool orb_k_fast_cells_fits(const OrbPlanDesc* plan);
 size_t orb_k_fast_cells_lds(int maxRows, int maxCols);
 hipError_t orb_k_fast_cells(const uint8_t* img0, long long img0Pitch, int img0Stride,
                             const uint8_t* arena, long long arenaPitch, const OrbPlanDesc* plan,
-                            const OrbCellDesc* cells, uint32_t* cellKeys, int32_t* cellCount,
+                            const OrbCellDesc* cells, const OrbCellClass* classes,
+                            uint32_t* cellKeys, int32_t* cellCount,
                             int32_t* errFlag, int cellBeg, int cellEnd, int nimg, hipStream_t s);
 size_t orb_k_octree_lds(int nodeCapMax, int maxCellsPerLevel, int ldsKeyCap);
 size_t orb_k_octree_node_bytes(int nodeCapMax, int maxCellsPerLevel);

@@ -126,7 +126,7 @@ static orb_status_t build_plan(orb_extractor* h, int W, int H) {
         c.y1 = (int16_t)(int)maxY;
         c.x0 = (int16_t)(int)iniX;
         c.x1 = (int16_t)(int)maxX;
-        c._pad = 0;
+        c.cls = 0;  // orb_build_cell_classes below
         cells.push_back(c);
         const int rows = c.y1 - c.y0, cols = c.x1 - c.x0;
         maxRows = std::max(maxRows, rows);
@@ -253,6 +253,16 @@ static orb_status_t build_plan(orb_extractor* h, int W, int H) {
   // candidate queue must fit the 64 KiB a workgroup may allocate
   if (orb_k_fast_band_lds(maxBandBytes) > 64 * 1024) return ORB_EINVAL;
   P.ncells = (int)cells.size();
+  // k_fast_cells' class table: the cells grouped by (level, rows, cols), and the
+  // host check of each class's quotient multipliers and 24-bit products; a plan
+  // that fails it (or has more classes than the table holds) takes k_fast_band
+  std::vector<OrbCellClass> classes(ORB_MAX_CELL_CLASSES);
+  const int nClasses =
+      orb_build_cell_classes(&P, cells.data(), P.ncells, classes.data(), ORB_MAX_CELL_CLASSES);
+  classes.resize(std::max(nClasses, 0));
+  P.nCellClasses = (int)classes.size();
+  P.cellClassesOk = nClasses >= 0;
+  for (const OrbCellClass& k : classes) P.cellClassesOk = P.cellClassesOk && orb_cell_class_ok(&k);
   P.nBlurTiles = (int)tiles.size();
   P.nBands = (int)bands.size();
   P.maxBandBytes = maxBandBytes;
@@ -277,7 +287,9 @@ static orb_status_t build_plan(orb_extractor* h, int W, int H) {
   // the tables below are read by the previous call's kernels, which may still
   // run on another stream (CallOrder): the uploads wait for that call
   if (must_wait(h->lastStream, h->stream)) HIP_TRY(hipStreamWaitEvent(h->stream, h->evBatch, 0));
-  orb_status_t st = h->dCells.ensure(cells.size() * sizeof(OrbCellDesc));
+  // the class table follows the cells in one buffer, 16-byte aligned
+  const size_t classOff = (cells.size() * sizeof(OrbCellDesc) + 15) & ~(size_t)15;
+  orb_status_t st = h->dCells.ensure(classOff + std::max<size_t>(classes.size(), 1) * sizeof(OrbCellClass));
   if (st) return st;
   st = h->dRtab.ensure(std::max<size_t>(rtab.size(), 1) * 4);
   if (st) return st;
@@ -291,6 +303,9 @@ static orb_status_t build_plan(orb_extractor* h, int W, int H) {
                          hipMemcpyHostToDevice, h->stream));
   HIP_TRY(hipMemcpyAsync(h->dCells.p, cells.data(), cells.size() * sizeof(OrbCellDesc),
                          hipMemcpyHostToDevice, h->stream));
+  if (!classes.empty())
+    HIP_TRY(hipMemcpyAsync((char*)h->dCells.p + classOff, classes.data(),
+                           classes.size() * sizeof(OrbCellClass), hipMemcpyHostToDevice, h->stream));
   if (!rtab.empty())
     HIP_TRY(hipMemcpyAsync(h->dRtab.p, rtab.data(), rtab.size() * 4, hipMemcpyHostToDevice,
                            h->stream));
@@ -298,6 +313,7 @@ static orb_status_t build_plan(orb_extractor* h, int W, int H) {
   h->lastStream = nullptr;  // the previous call has finished (waited for above)
   h->plan = P;
   h->cells.swap(cells);
+  h->cellClassOff = classOff;
   h->arenaBytes = (arena + 255) & ~255LL;
   h->blurBytes = (blurArena + 255) & ~255LL;
   h->maxCellsPerLevel = maxCellsPerLevel;
@@ -390,13 +406,16 @@ static orb_status_t run_batch(orb_extractor* h, const uint8_t* d_images, int B, 
   // staging; k_fast_band (one workgroup per run of cells) otherwise and for a
   // frame or two per call (the band kernel's fewer, larger workgroups and a
   // single stream give the lower latency)
-  const bool useBands = B < FAST_CELLS_MIN_BATCH || !orb_k_fast_cells_fits(&P);
+  // (a caller stride of 2^24 or more is past k_fast_cells' 24-bit row x pitch product)
+  const bool useBands = B < FAST_CELLS_MIN_BATCH || !orb_k_fast_cells_fits(&P) || stride >= (1 << 24);
   pf.names[2] = useBands ? "k_fast_band" : "k_fast_cells";
   // k_fast_cells over the cells [cb, ce) (whole levels) on stream st
   auto fast = [&](int cb, int ce, hipStream_t st) -> hipError_t {
     return orb_k_fast_cells(d_images, (long long)imgPitch, (int)stride, arena, ap, &P,
-                            h->dCells.as<OrbCellDesc>(), h->dCellKeys.as<uint32_t>(),
-                            h->dCellCount.as<int32_t>(), h->dErr.as<int32_t>(), cb, ce, B, st);
+                            h->dCells.as<OrbCellDesc>(),
+                            (const OrbCellClass*)((const char*)h->dCells.p + h->cellClassOff),
+                            h->dCellKeys.as<uint32_t>(), h->dCellCount.as<int32_t>(),
+                            h->dErr.as<int32_t>(), cb, ce, B, st);
   };
   // Level 0 is the caller's image: its FAST cells need no pyramid, so they run
   // on the side stream beside the latency-bound resize chain (fork / join by

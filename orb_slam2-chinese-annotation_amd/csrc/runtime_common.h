@@ -325,6 +325,7 @@ struct orb_extractor {
   int planW = -1, planH = -1;
   OrbPlanDesc plan;
   std::vector<OrbCellDesc> cells;
+  size_t cellClassOff = 0;  // byte offset of the OrbCellClass table inside dCells
   long long arenaBytes = 0, blurBytes = 0;
   int maxCellsPerLevel = 0, nodeCapMax = 0, ldsKeyCap = 0;
   int nResizePairs = 0;  // resize launches per call with the level pairs (PYR_PAIR_MAX_IMAGES)

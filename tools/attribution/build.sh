@@ -23,6 +23,9 @@
 # PATCHES=octree_stamps.patch adds k_octree's per-phase s_memtime sums per level
 # (-DOCT_STAMPS, read by tools/probe/oct_stamps.py; the stamps themselves cost
 # about a third of the stamped kernel's time, so read them as shares).
+# PATCHES=append_trips.patch adds counters of k_fast_cells' queue-append loop
+# (-DFC_TRIPS: rounds, trips, entries, trips-per-round histogram; read by
+# tools/probe/fc_append_trips.py; the counters are global atomics, timing is off).
 # Select the build with ORB_AMD_LIB=<path>.  variants.patch is the diff from
 # the product file to the round-5 source that held these blocks inline
 # (regenerate: tools/unifdef.py resolves them, see its docstring).
