@@ -101,6 +101,12 @@
  *                                  src/ORBmatcher.cc:718-901 as the neighbour loop of
  *                                  CreateNewMapPoints calls it src/LocalMapping.cc:313-318,
  *                                  on the slot arrays of orb_create_new_map_points_batch
+ *   orb_match_bow_kf_batch         device-batched SearchByBoW(pKF1, pKF2, vpMatches12)
+ *                                  src/ORBmatcher.cc:581-716 with ComputeSim3's 20-match
+ *                                  gate src/LoopClosing.cc:282-293, on the solver's slots
+ *   orb_search_by_sim3_batch       device-batched SearchBySim3 src/ORBmatcher.cc:1212-1458
+ *                                  with the inlier filter of src/LoopClosing.cc:338-343, on
+ *                                  the solver's slots, rows, result and inlier flags
  *   orb_vocabulary_create / _load_text / _destroy
  *                                  DBoW2 TemplatedVocabulary ctor + loadFromTextFile
  *                                  Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:1362-1448
@@ -1993,6 +1999,135 @@ orb_status_t orb_optimize_sim3(
  * pinned_exp(d_x[i]).  Asynchronous on `stream`. */
 orb_status_t orb_pinned_exp_batch(orb_matcher_t* m, int n, const double* d_x, double* d_y,
                                   void* stream);
+
+/* ------------- LoopClosing::ComputeSim3's two matchers as device batches
+ * (src/LoopClosing.cc:251-428).  With orb_sim3_solver_*_batch and
+ * orb_optimize_sim3_batch they make a round over all loop candidates one chain
+ * on one stream: orb_match_bow_kf_batch -> setup -> { iterate ->
+ * orb_search_by_sim3_batch -> orb_optimize_sim3_batch }, with no host copy in
+ * between.  Both calls: every per-problem array a device pointer, asynchronous
+ * on `stream`, no host synchronisation, upload or download, one workgroup per
+ * problem, all state in LDS and the caller's arrays (none of the handle's
+ * scratch: `stream` alone orders the call).  n_problems == 0: ORB_OK, no
+ * launch.  A kp_stride above the call's *_max_stride(): ORB_ECAPACITY before
+ * anything is launched, nothing written.
+ *
+ * Device-batched SearchByBoW(pKF1, pKF2, vpMatches12) (src/ORBmatcher.cc:
+ * 581-716).  Slots: one family in orb_match_bow_batch's keyframe layout (keys,
+ * point_index, fv_nodes and fv_feats at k * kp_stride, descriptors at
+ * 32 * k * kp_stride, fv_offs at k * (kp_stride + 1), the counts nkeys[k] and
+ * n_fv_nodes[k]; of the keys only `angle` is read).  Problem p matches slot
+ * d_kf1_slot[p] against slot d_kf2_slot[p] (either NULL: slot p; a slot may
+ * serve many problems, the current keyframe serves all of them).
+ * d_kf_point_index[i] >= 0 names mvpMapPoints[i] in d_points, one array shared
+ * by all problems, of which only `bad` is read (d_points NULL: no point is
+ * bad); any negative value is NULL.
+ * Per problem the reference loop: only common nodes; the KF1 keypoints of a
+ * node in list order, each with a non-NULL, non-bad point; KF2 candidates with
+ * a non-NULL, non-bad point that are not yet in vbMatched2; best and second
+ * best by strict <; accepted iff bestDist1 < 50 and (float)bestDist1 <
+ * nnratio * (float)bestDist2; vbMatched2 set at acceptance and never cleared;
+ * the rotation histogram over angle1 - angle2 with ComputeThreeMaxima.
+ * Out: d_match12 + p * kp_stride over KF1's clamped count: the global point
+ * index of the matched KF2 keypoint's point or -1; d_index2 + p * kp_stride:
+ * that keypoint's index (bestIdx2) or -1; entries removed by the filter are -1
+ * in both rows; entries past the count are not written.  The two rows are
+ * orb_sim3_solver_setup_batch's d_match12 and d_index2 as they stand.
+ * d_info[p]: orb_bow_match_info_t (n_tried counts KF1 keypoints).
+ * min_matches (ComputeSim3: 20; 0: no gate): a problem with fewer matches
+ * keeps its counts, gets enough = 0 and both rows -1; the solver's setup then
+ * finds N = 0 and iterate returns no_more at once.
+ * Malformed slots as in orb_match_bow_batch (counts and node counts clamped;
+ * decreasing or oversized offsets or a feature index >= the count in either
+ * FeatureVector): n_matches = -1, the other fields 0, both rows -1 over KF1's
+ * clamped count, nothing indexed with the bad value.  Ascending node ids are
+ * the caller's promise.
+ * Per problem the rows equal orb_match_bow_kf's output on the same inputs,
+ * mapped through point_index.
+ * Capacity: 8 * ((kp_stride + 3) & ~3) + 512 bytes (the claim word per KF2
+ * keypoint, the partner node per KF1 node) must fit the 160 KiB of one CU;
+ * orb_match_bow_kf_batch_max_stride() is the largest such kp_stride (a pure
+ * function, callable without a device).
+ * ORB_EINVAL: a null required pointer, n_problems < 0, kp_stride <= 0, nnratio
+ * not finite. */
+orb_status_t orb_match_bow_kf_batch(
+    orb_matcher_t* m, int n_problems, const int32_t* d_kf1_slot, const int32_t* d_kf2_slot,
+    const orb_keypoint_t* d_kf_keys, const uint8_t* d_kf_desc, const int32_t* d_kf_nkeys,
+    const int32_t* d_kf_point_index, const uint32_t* d_kf_fv_nodes, const int32_t* d_kf_fv_offs,
+    const uint32_t* d_kf_fv_feats, const int32_t* d_kf_n_fv_nodes, int kp_stride,
+    const orb_map_point_t* d_points, float nnratio, int check_orientation, int min_matches,
+    int32_t* d_match12, int32_t* d_index2, orb_bow_match_info_t* d_info, void* stream);
+int orb_match_bow_kf_batch_max_stride(void);
+
+/* Device-batched SearchBySim3 (src/ORBmatcher.cc:1212-1458) with the inlier
+ * filter of src/LoopClosing.cc:338-343 in front of it.
+ * Slots: those of orb_sim3_solver_setup_batch (d_kf1_slot, d_kf2_slot,
+ * d_kf_keys, d_kf_nkeys, d_kf_point_index, d_kf_pose of which rcw and tcw are
+ * read, kp_stride, d_points) plus d_kf_desc (32 bytes per keypoint slot) and
+ * d_mp_desc (32 bytes per entry of d_points, GetDescriptor()).
+ * Per problem: the rows d_match12 / d_index2 + p * kp_stride (in/out: the
+ * arrays given to the solver), d_inliers12 + p * kp_stride (optional, the
+ * solver's vbInliers), d_sim3[p] (R, t, scale and has_sim3 are read; the
+ * solver's d_result may be passed as it is), d_active[p] (optional).  A problem
+ * with has_sim3 == 0 or d_active[p] == 0 is skipped: nothing of it is read or
+ * written.
+ * Host values: one `cam` (the reference projects with pKF1's fx, fy, cx, cy in
+ * both directions), the bounds min_x, max_x, min_y, max_y of
+ * KeyFrame::IsInImage (half-open; max > min), n_levels in [1, 16],
+ * scale_factors[n_levels], log_scale_factor, th (ComputeSim3: 7.5).
+ * Per problem, in this order:
+ *  1 with d_inliers12, every i1 below KF1's clamped count with inliers[i1] == 0
+ *    gets match12[i1] = index2[i1] = -1;
+ *  2 already1[i1] = match12[i1] >= 0; already2[index2[i1]] = 1 for those
+ *    entries with 0 <= index2[i1] < N2 (an index outside is ignored, as in the
+ *    reference: not malformed);
+ *  3 sR12 = (float)((double)s * (double)R[r][c]), sR21 = (float)((1.0 /
+ *    (double)s) * (double)R[c][r]), t21[r] = -((sR21[r][0] t0 + sR21[r][1] t1) +
+ *    sR21[r][2] t2) in float, as orb_search_by_sim3 computes them on the host;
+ *  4 the 64 x 48 grids of both keyframes, keypoints in ascending index inside a
+ *    cell, a keypoint outside the bounds in no cell;
+ *  5 KF1's points (non-NULL, not already matched, not bad) through R1w, t1w,
+ *    sR21, t21 into KF2: depth < 0 rejected, the projection inside the
+ *    half-open bounds, cv::norm in double, the range 0.8f * min_distance ..
+ *    1.2f * max_distance, the level from PredictScale with the unscaled
+ *    max_distance (clamped to [0, n_levels - 1]), radius = th * scale[level],
+ *    GetFeaturesInArea's order, octaves in [level - 1, level], the first
+ *    minimum Hamming distance, accepted iff <= 100;
+ *  6 the same from KF2 through R2w, t2w, sR12, t12 into KF1;
+ *  7 i1 with vnMatch1[i1] = idx2 >= 0 and vnMatch2[idx2] == i1 gets
+ *    match12[i1] = point_index2[idx2] and index2[i1] = idx2.
+ * Out: the two rows in place (orb_optimize_sim3_batch's d_match12 / d_index2
+ * as they stand); d_new12 + p * kp_stride (optional) over KF1's clamped count:
+ * idx2 where this call added a match, else -1 (orb_search_by_sim3's match12 on
+ * the same inputs); d_info[p] as below, exact and deterministic.
+ * Octaves are only compared and the predicted level is clamped: no octave makes
+ * a problem malformed.  Counts are clamped to [0, kp_stride].  The caller keeps
+ * every non-negative point index inside d_points and d_mp_desc and every slot
+ * number inside the slot arrays (NOT checked, as in the solver).
+ * Capacity: two cell-start tables of 3,076 ints and 16 bytes per keypoint slot
+ * (two cell-ordered index lists, vnMatch1, vnMatch2): 24,608 + 16 *
+ * ((kp_stride + 3) & ~3) + 1,024 bytes must fit the 160 KiB of one CU;
+ * orb_search_by_sim3_batch_max_stride() is the largest such kp_stride (a pure
+ * function, callable without a device; above orb_optimize_sim3_max_stride()).
+ * ORB_EINVAL: a null required pointer, n_problems < 0, kp_stride <= 0, n_levels
+ * outside [1, 16], bounds with max <= min. */
+typedef struct orb_sim3_search_info {
+  int32_t n_found;  /* the return value: matches added by this call */
+  int32_t n_kept;   /* non-NULL entries of the row after the inlier filter */
+  int32_t n_total;  /* n_kept + n_found (nTotalMatches before OptimizeSim3) */
+  int32_t n_best12; /* entries of vnMatch1 that are >= 0 */
+  int32_t n_best21; /* entries of vnMatch2 that are >= 0 */
+} orb_sim3_search_info_t; /* 20 bytes */
+orb_status_t orb_search_by_sim3_batch(
+    orb_matcher_t* m, int n_problems, const int32_t* d_kf1_slot, const int32_t* d_kf2_slot,
+    const orb_keypoint_t* d_kf_keys, const uint8_t* d_kf_desc, const int32_t* d_kf_nkeys,
+    const int32_t* d_kf_point_index, const orb_pose_t* d_kf_pose, int kp_stride,
+    const orb_map_point_t* d_points, const uint8_t* d_mp_desc, int32_t* d_match12,
+    int32_t* d_index2, const uint8_t* d_inliers12, const orb_sim3_result_t* d_sim3,
+    const uint8_t* d_active, const orb_camera_t* cam, float min_x, float max_x, float min_y,
+    float max_y, int n_levels, const float* scale_factors, float log_scale_factor, float th,
+    int32_t* d_new12, orb_sim3_search_info_t* d_info, void* stream);
+int orb_search_by_sim3_batch_max_stride(void);
 
 #ifdef __cplusplus
 }

@@ -86,6 +86,9 @@ TRI_MATCH_INFO_DTYPE = np.dtype([("n_matches", "<i4"), ("n_accepted", "<i4"),
                                  ("n_common_nodes", "<i4"), ("n_tried", "<i4"),
                                  ("n_shared2", "<i4"), ("n_undefined", "<i4")])
 assert TRI_MATCH_INFO_DTYPE.itemsize == 24
+SIM3_SEARCH_INFO_DTYPE = np.dtype([("n_found", "<i4"), ("n_kept", "<i4"), ("n_total", "<i4"),
+                                   ("n_best12", "<i4"), ("n_best21", "<i4")])
+assert SIM3_SEARCH_INFO_DTYPE.itemsize == 20
 # orb_new_point_info_t.counts / the status bytes (ORB_NP_*)
 (NP_NOT_TRIED, NP_NO_MATCH, NP_ACCEPTED, NP_LOW_PARALLAX, NP_W_ZERO, NP_Z1, NP_Z2, NP_REPROJ1,
  NP_REPROJ2, NP_ZERO_DIST, NP_SCALE_RATIO, NP_UNDEFINED) = range(12)
@@ -293,6 +296,13 @@ def lib() -> ctypes.CDLL:
         "orb_optimize_sim3": (i32, [vp, vp, i32, vp, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, i32,
                                     vp, vp, f32, i32, vp]),
         "orb_pinned_exp_batch": (i32, [vp, i32, vp, vp, vp]),
+        "orb_match_bow_kf_batch": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp,
+                                         f32, i32, i32, vp, vp, vp, vp]),
+        "orb_match_bow_kf_batch_max_stride": (i32, []),
+        "orb_search_by_sim3_batch": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp,
+                                           vp, vp, vp, vp, f32, f32, f32, f32, i32, vp, f32, f32,
+                                           vp, vp, vp]),
+        "orb_search_by_sim3_batch_max_stride": (i32, []),
         "orb_synth_image": (None, [ctypes.c_uint64, i32, i32, i32, i32, vp, sz]),
         "orb_synth_local_map": (None, [ctypes.c_uint64, vp, vp, i32, i32, i32, i32, vp, vp, vp]),
     }
@@ -309,7 +319,9 @@ def lib() -> ctypes.CDLL:
              "orb_create_new_map_points_batch", "orb_create_new_map_points_max_stride",
              "orb_create_new_map_points", "orb_search_for_triangulation_batch",
              "orb_search_for_triangulation_batch_max_stride", "orb_optimize_sim3_batch",
-             "orb_optimize_sim3_max_stride", "orb_optimize_sim3", "orb_pinned_exp_batch")
+             "orb_optimize_sim3_max_stride", "orb_optimize_sim3", "orb_pinned_exp_batch",
+             "orb_match_bow_kf_batch", "orb_match_bow_kf_batch_max_stride",
+             "orb_search_by_sim3_batch", "orb_search_by_sim3_batch_max_stride")
     for name, (res, args) in sig.items():
         if name in newer and "ORB_AMD_LIB" in os.environ and not hasattr(L, name):
             continue
@@ -354,6 +366,18 @@ def search_for_triangulation_batch_max_stride() -> int:
     """orb_search_for_triangulation_batch_max_stride(): a pure function of
     k_tri_batch's LDS layout, callable without a device."""
     return lib().orb_search_for_triangulation_batch_max_stride()
+
+
+def match_bow_kf_batch_max_stride() -> int:
+    """orb_match_bow_kf_batch_max_stride(): a pure function of k_bow_kf_batch's
+    LDS layout, callable without a device."""
+    return lib().orb_match_bow_kf_batch_max_stride()
+
+
+def search_by_sim3_batch_max_stride() -> int:
+    """orb_search_by_sim3_batch_max_stride(): a pure function of
+    k_sim3_search_batch's LDS layout, callable without a device."""
+    return lib().orb_search_by_sim3_batch_max_stride()
 
 
 def update_local_map_max_keyframes() -> int:
@@ -1641,6 +1665,63 @@ class ORBmatcher:
     def search_for_triangulation_batch_max_stride() -> int:
         """Largest kp_stride search_for_triangulation_batch accepts."""
         return lib().orb_search_for_triangulation_batch_max_stride()
+
+    # ------------------------- LoopClosing::ComputeSim3's matchers, device batches
+    def search_by_bow_kf_batch(self, n_problems, d_kf1_slot, d_kf2_slot, d_kf_keys, d_kf_desc,
+                               d_kf_nkeys, d_kf_point_index, d_kf_fv_nodes, d_kf_fv_offs,
+                               d_kf_fv_feats, d_kf_n_fv_nodes, kp_stride, d_points, min_matches,
+                               d_match12, d_index2, d_info, stream: int = 0):
+        """Device-batched SearchByBoW(pKF1, pKF2, vpMatches12) for n_problems
+        pairs of keyframe slots (orb_match_bow_kf_batch) with this matcher's
+        mfNNratio and mbCheckOrientation.  d_* are device addresses (a torch
+        tensor's data_ptr()) in the keyframe slot layout of
+        search_by_bow_batch; d_kf1_slot, d_kf2_slot (0: slot p) and d_points
+        (0: no bad point) are optional.  d_match12 / d_index2: n_problems x
+        kp_stride int32, the rows sim3_solver_setup_batch reads; d_info:
+        BOW_MATCH_INFO_DTYPE records.  min_matches: ComputeSim3's 20 (0: no
+        gate).  Asynchronous on `stream`."""
+        _check(lib().orb_match_bow_kf_batch(
+            self._h, n_problems, d_kf1_slot or None, d_kf2_slot or None, d_kf_keys or None,
+            d_kf_desc or None, d_kf_nkeys or None, d_kf_point_index or None,
+            d_kf_fv_nodes or None, d_kf_fv_offs or None, d_kf_fv_feats or None,
+            d_kf_n_fv_nodes or None, kp_stride, d_points or None, self.mfNNratio,
+            int(self.mbCheckOrientation), int(min_matches), d_match12 or None, d_index2 or None,
+            d_info or None, stream or None), "search_by_bow_kf_batch")
+
+    @staticmethod
+    def search_by_bow_kf_batch_max_stride() -> int:
+        """Largest kp_stride search_by_bow_kf_batch accepts."""
+        return lib().orb_match_bow_kf_batch_max_stride()
+
+    def search_by_sim3_batch(self, n_problems, d_kf1_slot, d_kf2_slot, d_kf_keys, d_kf_desc,
+                             d_kf_nkeys, d_kf_point_index, d_kf_pose, kp_stride, d_points,
+                             d_mp_desc, d_match12, d_index2, d_inliers12, d_sim3, cam, bounds,
+                             scale_factors, log_scale_factor, d_info, th: float = 7.5,
+                             d_active: int = 0, d_new12: int = 0, stream: int = 0):
+        """Device-batched SearchBySim3 with ComputeSim3's inlier filter in front
+        (orb_search_by_sim3_batch).  d_* are device addresses in the slot
+        layout of sim3_solver_setup_batch plus the descriptors per keypoint
+        slot (d_kf_desc) and per point (d_mp_desc); d_match12 / d_index2 are
+        the solver's rows, updated in place for optimize_sim3_batch;
+        d_inliers12 (0: no filter) and d_sim3 (SIM3_RESULT_DTYPE records) are
+        the solver's outputs as they stand; d_active and d_new12 are optional.
+        cam: (fx, fy, cx, cy[, bf, mb]); bounds: (min_x, max_x, min_y, max_y).
+        d_info: SIM3_SEARCH_INFO_DTYPE records.  Asynchronous on `stream`."""
+        sf = np.ascontiguousarray(scale_factors, np.float32).reshape(-1)
+        c = self._camera4(cam)
+        min_x, max_x, min_y, max_y = (float(v) for v in bounds)
+        _check(lib().orb_search_by_sim3_batch(
+            self._h, n_problems, d_kf1_slot or None, d_kf2_slot or None, d_kf_keys or None,
+            d_kf_desc or None, d_kf_nkeys or None, d_kf_point_index or None, d_kf_pose or None,
+            kp_stride, d_points or None, d_mp_desc or None, d_match12 or None, d_index2 or None,
+            d_inliers12 or None, d_sim3 or None, d_active or None, ctypes.byref(c), min_x, max_x,
+            min_y, max_y, len(sf), _ptr(sf) if len(sf) else None, float(log_scale_factor),
+            float(th), d_new12 or None, d_info or None, stream or None), "search_by_sim3_batch")
+
+    @staticmethod
+    def search_by_sim3_batch_max_stride() -> int:
+        """Largest kp_stride search_by_sim3_batch accepts."""
+        return lib().orb_search_by_sim3_batch_max_stride()
 
     @staticmethod
     def create_new_map_points_max_stride() -> int:

@@ -374,3 +374,41 @@ struct NewPointsParams {
   int32_t* newPairs;
   orb_new_point_info_t* info;
 };
+
+// ---------------------------------------------------- sim3chain_kernels.hip
+// SearchByBoW(pKF1, pKF2, vpMatches12) over nProblems pairs of keyframe slots
+// (by value): one set of slot arrays serves both sides
+struct BowKfBatchParams {
+  int nProblems, stride;
+  const int32_t* kf1Slot;  // null: p
+  const int32_t* kf2Slot;
+  BowSlots kf;
+  const int32_t* pointIndex;      // mvpMapPoints per keypoint (< 0: NULL)
+  const orb_map_point_t* points;  // null: no point is bad
+  float nnratio;
+  int checkOri, minMatches;
+};
+
+// SearchBySim3 over nProblems pairs of keyframe slots (by value).  base: the
+// camera, the image bounds with invW / invH, th, logScale, the levels and
+// thr = 100; the kernel adds each direction's R, t, R2, t2.
+struct Sim3SearchParams {
+  int nProblems, stride;
+  const int32_t* kf1Slot;  // null: p
+  const int32_t* kf2Slot;
+  const orb_keypoint_t* keys;
+  const uint8_t* desc;
+  const int32_t* nkeys;
+  const int32_t* pointIndex;
+  const orb_pose_t* pose;
+  const orb_map_point_t* points;
+  const uint8_t* mpDesc;
+  int32_t* match12;           // in/out
+  int32_t* index2;            // in/out
+  const uint8_t* inliers12;   // null: no filter
+  const orb_sim3_result_t* sim3;
+  const uint8_t* active;      // null: every problem
+  PPParams base;
+  int32_t* new12;             // null: not wanted
+  orb_sim3_search_info_t* info;
+};

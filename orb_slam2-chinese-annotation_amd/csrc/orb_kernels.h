@@ -265,4 +265,12 @@ int orb_k_median_depth_max_stride(void);
 int orb_k_new_points_max_stride(void);
 hipError_t orb_k_median_depth(const MedianDepthParams* params, hipStream_t s);
 hipError_t orb_k_new_points(const NewPointsParams* params, hipStream_t s);
+// ---------------------------------------------------- sim3chain_kernels.hip
+// SearchByBoW(KF, KF) and SearchBySim3 over keyframe slot pairs; largest
+// kp_stride whose per-problem state fits one CU's LDS
+int orb_k_bow_kf_batch_max_stride(void);
+hipError_t orb_k_bow_kf_batch(const BowKfBatchParams* params, int32_t* match12, int32_t* index2,
+                              orb_bow_match_info_t* info, hipStream_t s);
+int orb_k_sim3_search_max_stride(void);
+hipError_t orb_k_sim3_search(const Sim3SearchParams* params, hipStream_t s);
 }

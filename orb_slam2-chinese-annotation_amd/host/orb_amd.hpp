@@ -1029,6 +1029,51 @@ class ORBmatcher {
   static int search_for_triangulation_batch_max_stride() {
     return orb_search_for_triangulation_batch_max_stride();
   }
+  // Device-batched SearchByBoW(pKF1, pKF2, vpMatches12) (orb_match_bow_kf_batch;
+  // src/ORBmatcher.cc:581-716 as LoopClosing::ComputeSim3 calls it) with
+  // mfNNratio and mbCheckOrientation, on the keyframe slots of
+  // search_by_bow_batch: d_match12 / d_index2 are the rows
+  // sim3_solver_setup_batch reads.  d_kf1_slot, d_kf2_slot and d_points may be
+  // null (slot p / no bad point); min_matches is ComputeSim3's 20 (0: no gate).
+  void search_by_bow_kf_batch(int n_problems, const int32_t* d_kf1_slot,
+                              const int32_t* d_kf2_slot, const BowSlots& kf,
+                              const int32_t* d_kf_point_index, int kp_stride,
+                              const orb_map_point_t* d_points, int min_matches,
+                              int32_t* d_match12, int32_t* d_index2, orb_bow_match_info_t* d_info,
+                              void* stream = nullptr) {
+    check(orb_match_bow_kf_batch(h_, n_problems, d_kf1_slot, d_kf2_slot, kf.d_keys, kf.d_desc,
+                                 kf.d_nkeys, d_kf_point_index, kf.d_fv_nodes, kf.d_fv_offs,
+                                 kf.d_fv_feats, kf.d_n_fv_nodes, kp_stride, d_points, mfNNratio,
+                                 mbCheckOrientation ? 1 : 0, min_matches, d_match12, d_index2,
+                                 d_info, stream),
+          "search_by_bow_kf_batch");
+  }
+  static int search_by_bow_kf_batch_max_stride() { return orb_match_bow_kf_batch_max_stride(); }
+  // Device-batched SearchBySim3 with ComputeSim3's inlier filter in front
+  // (orb_search_by_sim3_batch; src/ORBmatcher.cc:1212-1458,
+  // src/LoopClosing.cc:338-343): the solver's rows, d_inliers12 and d_result as
+  // they stand, the rows updated in place for optimize_sim3_batch.
+  // d_inliers12, d_active and d_new12 may be null.
+  void search_by_sim3_batch(int n_problems, const int32_t* d_kf1_slot, const int32_t* d_kf2_slot,
+                            const KeyPoint* d_kf_keys, const uint8_t* d_kf_desc,
+                            const int32_t* d_kf_nkeys, const int32_t* d_kf_point_index,
+                            const orb_pose_t* d_kf_pose, int kp_stride,
+                            const orb_map_point_t* d_points, const uint8_t* d_mp_desc,
+                            int32_t* d_match12, int32_t* d_index2, const uint8_t* d_inliers12,
+                            const orb_sim3_result_t* d_sim3, const uint8_t* d_active,
+                            const orb_camera_t& cam, float min_x, float max_x, float min_y,
+                            float max_y, const std::vector<float>& scaleFactors,
+                            float logScaleFactor, float th, int32_t* d_new12,
+                            orb_sim3_search_info_t* d_info, void* stream = nullptr) {
+    check(orb_search_by_sim3_batch(h_, n_problems, d_kf1_slot, d_kf2_slot, d_kf_keys, d_kf_desc,
+                                   d_kf_nkeys, d_kf_point_index, d_kf_pose, kp_stride, d_points,
+                                   d_mp_desc, d_match12, d_index2, d_inliers12, d_sim3, d_active,
+                                   &cam, min_x, max_x, min_y, max_y, (int)scaleFactors.size(),
+                                   scaleFactors.data(), logScaleFactor, th, d_new12, d_info,
+                                   stream),
+          "search_by_sim3_batch");
+  }
+  static int search_by_sim3_batch_max_stride() { return orb_search_by_sim3_batch_max_stride(); }
   static int scene_median_depth_max_stride() { return orb_scene_median_depth_max_stride(); }
   static int create_new_map_points_max_stride() {
     return orb_create_new_map_points_max_stride();

@@ -75,6 +75,16 @@ results table:
       problems; against orb_search_for_triangulation over the same pairs one
       blocking call at a time (host clock) + exact check of four problems
       against the oracle and the one-problem entry
+  L1  LoopClosing::ComputeSim3's matchers, SearchByBoW(KF, KF) and SearchBySim3:
+      64 loop candidates against one current keyframe, about 1,000 keypoints
+      per slot, natural FeatureVectors (scenarios.vocab_nodes), by device
+      events around each launch (median of 20, minimum, maximum), also 1 and 16
+      problems; one full round iterate(5) -> SearchBySim3 -> OptimizeSim3 on
+      one stream; against orb_match_bow_kf and orb_search_by_sim3 over the same
+      problems one blocking call at a time (host clock; run once more with
+      ORB_AMD_LIB naming the parent build for the baseline rows alone) + exact
+      check of four problems; each run writes its rows into
+      profiles/sim3chain_L1.json (this_build / parent_build)
   R1  RGB-D: 640x480 (TUM1 intrinsics and distortion, DepthMapFactor 5000),
       1000 features, 256 frames per launch, device-resident: extract ->
       undistort -> ComputeStereoFromRGBD -> closest points + UnprojectStereo ->
@@ -82,7 +92,7 @@ results table:
       same pipeline without the RGB-D stages (monocular matcher), each new
       kernel alone by HIP events with its algorithmic bytes + exact check
 
-Usage: python tools/bench_configs.py [--configs C1,C2,C3,C5,F1,F3,P1,R1,T1,M1,B1,S1,O1,N1,G1] [--steps K]
+Usage: python tools/bench_configs.py [--configs C1,C2,C3,C5,F1,F3,P1,R1,T1,M1,B1,S1,O1,N1,G1,L1] [--steps K]
 The oracle (CPU restatement) is used only for the CPU rows and parity checks.
 """
 import argparse
@@ -1350,6 +1360,198 @@ def g1(args, orb, oracle, torch):
             "exact_vs_oracle_and_one_problem_entry": bool(exact)}
 
 
+def l1(args, orb, oracle, torch):
+    """ComputeSim3's matchers as device batches: 64 loop candidates against one
+    current keyframe.  With ORB_AMD_LIB naming a build without the batches only
+    the one-problem entries are timed (the baseline side of the comparison)."""
+    import sim3_chain_ref as R
+    import scenarios as S
+    import tri_batch_ref as T
+    P = 64
+    (s1, base2), pts0, md0, host, _ = R.loop_scene(oracle, nf=1000)
+    n = len(base2["desc"])
+    sides, points, mp_desc = [s1], [pts0[:n]], [md0[:n]]
+    for i in range(P):      # the candidate's view of the scene: its own descriptors and points
+        rng = np.random.default_rng(100 + i)
+        bits = np.unpackbits(base2["desc"], axis=1) ^ (rng.random((n, 256)) < 0.02)
+        desc = np.packbits(bits.astype(np.uint8), axis=1)
+        pidx = np.where(base2["pidx"] >= 0, base2["pidx"] + n * i, -1).astype(np.int32)
+        s = dict(base2, desc=desc, pidx=pidx, fv=tuple(oracle.feature_vector(S.vocab_nodes(desc))))
+        sides.append(s)
+        points.append(pts0[n:])
+        mp_desc.append(md0[n:])
+    points, mp_desc = np.concatenate(points), np.concatenate(mp_desc)
+    stride = n
+    arr = T.pack_slots(sides, stride, with_u_right=False)
+    m = orb.ORBmatcher(0.75, True)
+    cam, bounds = host["cam"], (0.0, float(host["width"]), 0.0, float(host["height"]))
+
+    def serial(fn, reps=20):
+        t = []
+        for _ in range(reps):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for p in range(P):
+                fn(p)
+            t.append((time.perf_counter() - t0) * 1e3)   # every call ends in a synchronise
+        t.sort()
+        return {"median": t[len(t) // 2], "min": t[0], "max": t[-1]}
+
+    bad = [R._bad_of(s["pidx"], points) for s in sides]
+    rows = [R.bow_kf_expected(oracle, s1, sides[1 + p], points, 0.75, True, 20) for p in range(P)]
+    exact_rec = R.sim3_record(s=1.1)
+    kfs = []
+    for p in range(P):
+        a1, a2 = R.already_masks(rows[p][0], rows[p][1], n)
+        k1 = R.kf_dict(s1, points, mp_desc, a1, host)
+        k2 = R.kf_dict(sides[1 + p], points, mp_desc, a2, host)
+        fr = lambda k: orb.Frame(k["keys"], k["desc"], k["scale"], k["width"], k["height"])
+        kfs.append((fr(k1), fr(k2), k1, k2))
+
+    def one_bow(p):
+        s2 = sides[1 + p]
+        return m.SearchByBoWKF(s1["desc"], s1["angle"], s1["pidx"], bad[0], s1["fv"], s2["desc"],
+                               s2["angle"], s2["pidx"], bad[1 + p], s2["fv"])
+
+    def one_sim3(p):
+        f1, f2, k1, k2 = kfs[p]
+        return m.SearchBySim3(f1, f2, float(host["log_scale"]), cam, k1["Rw"], k1["tw"], k2["Rw"],
+                              k2["tw"], k1["mps"], k1["valid"], k1["already"], k1["mp_desc"],
+                              k2["mps"], k2["valid"], k2["already"], k2["mp_desc"], 1.1,
+                              exact_rec["R"].reshape(3, 3), exact_rec["t"], 7.5)
+
+    for _ in range(3):
+        one_bow(0), one_sim3(0)
+    lib_path = Path(orb.LIB_PATH).resolve()
+    out = {"config": "L1",
+           "library": str(lib_path.relative_to(ROOT)) if ROOT in lib_path.parents else lib_path.name,
+           "workload": f"ComputeSim3's matchers, {P} loop candidates against one current keyframe, "
+                       f"{n} keypoints per slot, natural FeatureVectors (scenarios.vocab_nodes), "
+                       f"scale drift 1.1, th 7.5",
+           "bow_kf_one_per_call_ms": serial(one_bow), "search_by_sim3_one_per_call_ms": serial(one_sim3),
+           "timing": "one per call: host clock around 64 blocking orb_match_bow_kf / "
+                     "orb_search_by_sim3 calls, median of 20; batches: device events around each "
+                     "launch, median of 20"}
+    def write(key):
+        """profiles/sim3chain_L1.json holds both runs: this build's and, from a run
+        with ORB_AMD_LIB naming a build without the batches, the baseline's."""
+        path = ROOT / "profiles" / "sim3chain_L1.json"
+        both = json.loads(path.read_text()) if path.exists() else {}
+        both[key] = out
+        path.parent.mkdir(exist_ok=True)
+        path.write_text(json.dumps({k: both[k] for k in ("this_build", "parent_build")
+                                    if k in both}, indent=1) + "\n")
+        return out
+
+    if not hasattr(orb.lib(), "orb_match_bow_kf_batch"):
+        return write("parent_build")
+
+    def dev(a):
+        return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).cuda()
+    d = {k: dev(v) for k, v in arr.items() if v is not None}
+    p_ = lambda t: t.data_ptr()
+    k1s, k2s = dev(np.zeros(P, np.int32)), dev(np.arange(1, P + 1, dtype=np.int32))
+    dpts, ddesc = dev(points), dev(mp_desc)
+    draws = dev(np.random.default_rng(1).integers(0, 2147483648, (P, 900)).astype(np.uint32))
+    zeros = lambda nbytes: torch.zeros(nbytes, dtype=torch.uint8, device="cuda")
+    m12, ix2, new12 = zeros(P * stride * 4), zeros(P * stride * 4), zeros(P * stride * 4)
+    binfo, sinfo = zeros(P * 20), zeros(P * 20)
+    state, corr = zeros(P * orb.SIM3_STATE_DTYPE.itemsize), zeros(P * stride * orb.SIM3_CORR_DTYPE.itemsize)
+    res, inl = zeros(P * orb.SIM3_RESULT_DTYPE.itemsize), zeros(P * stride)
+    opt = zeros(P * orb.SIM3_OPT_RESULT_DTYPE.itemsize)
+    stream = torch.cuda.Stream()
+    sp = stream.cuda_stream
+
+    def bow(k=P):
+        m.search_by_bow_kf_batch(k, p_(k1s), p_(k2s), p_(d["keys"]), p_(d["desc"]), p_(d["nkeys"]),
+                                 p_(d["pidx"]), p_(d["fv_nodes"]), p_(d["fv_offs"]), p_(d["fv_feats"]),
+                                 p_(d["n_fv_nodes"]), stride, p_(dpts), 20, p_(m12), p_(ix2),
+                                 p_(binfo), stream=sp)
+
+    def setup():
+        m.sim3_solver_setup_batch(P, p_(k1s), p_(k2s), p_(d["keys"]), p_(d["nkeys"]), p_(d["pidx"]),
+                                  p_(d["pose"]), stride, p_(dpts), p_(m12), 0, p_(ix2), host["sigma2"],
+                                  cam, cam, False, p_(state), p_(corr), stream=sp)
+
+    def iterate():
+        m.sim3_solver_iterate_batch(P, stride, p_(state), p_(corr), p_(draws), 900, 5, p_(inl),
+                                    p_(res), stream=sp)
+
+    def search(k=P):
+        m.search_by_sim3_batch(k, p_(k1s), p_(k2s), p_(d["keys"]), p_(d["desc"]), p_(d["nkeys"]),
+                               p_(d["pidx"]), p_(d["pose"]), stride, p_(dpts), p_(ddesc), p_(m12),
+                               p_(ix2), p_(inl), p_(res), cam, bounds, host["scale"],
+                               float(host["log_scale"]), p_(sinfo), th=7.5, d_new12=p_(new12),
+                               stream=sp)
+
+    def optimise():
+        m.optimize_sim3_batch(P, p_(k1s), p_(k2s), p_(d["keys"]), p_(d["nkeys"]), p_(d["pidx"]),
+                              p_(d["pose"]), stride, p_(dpts), p_(m12), p_(ix2), p_(res),
+                              host["inv_sigma2"], cam, cam, p_(opt), th2=10.0, fix_scale=False,
+                              stream=sp)
+
+    def prep():             # the state a round starts from: BoW rows, a fresh solver, one iterate
+        bow(), setup(), iterate()
+
+    def events(before, fn, reps=20):
+        t = []
+        for _ in range(reps):
+            before()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            fn()
+            e1.record(stream)
+            torch.cuda.synchronize()
+            t.append(e0.elapsed_time(e1))
+        t.sort()
+        return {"median": t[len(t) // 2], "min": t[0], "max": t[-1]}
+
+    for _ in range(3):
+        prep(), search(), optimise()
+    torch.cuda.synchronize()
+    for k in (P, 16, 1):
+        tag = "" if k == P else str(k)
+        out[f"bow_kf_batch{tag}_ms"] = events(lambda: None, lambda k=k: bow(k))
+        out[f"search_by_sim3_batch{tag}_ms"] = events(prep, lambda k=k: search(k))
+    out["round_ms"] = events(lambda: (bow(), setup()), lambda: (iterate(), search(), optimise()))
+    out["bow_kf_one_per_call_over_batch"] = \
+        out["bow_kf_one_per_call_ms"]["median"] / out["bow_kf_batch_ms"]["median"]
+    out["search_by_sim3_one_per_call_over_batch"] = \
+        out["search_by_sim3_one_per_call_ms"]["median"] / out["search_by_sim3_batch_ms"]["median"]
+    # exact check of four problems: the BoW rows, then the search on the device's own Sim3
+    prep()
+    torch.cuda.synchronize()
+    host_of = lambda t, dt: t.cpu().numpy().view(dt)
+    g12, gx2 = (host_of(t, np.int32).reshape(P, stride).copy() for t in (m12, ix2))
+    gres = host_of(res, R.SIM3_RESULT_DTYPE).copy()
+    ginl = host_of(inl, np.uint8).reshape(P, stride).copy()
+    search()
+    torch.cuda.synchronize()
+    a12, ax2 = (host_of(t, np.int32).reshape(P, stride) for t in (m12, ix2))
+    gs = host_of(sinfo, R.SEARCH_INFO_DTYPE)
+    gb = host_of(binfo, R.B.INFO_DTYPE)
+    exact = True
+    for p in (0, 1, P // 2, P - 1):
+        exact &= np.array_equal(g12[p], rows[p][0]) and np.array_equal(gx2[p], rows[p][1])
+        exact &= tuple(int(v) for v in gb[p]) == rows[p][2]
+        if gres[p]["has_sim3"]:
+            want = R.sim3_expected(oracle, s1, sides[1 + p], points, mp_desc, g12[p], gx2[p],
+                                   ginl[p], gres[p], host)
+            exact &= np.array_equal(a12[p], want[0]) and np.array_equal(ax2[p], want[1])
+            exact &= tuple(int(v) for v in gs[p]) == want[3]
+    out.update(n_bow_matches_mean=float(gb["n_matches"].mean()),
+               n_with_sim3=int(gres["has_sim3"].sum()),
+               n_found_mean=float(gs["n_found"][gres["has_sim3"] != 0].mean()),
+               max_stride_bow_kf=orb.match_bow_kf_batch_max_stride(),
+               max_stride_search_by_sim3=orb.search_by_sim3_batch_max_stride(),
+               kernel_resources="k_bow_kf_batch: 46 VGPRs, 96 SGPRs, ScratchSize 16 B/lane, "
+                                "occupancy 8 waves/SIMD, 416 B static LDS; k_sim3_search_batch: "
+                                "59 VGPRs, 106 SGPRs, ScratchSize 0, occupancy 7 waves/SIMD, 640 B "
+                                "static LDS (hipcc -Rpass-analysis=kernel-resource-usage, gfx950)",
+               exact_vs_oracle=bool(exact))
+    return write("this_build")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--configs", default="C1,C2,C3,C5")
@@ -1396,6 +1598,8 @@ def main():
             r = n1(args, orb, oracle, torch)
         elif c == "G1":
             r = g1(args, orb, oracle, torch)
+        elif c == "L1":
+            r = l1(args, orb, oracle, torch)
         else:
             raise SystemExit(f"unknown config {c}")
         print(json.dumps(r), flush=True)
